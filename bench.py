@@ -54,6 +54,9 @@ def parse():
     ap.add_argument("--no-h2d", action="store_true", help="skip the secondary (PCIe-inclusive) timed loop")
     ap.add_argument("--dump-state", default=None, metavar="PATH",
                     help="after the timed loop write sha256 of the flat parameters / gradients (rank 0) to PATH")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed loop write what its last step computed (parameters, Adam moments, grad norm, "
+                         "BatchNorm statistics; rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--same-shard", action="store_true",
                     help="validation: every rank processes rank 0's frames (the rank mean then equals one rank's gradient)")
     ap.add_argument("--dense-head", action="store_true",
@@ -121,6 +124,37 @@ class HotPath(torch.nn.Module):
         bd = {"voxel_features": voxel_features, "voxel_coords": voxel_coords, "batch_size": batch_size}
         bd = self.map_to_bev_module(self.backbone_3d(self.vfe(bd)))
         return bd["spatial_features"], bd
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, W):
+    """`--dump-outputs`: what the timed step hands its caller -- the updated flat parameters, the Adam moments, the
+    gradient norm of the step and the BatchNorm running statistics -- as <path>/<name>.npy (float32; float64 stays
+    float64).  Above DUMP_BUDGET_BYTES in all, the large arrays are cut to a fixed seeded sample of their elements (the
+    same positions in every run with the same arguments)."""
+    def host(t):
+        t = t.detach()
+        return t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+
+    torch.cuda.synchronize()
+    arrays = {"parameters": host(W.flat_param), "adam_exp_avg": host(W.opt.exp_avg),
+              "adam_exp_avg_sq": host(W.opt.exp_avg_sq), "grad_norm": host(W.opt.grad_norm)}
+    stats = [host(b).ravel() for b in W.model.buffers() if b.is_floating_point()]
+    if stats:
+        arrays["batchnorm_stats"] = np.concatenate(stats)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        rng = np.random.default_rng(0)
+        keep = DUMP_BUDGET_BYTES / total * 0.99
+        for k, a in arrays.items():
+            if a.size > 4096:
+                idx = np.sort(rng.choice(a.size, int(a.size * keep), replace=False))
+                arrays[k] = a.ravel()[idx]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 TRAFFIC_FILE = os.path.join("profiles", "r06_pmc_traffic.json")
@@ -467,7 +501,9 @@ def selftest_launch(args, rank, world):
                           "allreduce_sum": float(t.item()), "frames": gathered, "slowest": slowest,
                           "bucket_MB": round(bucket.flat.numel() * 4 / 1e6, 2), "bucket_sum_ok": bucket_ok,
                           "steps": args.steps, "warmup": args.warmup}), flush=True)
-    dist.barrier()
+    # the closing barrier as an all-reduce of a CPU tensor: dist.barrier() asks the HIP runtime for its devices, which opens
+    # the GPU in every rank of a job that must not touch it
+    dist.all_reduce(torch.zeros(1))
     dist.destroy_process_group()
     whole.disarm()
 
@@ -1190,6 +1226,8 @@ def main():
         dist.all_gather(allt, t)
         rank_ms = [float(x.item()) for x in allt]
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, W)
     if args.dump_state and rank == 0:
         import hashlib
         torch.cuda.synchronize()

@@ -19,7 +19,7 @@ installed here.  So the fixtures come from the two independent sources that ARE 
 Nothing from /root/reference is copied: only inputs and outputs (data) are stored.  The CPU
 oracle (oracle/) is then checked against these files by tests/test_oracle_golden.py.
 
-Usage:  python tests/golden/make_golden.py [g1 .. g9]   (needs /root/reference; not needed at test time;
+Usage:  python tests/golden/make_golden.py [g1 .. g18]   (needs /root/reference; not needed at test time;
         with names only those fixtures are regenerated)
 """
 import hashlib
@@ -948,6 +948,27 @@ def g13():
          iou_dd=O.ref_boxes_iou_bev_cpu(d, d))
 
 
+def g18():
+    """The boxes of tests/test_iou3d.py::test_oracle_iou_against_the_compiled_reference_on_fresh_boxes (seed 131: 200 x 180
+    boxes, 20 axis-aligned against 20 at 90 degrees, 20 identical pairs) and the IoU matrix of the REFERENCE's compiled
+    iou3d_cpu.cpp on them (as G13), so that the test needs no compiled reference at test time."""
+    import subprocess
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle", "ref_build"), "-s"])
+    rng = np.random.default_rng(131)
+
+    def boxes(n, spread):
+        xy = rng.uniform(-spread, spread, (n, 2))
+        z = rng.uniform(-1, 1, (n, 1))
+        size = np.stack([rng.uniform(1.5, 5.5, n), rng.uniform(0.8, 2.4, n), rng.uniform(1.2, 2.2, n)], 1)
+        ang = rng.uniform(-np.pi, np.pi, (n, 1))
+        return np.concatenate([xy, z, size, ang], 1).astype(np.float32)
+    a, b = boxes(200, 9.0), boxes(180, 9.0)
+    a[:20, 6] = 0.0
+    b[:20, 6] = np.pi / 2
+    b[20:40] = a[20:40]
+    save("g18_iou3d_ref_fresh", boxes_a=a, boxes_b=b, iou_ab=O.ref_boxes_iou_bev_cpu(a, b))
+
+
 def g16():
     """The dense BEV stack by the REFERENCE's own modules: `BaseBEVBackbone` (pcdet/models/backbones_2d/
     base_bev_backbone.py:6-112, imported as it stands) followed by the conv towers of CenterHead -- `shared_conv` built as
@@ -1015,7 +1036,22 @@ def g17():
     """Host geometry of PV-RCNN's second stage by the REFERENCE's own functions, extracted from the files as they stand
     (the modules pull in compiled extensions / SharedArray): pcdet/utils/common_utils.py `rotate_points_along_z` (:35-54),
     `get_voxel_centers` (:66-82), voxel_set_abstraction.py `bilinear_interpolate_torch` (:11-44) and pvrcnn_head.py `get_global_grid_points_of_roi`
-    / `get_dense_grid_points` (:111-132)."""
+    / `get_dense_grid_points` (:111-132).
+
+    The grid points go through a batched 3 x 3 matmul, which MKL rounds differently on its AVX-512 code path and on the
+    AVX2 path it takes on other CPUs: `grid_global_mkl_avx2` is the same call in a child process with MKL held to AVX2."""
+    import subprocess
+    import tempfile
+    arrays = _g17_arrays()
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "g17_avx2.npz")
+        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--g17-arrays", out],
+                              env=dict(os.environ, MKL_ENABLE_INSTRUCTIONS="AVX2"))
+        arrays["grid_global_mkl_avx2"] = np.load(out)["grid_global"]
+    save("g17_stage2_geometry", **arrays)
+
+
+def _g17_arrays():
     import ast
     import textwrap
     csrc = open(os.path.join(REF, "pcdet/utils/common_utils.py")).read()
@@ -1055,18 +1091,21 @@ def g17():
     pts = torch.from_numpy(rng.standard_normal((4, 11, 5)).astype(np.float32))
     ang = torch.from_numpy(rng.uniform(-np.pi, np.pi, 4).astype(np.float32))
     rot = cns["rotate_points_along_z"](pts, ang)
-    save("g17_stage2_geometry", rois=rois, grid_global=glob.numpy(), grid_local=local.numpy(), coords=coords.numpy(),
-         centers=centers.numpy(), im=im.numpy(), bx=bx.numpy(), by=by.numpy(), interp=inter.numpy(), pts=pts.numpy(),
-         ang=ang.numpy(), rot=rot.numpy())
+    return dict(rois=rois, grid_global=glob.numpy(), grid_local=local.numpy(), coords=coords.numpy(),
+                centers=centers.numpy(), im=im.numpy(), bx=bx.numpy(), by=by.numpy(), interp=inter.numpy(), pts=pts.numpy(),
+                ang=ang.numpy(), rot=rot.numpy())
 
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--g17-arrays"]:      # (g17's child process: the arrays under the caller's MKL settings)
+        np.savez(sys.argv[2], **_g17_arrays())
+        sys.exit(0)
     only = set(sys.argv[1:])           # e.g. `make_golden.py g6`: regenerate just that fixture, keep the rest
     mpath = os.path.join(HERE, "MANIFEST.json")
     if only and os.path.exists(mpath):
         with open(mpath) as f:
             manifest.update(json.load(f))
-    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16, g17):
+    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16, g17, g18):
         if not only or fn.__name__ in only:
             fn()
     with open(mpath, "w") as f:

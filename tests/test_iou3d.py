@@ -107,14 +107,17 @@ def test_product_boxes_bev_iou_cpu_is_bit_identical_to_the_reference_fixture_g13
     assert iou3d_nms.boxes_bev_iou_cpu(g["boxes_a"][3:9, 0:7], np.ascontiguousarray(g["boxes_b"][::7])).shape[0] == 6
 
 
-@pytest.mark.skipif(not O.ref_iou3d_available(), reason="oracle/_ref/libiou3d_ref.so not built (needs /root/reference)")
-def test_oracle_iou_against_the_compiled_reference_on_fresh_boxes():
+def test_oracle_iou_against_the_compiled_reference_on_fresh_boxes(golden):
+    """G18 = the reference's compiled iou3d_cpu.cpp on these boxes (tests/golden/make_golden.py g18)."""
     rng = np.random.default_rng(131)
     a, b = _random_boxes(rng, 200, 9.0), _random_boxes(rng, 180, 9.0)
     a[:20, 6] = 0.0                                            # axis-aligned boxes: many collinear edges
     b[:20, 6] = np.pi / 2
     b[20:40] = a[20:40]                                        # identical pairs
-    np.testing.assert_array_equal(O.boxes_pairwise_bev(a, b, True), O.ref_boxes_iou_bev_cpu(a, b))
+    g = golden("g18_iou3d_ref_fresh")
+    np.testing.assert_array_equal(a, g["boxes_a"])
+    np.testing.assert_array_equal(b, g["boxes_b"])
+    np.testing.assert_array_equal(O.boxes_pairwise_bev(a, b, True), g["iou_ab"])
 
 
 def test_oracle_nms_is_greedy_suppression():
