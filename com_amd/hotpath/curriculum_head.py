@@ -7,78 +7,14 @@ Same constructor arguments, `forward(data_dict)` contract (`spatial_features_2d`
 the towers on the hand-written 3x3 conv kernels (bf16 channels-last), `cluster` / `assign_targets` / the curriculum
 loss on the device (com_head.py) and NMS through com_amd.iou3d_nms.  `self.epoch` is set by the training loop as in the
 reference (train_utils.py pushes it every epoch)."""
-import torch
 import torch.nn as nn
 
 from . import com_head
+from .center_head import BoxDecodeMixin, class_agnostic_nms, decode_bbox_from_heatmap  # noqa: F401
 from .dense2d import CenterHeadTowers, _get
-from .. import iou3d_nms
 
 
-def _topk(scores, K):
-    """centernet_utils.py:199-214"""
-    batch, num_class, height, width = scores.size()
-    topk_scores, topk_inds = torch.topk(scores.flatten(2, 3), K)
-    topk_inds = topk_inds % (height * width)
-    topk_ys = (topk_inds // width).float()
-    topk_xs = (topk_inds % width).int().float()
-    topk_score, topk_ind = torch.topk(topk_scores.view(batch, -1), K)
-    topk_classes = (topk_ind // K).int()
-    pick = lambda t: t.view(batch, -1).gather(1, topk_ind)
-    return topk_score, pick(topk_inds), topk_classes, pick(topk_ys), pick(topk_xs)
-
-
-def _gather_map(feat, inds):
-    """[B, C, H, W] at flat pixel indices [B, K] -> [B, K, C]  (centernet_utils.py:181-196)"""
-    B, C = feat.shape[0], feat.shape[1]
-    flat = feat.permute(0, 2, 3, 1).reshape(B, -1, C)
-    return flat.gather(1, inds.unsqueeze(2).expand(B, inds.shape[1], C))
-
-
-def decode_bbox_from_heatmap(heatmap, rot_cos, rot_sin, center, center_z, dim, point_cloud_range, voxel_size,
-                             feature_map_stride, K=100, score_thresh=None, post_center_limit_range=None, vel=None):
-    """centernet_utils.py:217-279 (circle_nms is `assert False` there: not offered).  Returns the per-frame list of
-    dicts pred_boxes [n, 7(+2)], pred_scores [n], pred_labels [n] (int32, 0-based class inside the head)."""
-    B = heatmap.shape[0]
-    scores, inds, class_ids, ys, xs = _topk(heatmap, K)
-    center = _gather_map(center, inds)
-    rot_sin, rot_cos = _gather_map(rot_sin, inds), _gather_map(rot_cos, inds)
-    center_z, dim = _gather_map(center_z, inds), _gather_map(dim, inds)
-    angle = torch.atan2(rot_sin, rot_cos)
-    xs = xs.view(B, K, 1) + center[:, :, 0:1]
-    ys = ys.view(B, K, 1) + center[:, :, 1:2]
-    xs = xs * feature_map_stride * voxel_size[0] + point_cloud_range[0]
-    ys = ys * feature_map_stride * voxel_size[1] + point_cloud_range[1]
-    parts = [xs, ys, center_z, dim, angle]
-    if vel is not None:
-        parts.append(_gather_map(vel, inds))
-    boxes = torch.cat(parts, dim=-1)
-    assert post_center_limit_range is not None
-    mask = (boxes[..., :3] >= post_center_limit_range[:3]).all(2) & (boxes[..., :3] <= post_center_limit_range[3:]).all(2)
-    if score_thresh is not None:
-        mask &= scores > score_thresh
-    return [{'pred_boxes': boxes[k, mask[k]], 'pred_scores': scores[k, mask[k]], 'pred_labels': class_ids[k, mask[k]]}
-            for k in range(B)]
-
-
-def class_agnostic_nms(box_scores, box_preds, nms_config, score_thresh=None):
-    """model_nms_utils.py:5-27 over com_amd.iou3d_nms (nms_gpu / nms_normal_gpu)."""
-    src = box_scores
-    if score_thresh is not None:
-        keep_mask = box_scores >= score_thresh
-        box_scores, box_preds = box_scores[keep_mask], box_preds[keep_mask]
-    selected = box_scores.new_zeros((0,), dtype=torch.int64)
-    if box_scores.shape[0] > 0:
-        top, indices = torch.topk(box_scores, k=min(int(_get(nms_config, 'NMS_PRE_MAXSIZE')), box_scores.shape[0]))
-        fn = getattr(iou3d_nms, _get(nms_config, 'NMS_TYPE'))
-        keep, _ = fn(box_preds[indices][:, 0:7].contiguous(), top, float(_get(nms_config, 'NMS_THRESH')))
-        selected = indices[keep[:int(_get(nms_config, 'NMS_POST_MAXSIZE'))]]
-    if score_thresh is not None:
-        selected = keep_mask.nonzero().view(-1)[selected]
-    return selected, src[selected]
-
-
-class CurriculumCenterHead(nn.Module):
+class CurriculumCenterHead(BoxDecodeMixin, nn.Module):
     conf_shape = None            # base class: FocalLossCenterCurriculum(conf_shape=None), curriculum_center_head.py:103-105
 
     def __init__(self, model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range, voxel_size,
@@ -125,49 +61,6 @@ class CurriculumCenterHead(nn.Module):
 
     def get_loss(self):
         return self.loss(self.forward_ret_dict['pred_dicts'], self.forward_ret_dict['target_dicts'], epoch=self.epoch)
-
-    def generate_predicted_boxes(self, batch_size, pred_dicts):
-        """curriculum_center_head.py:360-412"""
-        pp = _get(self.model_cfg, 'POST_PROCESSING')
-        nms_cfg = _get(pp, 'NMS_CONFIG')
-        dev = pred_dicts[0]['hm'].device
-        limit = torch.tensor(_get(pp, 'POST_CENTER_LIMIT_RANGE'), device=dev).float()
-        ret = [{'pred_boxes': [], 'pred_scores': [], 'pred_labels': []} for _ in range(batch_size)]
-        order = _get(self.separate_head_cfg, 'HEAD_ORDER')
-        for idx, pd in enumerate(pred_dicts):
-            f = lambda t: t.float()
-            finals = decode_bbox_from_heatmap(
-                heatmap=f(pd['hm']).sigmoid(), rot_cos=f(pd['rot'])[:, 0:1], rot_sin=f(pd['rot'])[:, 1:2],
-                center=f(pd['center']), center_z=f(pd['center_z']), dim=f(pd['dim']).exp(),
-                vel=f(pd['vel']) if 'vel' in order else None, point_cloud_range=self.point_cloud_range,
-                voxel_size=self.voxel_size, feature_map_stride=self.feature_map_stride,
-                K=_get(pp, 'MAX_OBJ_PER_SAMPLE'), score_thresh=_get(pp, 'SCORE_THRESH'), post_center_limit_range=limit)
-            mapping = torch.tensor(self.class_id_mapping_each_head[idx], device=dev)
-            for k, fd in enumerate(finals):
-                fd['pred_labels'] = mapping[fd['pred_labels'].long()]
-                if _get(nms_cfg, 'NMS_TYPE') != 'circle_nms':
-                    sel, sel_scores = class_agnostic_nms(fd['pred_scores'], fd['pred_boxes'], nms_cfg, score_thresh=None)
-                    fd['pred_boxes'], fd['pred_scores'], fd['pred_labels'] = fd['pred_boxes'][sel], sel_scores, fd['pred_labels'][sel]
-                for key in ret[k]:
-                    ret[k][key].append(fd[key])
-        for k in range(batch_size):
-            ret[k]['pred_boxes'] = torch.cat(ret[k]['pred_boxes'], dim=0)
-            ret[k]['pred_scores'] = torch.cat(ret[k]['pred_scores'], dim=0)
-            ret[k]['pred_labels'] = torch.cat(ret[k]['pred_labels'], dim=0) + 1
-        return ret
-
-    @staticmethod
-    def reorder_rois_for_refining(batch_size, pred_dicts):
-        """curriculum_center_head.py:394-412"""
-        num_max = max(1, max(len(d['pred_boxes']) for d in pred_dicts))
-        b0 = pred_dicts[0]['pred_boxes']
-        rois = b0.new_zeros((batch_size, num_max, b0.shape[-1]))
-        roi_scores = b0.new_zeros((batch_size, num_max))
-        roi_labels = b0.new_zeros((batch_size, num_max)).long()
-        for b in range(batch_size):
-            n = len(pred_dicts[b]['pred_boxes'])
-            rois[b, :n], roi_scores[b, :n], roi_labels[b, :n] = pred_dicts[b]['pred_boxes'], pred_dicts[b]['pred_scores'], pred_dicts[b]['pred_labels']
-        return rois, roi_scores, roi_labels
 
     def forward(self, data_dict):
         """curriculum_center_head.py:461-487"""

@@ -102,6 +102,78 @@ def _split_batch(batch):
     return batch
 
 
+class _LabelStage:
+    """The static ground-truth buffers of CapturedStep(batch_keys=...): `live` is what the step's graph reads, `pend` holds
+    the labels of the batch the last call handed over (one flat fp32 buffer each, a [B, max_gt, ...] view per key): one
+    launch moves pend -> live in front of a replay, one fill + one copy per key refill pend."""
+
+    def __init__(self, keys, batch_size, max_gt):
+        self.keys, self.B, self.max_gt = tuple(keys), int(batch_size), int(max_gt)
+        self.live = self.pend = None
+        self.shapes = None
+
+    def _rows(self, batch, k):
+        if not isinstance(batch, dict) or k not in batch:
+            raise ops.L.PcdError(f"CapturedStep: the batch carries no '{k}' (batch_keys {self.keys})")
+        t = batch[k]
+        if t.dim() < 2 or t.shape[0] != self.B:
+            raise ops.L.PcdError(f"CapturedStep: '{k}' must be [B={self.B}, n, ...], got {tuple(t.shape)}")
+        return t
+
+    def check(self, batch):
+        """Host-side capacity check (the row count is a shape: no device read)."""
+        for k in self.keys:
+            t = self._rows(batch, k)
+            if t.shape[1] > self.max_gt:
+                raise ops.L.PcdError(f"CapturedStep: '{k}' has {t.shape[1]} rows per frame, more than max_gt={self.max_gt}")
+            if self.shapes is not None and tuple(t.shape[2:]) != self.shapes[k][2:]:
+                raise ops.L.PcdError(f"CapturedStep: '{k}' trailing shape {tuple(t.shape[2:])}, the step holds "
+                                     f"{self.shapes[k][2:]}")
+
+    def padded(self, batch):
+        """Fresh zero-padded copies (eager steps)."""
+        self.check(batch)
+        out = {}
+        for k in self.keys:
+            t = batch[k]
+            z = torch.zeros((self.B, self.max_gt) + tuple(t.shape[2:]), dtype=torch.float32, device=t.device)
+            z[:, :t.shape[1]] = t
+            out[k] = z
+        return out
+
+    def allocate(self, example, dev):
+        self.check(example)
+        self.shapes = {k: (self.B, self.max_gt) + tuple(example[k].shape[2:]) for k in self.keys}
+        n = sum(int(torch.Size(sh).numel()) for sh in self.shapes.values())
+        self.live = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.pend = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.stage(example)
+        self.promote()
+
+    def _views(self, flat):
+        out, off = {}, 0
+        for k in self.keys:
+            sh = self.shapes[k]
+            n = int(torch.Size(sh).numel())
+            out[k] = flat[off:off + n].view(sh)
+            off += n
+        return out
+
+    def live_views(self):
+        return self._views(self.live)
+
+    def stage(self, batch):
+        views = self._views(self.pend)
+        if any(batch[k].shape[1] < self.max_gt for k in self.keys):
+            self.pend.zero_()
+        for k in self.keys:
+            t = batch[k]
+            views[k][:, :t.shape[1]].copy_(t, non_blocking=True)
+
+    def promote(self):
+        self.live.copy_(self.pend, non_blocking=True)
+
+
 class CapturedStep:
     """One training step of the hot path (module docstring).
 
@@ -116,10 +188,18 @@ class CapturedStep:
     hook_at      where the next batch's voxelisation may start inside the forward pass ("conv3": not before the main chain
                  has finished level 3 -- DESIGN.md 4.4; None: right behind the rulebook chain).
     after_update callables run right after the optimizer step, inside the step (default: the backbone's weight packs).
+    batch_keys   per-batch ground truth the heads read from batch_dict (e.g. "gt_boxes", the COM attributes
+                 "num_points_in_gt", "true_object", "occupancy_ratio", "facade_type"): [B, n, ...] float32 device tensors of
+                 each dict batch, zero-padded to `max_gt` rows (the reference's collate pads with zeros; class 0 is dropped by
+                 target assignment) into static buffers the captured graph reads.  Staged one call behind the points, as the
+                 step trains one batch behind: the labels a replay sees are those of the batch the previous call (or
+                 prime()) handed over.  A batch with more than `max_gt` rows raises before anything is enqueued.  Default:
+                 none -- nothing but the points is staged.
     """
 
     def __init__(self, model, model_func, optimizer, voxelize, batch_size, *, lr_scheduler=None, world=1, form="auto",
-                 hook_at="conv3", after_update=None, capture=True, margin=1.25, options=None, all_reduce=True):
+                 hook_at="conv3", after_update=None, capture=True, margin=1.25, options=None, all_reduce=True,
+                 batch_keys=(), max_gt=None):
         self.model, self.model_func, self.optimizer, self.vox_cfg = model, model_func, optimizer, voxelize
         self.bucket = optimizer.bucket
         self.batch_size, self.world, self.lr_scheduler = int(batch_size), int(world), lr_scheduler
@@ -147,6 +227,11 @@ class CapturedStep:
         self._pending = None            # eager mode: the batch handed over by the previous call
         self._g = {}
         self._example = None
+        self.batch_keys = tuple(batch_keys or ())
+        self.max_gt = None if max_gt is None else int(max_gt)
+        if self.batch_keys and self.max_gt is None:
+            raise ops.L.PcdError("CapturedStep: batch_keys need a capacity (max_gt)")
+        self._labels = _LabelStage(self.batch_keys, self.batch_size, self.max_gt) if self.batch_keys else None
 
     # ------------------------------------------------------------------ pieces of the step
     def _voxelize(self, pts, offs, out=None):
@@ -167,9 +252,13 @@ class CapturedStep:
             self.last_voxel_batch = bd2
         return bd2
 
-    def _forward_backward(self, bd2, hook=None):
+    def _forward_backward(self, bd2, hook=None, labels=None):
         """model_func -> loss.backward() (gradients land in the flat bucket) -> join of the weight-gradient stream"""
         bd = {k: v for k, v in bd2.items() if k != "_result"}
+        if labels is None and self._labels is not None and self._labels.live is not None:
+            labels = self._labels.live_views()               # (static buffers: what a captured step reads)
+        if labels:
+            bd.update(labels)
         if hook is not None:
             bd["after_rulebooks_hook"], bd["after_rulebooks_at"] = hook, self.hook_at
         out = self.model_func(self.model, bd)
@@ -200,11 +289,12 @@ class CapturedStep:
         """The whole step on `batch` with one launch per kernel from Python (observes the data-dependent row counts for
         the plan while it is not active)."""
         pts, offs = _split_batch(batch)
+        labels = self._labels.padded(batch) if self._labels is not None else None
         with self.plan, self.options:
             if ev is not None: ev("voxelize")
             bd2 = self._voxelize(pts, offs)
             if ev is not None: ev("forward")
-            self._forward_backward(bd2)
+            self._forward_backward(bd2, labels=labels)
             if ev is not None: ev("allreduce")
             self._exchange()
             if ev is not None: ev("optimizer")
@@ -224,6 +314,11 @@ class CapturedStep:
         """Capture the step for batches of up to `example_batch`'s row count.  `validate`: batches replayed right after the
         capture (two steps); a capacity overflow among them grows the plan (x 1.5) and captures again, up to `attempts`.
         pull (one-graph form only): an object with enqueue(s_pts, s_offs8) -- the graph itself fetches the next batch."""
+        report = getattr(self.model, "_com_amd_adopt_report", None)
+        if report is not None and report.unrecognised:
+            raise ops.L.PcdError(f"CapturedStep: the model has modules adopt_model() left unfused: {report.unrecognised}")
+        if self._labels is not None and (pull is not None or self.form == "three_graph"):
+            raise ops.L.PcdError("CapturedStep: batch_keys are staged by the one-graph and n_gt_1 forms only")
         self._example = example_batch
         for _ in range(attempts):
             self._build(example_batch, pull)
@@ -263,6 +358,8 @@ class CapturedStep:
         g["s_offs8"] = s_offs8 = torch.zeros(max(8, offs0.numel()), dtype=torch.int32, device=dev)
         s_offs8[:offs0.numel()] = offs0
         g["s_offs"] = s_offs = s_offs8[:offs0.numel()]       # (a view: the pull kernel writes the padded 32 bytes)
+        if self._labels is not None:
+            self._labels.allocate(example_batch, dev)        # (the warm-up steps below train on the example's labels)
         with plan, self.options:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -339,6 +436,8 @@ class CapturedStep:
         assert n <= g["s_pts"].shape[0], "batch has more rows than the example batch the step was captured for"
         (g["s_pts"] if n == g["s_pts"].shape[0] else g["s_pts"][:n]).copy_(pts, non_blocking=True)     # device -> device
         g["s_offs"].copy_(offs, non_blocking=True)           # (rows behind offs[-1] are never read)
+        if self._labels is not None:
+            self._labels.stage(batch)                        # -> pending: the replay of the NEXT call reads them
         if staged is not None:
             staged()                                         # the caller's buffers may be refilled from here on
 
@@ -346,6 +445,8 @@ class CapturedStep:
         """Hand over the FIRST batch of a loop: the first `step(next)` trains on it.  Captured forms voxelise it now (eager
         launches into the graph's own buffers), so that every loop -- and every execution form -- sees the batches in the
         same order 0, 1, 2, ..."""
+        if self._labels is not None:
+            self._labels.check(batch)
         if not self.captured:
             self._pending = batch
             if staged is not None:
@@ -377,6 +478,11 @@ class CapturedStep:
         """model_func + backward + clip + optimizer.step of the batch handed over by the previous call (or prime());
         `next_batch` is voxelised beside it for the next call.  `staged()` is called once the step no longer reads
         `next_batch`'s own buffers from the host's point of view (copies enqueued): H2D sources refill their slot there."""
+        if self._labels is not None:
+            if next_batch is not None:
+                self._labels.check(next_batch)               # on the host, before anything is enqueued
+            if self.captured:
+                self._labels.promote()                       # the previous call's labels -> the buffers this replay reads
         if not self.captured:
             batch, self._pending = self._pending, next_batch
             if staged is not None:
@@ -422,6 +528,74 @@ class CapturedStep:
             return ("hipGraph replay (ONE graph: fwd+bwd with the next batch voxelised mid-forward on the rulebook stream), "
                     "all-reduce, clip+Adam as plain launches" + tail)
         return "hipGraph replay (voxelise [prefetched one batch ahead] | fwd+bwd), all-reduce, clip+Adam" + tail
+
+
+COM_GT_KEYS = ("gt_boxes", "num_points_in_gt", "true_object", "occupancy_ratio", "facade_type")
+
+
+def model_fn_decorator():
+    """model_func of the reference's loop (pcdet/models/__init__.py:37-51) without the host -> device batch loading (the
+    step's batch_dict is on the device already): the detector's own forward -> (loss, tb_dict, disp_dict)."""
+    def model_func(model, batch_dict):
+        ret_dict, tb_dict, disp_dict = model(batch_dict)
+        loss = ret_dict['loss'].mean()
+        if hasattr(model, 'update_global_step'):
+            model.update_global_step()
+        return loss, tb_dict, disp_dict
+    return model_func
+
+
+def _cfg(cfg, key, default=None):
+    if isinstance(cfg, dict):
+        return cfg.get(key, default)
+    return getattr(cfg, key, default)
+
+
+def prepare_training(model, optim_cfg, total_iters, voxelize, batch_size, *, world=1, model_func=None, gt_keys="auto",
+                     max_gt=256, capture=True, **step_kw):
+    """(optimizer, lr_scheduler, step) for a model adopted with com_amd.adopt.adopt_model -- what build_optimizer /
+    build_scheduler (tools/train_utils/optimization/__init__.py:19-56) and bench.py's step assembly do:
+      * the flat-bucket parameter order: dense2d.batched_param_order when the model has centre-head branches (their
+        batched path), model.parameters() otherwise -- it fixes the reduction order of the clip norm, hence the bits;
+      * OPTIMIZATION (OPTIMIZER adam_onecycle: LR, WEIGHT_DECAY, MOMS, DIV_FACTOR, PCT_START, GRAD_NORM_CLIP) -> FlatAdam,
+        OneCycle with the schedule as a device table;
+      * after-update hooks: the backbone's weight packs, and the dense 3x3 packs (Conv3x3Packs) when a dense stack runs;
+      * gt_keys "auto": nothing without a dense head, gt_boxes for CenterHead, + the COM attributes for the curriculum
+        heads -- staged per batch into `max_gt`-row buffers (CapturedStep batch_keys).
+    model_func defaults to model_fn_decorator(); step_kw go to CapturedStep (form, hook_at, options, ...)."""
+    from . import adopt
+    from .hotpath import conv2d_fast, curriculum_head, dense2d
+    report = adopt.adopt_report(model)
+    if report is None:
+        raise ops.L.PcdError("prepare_training: adopt_model(model) first")
+    name = str(_cfg(optim_cfg, "OPTIMIZER", "adam_onecycle"))
+    if name != "adam_onecycle":
+        raise ops.L.PcdError(f"prepare_training: OPTIMIZER {name} (only adam_onecycle is fused)")
+    kw = dict(lr_max=float(_cfg(optim_cfg, "LR", 3e-3)), moms=tuple(float(m) for m in _cfg(optim_cfg, "MOMS", (0.95, 0.85))),
+              div_factor=float(_cfg(optim_cfg, "DIV_FACTOR", 10.0)), pct_start=float(_cfg(optim_cfg, "PCT_START", 0.4)))
+    model.train()
+    head = getattr(model, "dense_head", None)
+    if any(isinstance(m, dense2d.SeparateHead) for m in model.modules()):
+        params = [p for p in dense2d.batched_param_order(model) if p.requires_grad]
+    else:
+        params = [p for p in model.parameters() if p.requires_grad]
+    lr0, mom0 = cdist.one_cycle(0, total_iters, **kw)
+    optimizer = build_optimizer(params, lr=lr0, weight_decay=float(_cfg(optim_cfg, "WEIGHT_DECAY", 0.01)),
+                                moms=(mom0, kw["moms"][1]), grad_norm_clip=float(_cfg(optim_cfg, "GRAD_NORM_CLIP", 10.0)),
+                                world=world)
+    lr_scheduler = OneCycle(optimizer, total_iters, device_table=True, **kw)
+    after_update = []
+    if getattr(model, "backbone_3d", None) is not None and hasattr(model.backbone_3d, "pack_after_update"):
+        after_update.append(model.backbone_3d.pack_after_update)
+    if getattr(model, "backbone_2d", None) is not None or head is not None:
+        after_update.append(conv2d_fast.Conv3x3Packs(model).run)      # (after the parameters moved into the flat buffer)
+    if gt_keys == "auto":
+        gt_keys = () if head is None else \
+            COM_GT_KEYS if isinstance(head, curriculum_head.CurriculumCenterHead) else ("gt_boxes",)
+    step = CapturedStep(model, model_func or model_fn_decorator(), optimizer, voxelize, batch_size,
+                        lr_scheduler=lr_scheduler, world=world, after_update=after_update, capture=capture,
+                        batch_keys=tuple(gt_keys), max_gt=max_gt if gt_keys else None, **step_kw)
+    return optimizer, lr_scheduler, step
 
 
 def train_one_epoch(step, batches, total_it_each_epoch, accumulated_iter=0, poll_every=8, on_staged=None, gc_collect=True):
