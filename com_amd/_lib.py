@@ -212,6 +212,8 @@ PROTOTYPES = {
     "pcd_boxes_iou_bev_host": (_i, [_vp, _i, _vp, _i, _vp]),
     "pcd_nms_workspace_bytes": (_sz, [_i]),
     "pcd_nms_bev": (_i, [_vp, _i, ctypes.c_float, _i, _vp, _vp, _vp, _sz, _vp]),
+    "pcd_centerhead_postproc_workspace_bytes": (_sz, [_vp, _vp]),
+    "pcd_centerhead_postproc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pcd_bn_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                              _i, _vp, _vp, _sz, _vp]),
     "pcd_bn_backward_colsum_rows": (_i, [_i, _i, _i]),
@@ -247,6 +249,26 @@ COUNT_CHECK_MAX = 24
 class PcdCountCheck(ctypes.Structure):
     """include/pcd_ops.h: struct PcdCountCheck (static-shape overflow guard)."""
     _fields_ = [("count", ctypes.c_void_p * COUNT_CHECK_MAX), ("cap", ctypes.c_int32 * COUNT_CHECK_MAX)]
+
+
+POSTPROC_MAX_HEADS = 8     # include/pcd_ops.h: PCD_POSTPROC_MAX_HEADS
+POSTPROC_MAX_CLASSES = 16  # include/pcd_ops.h: PCD_POSTPROC_MAX_CLASSES
+POSTPROC_MAX_K = 4096      # include/pcd_ops.h: PCD_POSTPROC_MAX_K
+
+
+class PcdPostprocHead(ctypes.Structure):
+    """include/pcd_ops.h: struct PcdPostprocHead (the maps of one centre head)."""
+    _fields_ = [("map", ctypes.c_void_p * 6), ("strides", (ctypes.c_longlong * 4) * 6), ("dtype", ctypes.c_int * 6),
+                ("num_class", ctypes.c_int), ("label", ctypes.c_int * POSTPROC_MAX_CLASSES)]
+
+
+class PcdPostprocConfig(ctypes.Structure):
+    """include/pcd_ops.h: struct PcdPostprocConfig (POST_PROCESSING of a centre head)."""
+    _fields_ = [("batch", ctypes.c_int), ("num_heads", ctypes.c_int), ("height", ctypes.c_int), ("width", ctypes.c_int),
+                ("max_obj", ctypes.c_int), ("nms_pre", ctypes.c_int), ("nms_post", ctypes.c_int), ("nms_normal", ctypes.c_int),
+                ("use_score_thresh", ctypes.c_int), ("score_thresh", ctypes.c_float), ("nms_thresh", ctypes.c_float),
+                ("limit", ctypes.c_float * 6), ("feature_map_stride", ctypes.c_float), ("voxel_x", ctypes.c_float),
+                ("voxel_y", ctypes.c_float), ("pc_x", ctypes.c_float), ("pc_y", ctypes.c_float)]
 
 
 BN_MID_ROWS = 16          # include/pcd_ops.h: PCD_BN_MID_ROWS

@@ -96,6 +96,32 @@ def build_optimizer(params, lr=3e-3, weight_decay=0.01, moms=(0.95, 0.85), grad_
                           max_norm=grad_norm_clip, world=world, decoupled=True)
 
 
+def feature_stride(model, voxelize):
+    """The voxeliser emits the MeanVFE rows as the bf16 operand of the first conv: zero-padded to that conv's OUTPUT width
+    when it runs on the window tiles (conv_input 5 -> 16 over z-fastest rows), to the next power of two >= 8 otherwise (None)."""
+    backbone = getattr(model, "backbone_3d", None)
+    first = next((m for m in backbone.modules() if hasattr(m, "window_capable")), None) if backbone is not None else None
+    if first is not None and voxelize.row_order == "yxz" and first.in_channels < first.out_channels and first.window_capable():
+        return first.out_channels
+    return None
+
+
+def voxelize_batch(c, batch_size, feature_stride, pts, offs, out=None):
+    """Hard voxelisation + fused MeanVFE of one batch (what the reference's DataLoader workers do on the CPU) -> (the
+    voxeliser's dict, the batch_dict entries the model reads + "_result": the buffers `out` reuses)."""
+    bd = {"points": pts, "frame_offsets": offs, "batch_size": batch_size}
+    bd = hotpath.transform_points_to_voxels(bd, c.point_cloud_range, c.voxel_size, c.max_points_per_voxel, c.max_voxels,
+                                            fuse_mean=True, bf16_features=True,
+                                            out=out["_result"] if out is not None else None, row_order=c.row_order,
+                                            bf16_feature_stride=feature_stride)
+    bd2 = {"voxel_features": bd["voxel_features"], "voxel_coords": bd["voxel_coords"], "batch_size": batch_size,
+           "_result": bd["voxelize_result"]}
+    for k in ("voxel_num_rows", "voxel_rank"):
+        if k in bd:
+            bd2[k] = bd[k]               # device-side row count; coordinate -> row map (level-1 SubM without a hash table)
+    return bd, bd2
+
+
 def _split_batch(batch):
     if isinstance(batch, dict):
         return batch["points"], batch["frame_offsets"]
@@ -214,12 +240,7 @@ class CapturedStep:
         backbone = getattr(model, "backbone_3d", None)
         self.after_update = list(after_update) if after_update is not None else \
             ([backbone.pack_after_update] if backbone is not None else [])
-        # the voxeliser emits the MeanVFE rows as the bf16 operand of the first conv: zero-padded to that conv's OUTPUT width when
-        # it runs on the window tiles (conv_input 5 -> 16 over z-fastest rows), to the next power of two >= 8 otherwise
-        self.feature_stride = None
-        first = next((m for m in backbone.modules() if hasattr(m, "window_capable")), None) if backbone is not None else None
-        if first is not None and voxelize.row_order == "yxz" and first.in_channels < first.out_channels and first.window_capable():
-            self.feature_stride = first.out_channels
+        self.feature_stride = feature_stride(model, voxelize)
         self.captured = False
         self.recaptures = 0
         self.last_voxels = 0            # voxels of the last eagerly voxelised batch (reporting)
@@ -236,17 +257,7 @@ class CapturedStep:
     # ------------------------------------------------------------------ pieces of the step
     def _voxelize(self, pts, offs, out=None):
         """hard voxelisation + fused MeanVFE of one batch (what the reference's DataLoader workers do on the CPU)"""
-        c = self.vox_cfg
-        bd = {"points": pts, "frame_offsets": offs, "batch_size": self.batch_size}
-        bd = hotpath.transform_points_to_voxels(bd, c.point_cloud_range, c.voxel_size, c.max_points_per_voxel, c.max_voxels,
-                                                fuse_mean=True, bf16_features=True,
-                                                out=out["_result"] if out is not None else None, row_order=c.row_order,
-                                                bf16_feature_stride=self.feature_stride)
-        bd2 = {"voxel_features": bd["voxel_features"], "voxel_coords": bd["voxel_coords"], "batch_size": self.batch_size,
-               "_result": bd["voxelize_result"]}
-        for k in ("voxel_num_rows", "voxel_rank"):
-            if k in bd:
-                bd2[k] = bd[k]               # device-side row count; coordinate -> row map (level-1 SubM without a hash table)
+        bd, bd2 = voxelize_batch(self.vox_cfg, self.batch_size, self.feature_stride, pts, offs, out)
         if not self.plan.active:
             self.last_voxels = sum(bd["voxel_counts"])
             self.last_voxel_batch = bd2

@@ -908,6 +908,56 @@ int pcd_nms_bev(const float *boxes, int num_boxes, float thresh, int normal, lon
                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* ============================================================================================
+ * (f4) Static post-processing of CenterPoint-style heads -- replaces the eval half of the dense head:
+ *      CenterHead.generate_predicted_boxes (center_head.py:266-317) -> decode_bbox_from_heatmap (centernet_utils.py:199-257;
+ *      its two torch.topk calls at 199-214) -> class_agnostic_nms (model_nms_utils.py:15-27) -> nms_gpu / nms_normal_gpu
+ *      (iou3d_nms_utils.py:85-116).  Every (frame, head) pair of a batch in a fixed number of launches, no host read-back,
+ *      no allocation, grids from the shapes alone: capturable.
+ *   Maps of head h: hm [B, C_h, H, W], center [B, 2, H, W], center_z [B, 1, H, W], dim [B, 3, H, W] (log sizes),
+ *   rot [B, 2, H, W] (cos, sin), vel [B, 2, H, W] (NULL in every head or in none), f32 or bf16, arbitrary element strides
+ *   {batch, channel, y, x}; arithmetic in fp32.
+ *   Per frame and head:
+ *     select   the top K = max_obj scores over the whole C x H x W map (score = fp32 sigmoid of the map value) among the
+ *              pixels with score > score_thresh (when use_score_thresh).  ORDER: score descending, then flat index
+ *              c*H*W + y*W + x ascending -- a total order, ties included (torch.topk leaves ties unordered).
+ *     decode   x = ((x_px + center0) * feature_map_stride) * voxel_x + pc_x (y alike), z = center_z, dims = exp(dim),
+ *              heading = atan2(sin, cos), [vx, vy] -- the torch code's fp32 operations in its order.
+ *     mask     POST_CENTER_LIMIT_RANGE on x, y, z, inclusive on both ends; survivors keep the score order.
+ *     nms      greedy class-agnostic NMS over the first min(count, nms_pre) survivors with the geometry of pcd_nms_bev
+ *              (nms_normal: the axis-aligned IoU of nms_normal_gpu): same keep lists, bit for bit; then the first nms_post.
+ *   Outputs (per frame, heads concatenated in head order, M = num_heads * nms_post rows, zeros behind count):
+ *     boxes f32 [B, M, 7 | 9], scores f32 [B, M], labels int64 [B, M] (= head.label[c], i.e.
+ *     class_id_mapping_each_head[h][c] + 1), count int32 [B].
+ *   Refused (PCD_ERR_UNSUPPORTED; the workspace query returns 0): max_obj or nms_pre above PCD_POSTPROC_MAX_K (the
+ *   per-problem sort runs in LDS), more than PCD_POSTPROC_MAX_HEADS heads or PCD_POSTPROC_MAX_CLASSES classes in a head,
+ *   C * H * W or a map's element span beyond int32.  circle_nms has no entry (the reference asserts False).
+ *   workspace: pcd_centerhead_postproc_workspace_bytes(heads, cfg) bytes, 256-byte aligned.
+ * ============================================================================================ */
+#define PCD_POSTPROC_MAX_HEADS 8
+#define PCD_POSTPROC_MAX_CLASSES 16
+#define PCD_POSTPROC_MAX_K 4096
+typedef struct PcdPostprocHead {
+    const void *map[6];                       /* hm, center, center_z, dim, rot, vel (or NULL) */
+    long long strides[6][4];                  /* element strides {batch, channel, y, x} of each map */
+    int dtype[6];                             /* PCD_F32 | PCD_BF16 */
+    int num_class;                            /* C_h of hm */
+    int label[PCD_POSTPROC_MAX_CLASSES];      /* output label of class c of this head */
+} PcdPostprocHead;
+typedef struct PcdPostprocConfig {
+    int batch, num_heads, height, width;
+    int max_obj;                              /* MAX_OBJ_PER_SAMPLE */
+    int nms_pre, nms_post;                    /* NMS_PRE_MAXSIZE, NMS_POST_MAXSIZE */
+    int nms_normal;                           /* 0: nms_gpu, 1: nms_normal_gpu */
+    int use_score_thresh;
+    float score_thresh, nms_thresh;
+    float limit[6];                           /* POST_CENTER_LIMIT_RANGE */
+    float feature_map_stride, voxel_x, voxel_y, pc_x, pc_y;
+} PcdPostprocConfig;
+size_t pcd_centerhead_postproc_workspace_bytes(const PcdPostprocHead *heads, const PcdPostprocConfig *cfg);
+int pcd_centerhead_postproc(const PcdPostprocHead *heads, const PcdPostprocConfig *cfg, float *boxes, float *scores,
+                            long long *labels, int32_t *count, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ============================================================================================
  * Static-shape execution guard.  Buffers of a captured step are allocated at CAPACITIES (see "Device-side row
  * counts" above) and the kernels clamp to them, so a batch denser than the capacity would be truncated silently.
  * pcd_static_overflow_check enqueues a one-thread kernel that compares up to PCD_COUNT_CHECK_MAX device-side counts

@@ -1,0 +1,160 @@
+"""Inference frames/s of the adopted stock CenterPoint detector (tools/stock_detector.py "centerpoint") at Waymo size
+(B = 4 x 160 k synth points), three forms in one process, timed alternately (synchronised host clock per batch):
+
+  eager_reference   model.eval() + no_grad, voxelise -> module_list forward -> the existing eager post-processing
+                    (generate_predicted_boxes -> class_agnostic_nms -> nms_gpu): the reference's eval loop body
+                    (tools/eval_utils/eval_utils.py:58-80) on the fused modules
+  eager_static      the same forward, static post-processing (com_amd.postprocess) instead
+  captured          com_amd.infer.CapturedInference replays (voxelise + forward + static post-processing, one graph)
+
+plus the post-processing alone on one batch's head maps, eager vs static.  Writes JSON to --out (profiles/infer_fps.json).
+
+    python tools/exp_infer.py [--batches 200] [--out profiles/infer_fps.json]
+    python tools/exp_infer.py --replay-only          (capture, pause, ONE replay: for rocprofv3 --kernel-trace --stats)
+    python tools/exp_infer.py --kernel-table <kernel_trace.csv>    (host only: the kernels of that last replay as a table)
+"""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def _short(name):
+    """kernel name without its parameter list (the parenthesis matching the final one)"""
+    if name.endswith(")"):
+        depth = 0
+        for i in range(len(name) - 1, -1, -1):
+            depth += {")": 1, "(": -1}.get(name[i], 0)
+            if depth == 0:
+                name = name[:i]
+                break
+    return name.replace("(anonymous namespace)::", "")[:110]
+
+
+def kernel_table(path):
+    """Kernels of the last burst of a rocprofv3 kernel trace (the replay after --replay-only's pause), in launch order."""
+    rows = list(csv.DictReader(open(path)))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    start = 0
+    for i in range(1, len(rows)):
+        if int(rows[i]["Start_Timestamp"]) - int(rows[i - 1]["End_Timestamp"]) > 200_000_000:     # > 0.2 s gap
+            start = i
+    rows = rows[start:]
+    t0, t1 = int(rows[0]["Start_Timestamp"]), max(int(r["End_Timestamp"]) for r in rows)
+    lines = [f"one CapturedInference replay: {len(rows)} kernels, {(t1 - t0) / 1e6:.3f} ms first start -> last end",
+             f"{'start_us':>9} {'dur_us':>8}  kernel"]
+    agg = {}
+    for r in rows:
+        s, e = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
+        name = _short(r["Kernel_Name"])
+        lines.append(f"{(s - t0) / 1e3:9.1f} {(e - s) / 1e3:8.1f}  {name}")
+        a = agg.setdefault(name, [0, 0])
+        a[0] += 1
+        a[1] += e - s
+    lines += ["", "by kernel (sum of durations):", f"{'calls':>5} {'sum_us':>9}  kernel"]
+    for name, (n, d) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
+        lines.append(f"{n:5d} {d / 1e3:9.1f}  {name}")
+    return "\n".join(lines)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--batches", type=int, default=200, help="timed batches per form")
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "infer_fps.json"))
+    ap.add_argument("--replay-only", action="store_true")
+    ap.add_argument("--kernel-table")
+    a = ap.parse_args()
+    if a.kernel_table:
+        print(kernel_table(a.kernel_table))
+        return
+
+    import torch
+    import stock_detector as SD
+    from com_amd import hotpath, postprocess, train
+    from com_amd.adopt import adopt_model
+    from com_amd.infer import CapturedInference
+    from com_amd.utils import synth
+
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    B = a.batch
+    model = SD.build_detector("centerpoint").to(dev)
+    adopt_model(model)
+    batches = [hotpath.collate_points([synth.synth_cloud(B * i + f) for f in range(B)], dev) for i in range(3)]
+    vox = train.VoxelizeConfig(synth.WAYMO_RANGE, synth.WAYMO_VOXEL, synth.WAYMO_MAX_POINTS, synth.WAYMO_MAX_VOXELS)
+    inf = CapturedInference(model, vox, B)
+    inf.capture(batches[0], validate=batches[1:])
+    if a.replay_only:
+        torch.cuda.synchronize()
+        time.sleep(1.0)
+        inf(batches[1])
+        torch.cuda.synchronize()
+        print("replay-only: one replay done")
+        return
+
+    fs = train.feature_stride(model, vox)
+    head = model.dense_head
+
+    def eager(batch, static):
+        pts, offs = batch
+        model.eval()
+        with torch.no_grad():
+            bd = train.voxelize_batch(vox, B, fs, pts, offs)[1]
+            bd = {k: v for k, v in bd.items() if k != "_result"}
+            if static:
+                bd["static_predictions"] = True
+            for m in model.module_list:
+                bd = m(bd)
+        return bd["final_box_tensors"] if static else bd["final_box_dicts"]
+
+    forms = {"eager_reference": lambda b: eager(b, False), "eager_static": lambda b: eager(b, True),
+             "captured": lambda b: inf(b)}
+    # the post-processing alone, on the head maps of one eager forward
+    eager(batches[0], True)
+    maps = [{k: v.clone() for k, v in pd.items()} for pd in head.forward_ret_dict["pred_dicts"]]
+    post = {"post_eager": lambda b: head.generate_predicted_boxes(B, maps),
+            "post_static": lambda b: postprocess.decode_predictions_static(maps, head)}
+    times = {k: [] for k in list(forms) + list(post)}
+    allf = dict(forms, **post)
+    for name, fn in allf.items():
+        for i in range(a.warmup):
+            fn(batches[i % 3])
+    torch.cuda.synchronize()
+    rounds, per = 10, max(1, a.batches // 10)
+    for r in range(rounds):
+        for name, fn in allf.items():
+            for i in range(per):
+                t0 = time.perf_counter()
+                fn(batches[(r * per + i) % 3])
+                torch.cuda.synchronize()
+                times[name].append(time.perf_counter() - t0)
+    inf.check()
+    res = {"unit": "ms per batch (median over timed batches), frames/s = B / median", "device": torch.cuda.get_device_name(0),
+           "batch": B, "points_per_frame": int(batches[0][0].shape[0] // B), "timed_batches_per_form": rounds * per,
+           "warmup": a.warmup, "clock": "host perf_counter around each call + torch.cuda.synchronize()",
+           "model": "tools/stock_detector.py centerpoint, adopt_model(), fresh weights (every pixel passes SCORE_THRESH)"}
+    for name, ts in times.items():
+        ts = sorted(ts)
+        med = ts[len(ts) // 2]
+        res[name] = {"ms_median": round(med * 1e3, 3), "ms_p10": round(ts[len(ts) // 10] * 1e3, 3),
+                     "ms_p90": round(ts[(9 * len(ts)) // 10] * 1e3, 3)}
+        if name in forms:
+            res[name]["frames_per_s"] = round(B / med, 1)
+    res["captured_over_eager_reference"] = round(res["eager_reference"]["ms_median"] / res["captured"]["ms_median"], 3)
+    print(json.dumps(res, indent=1))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
