@@ -691,20 +691,18 @@ __global__ __launch_bounds__(256, 2) void conv2d_wgrad_kernel(const unsigned sho
 }
 
 
-// Weight gradients of the plane operators (pcd_conv2d_planes_nhwc): the same tile / transposing-read machinery as
+// Weight gradients of the transposed plane operators (pcd_conv2d_planes_nhwc): the same tile / transposing-read machinery as
 // conv2d_wgrad_kernel with the A operand taken from the FINE map plane by plane (stride-2 pixel addressing, the plane's
-// 1 / 2 / 4 taps as LDS row offsets) and the B operand from the coarse map, staged once per tile:
-//   C3S2  A = x (fine), B = dy (coarse)               -> slabs [cout][9][cin]
+// tap as an LDS row offset) and the B operand from the coarse map, staged once per tile:
 //   K2S2  A = dy (fine), B = x (coarse)                -> slabs [cin][4][cout]   (the ConvTranspose2d parameter's layout)
 //   K1    A = dy, B = x, one plane, one tap            -> slabs [cin][1][cout]
 template <int KIND, int NBW>
-__global__ __launch_bounds__(256, KIND == K_C3S2 ? 1 : 2) void conv2d_wgrad_planes_kernel(
+__global__ __launch_bounds__(256, 2) void conv2d_wgrad_planes_kernel(
     const unsigned short *__restrict__ xa, int Ha, int Wa, int ca, const unsigned short *__restrict__ xb, int B, int Hc,
     int Wc, int cb, int n_splits, int n_chunks, int n_cb_chunks, float *__restrict__ slab, unsigned a_bytes,
     unsigned b_bytes) {
     constexpr int NP = pl_count<KIND>(), ST = pl_step<KIND>(), NT = taps_total<KIND>(), KW = kernel_w<KIND>();
-    constexpr int HL = KIND == K_C3S2 ? 1 : 0;                                   // halo (low and high side)
-    constexpr int AH = WG_TH + 2 * HL, AW = WG_TW + 2 * HL;
+    constexpr int AH = WG_TH, AW = WG_TW;                                      // (one tap per plane: no halo)
     constexpr int CO = NBW * 16, YS = WgYs<CO>::value;
     constexpr int XP = AH * AW * 8, YP = WG_TH * WG_TW * (CO / 8);
     constexpr int XI = (XP + 255) / 256, YI = (YP + 255) / 256;
@@ -743,7 +741,7 @@ __global__ __launch_bounds__(256, KIND == K_C3S2 ? 1 : 2) void conv2d_wgrad_plan
             const int p = it * 256 + threadIdx.x;
             const int pix = p >> 3, piece = p & 7;
             const int hy = pix / AW, hx = pix - hy * AW;
-            const int gy = (ty * WG_TH + hy - HL) * ST + py, gx = (tx * WG_TW + hx - HL) * ST + px;
+            const int gy = (ty * WG_TH + hy) * ST + py, gx = (tx * WG_TW + hx) * ST + px;
             const bool ok = p < XP && tile < n_tiles && gy >= 0 && gy < Ha && gx >= 0 && gx < Wa;
             const unsigned off = ok ? (unsigned)((((size_t)b * Ha + gy) * Wa + gx) * ca * 2 + (ca0 + piece * 8) * 2)
                                     : 0xFFFFFFF0u;
@@ -803,8 +801,7 @@ __global__ __launch_bounds__(256, KIND == K_C3S2 ? 1 : 2) void conv2d_wgrad_plan
 #pragma unroll
                 for (int tx_ = 0; tx_ < nx; ++tx_) {
                     const int dy = ax_d<KIND, true>(py, ty_), dx = ax_d<KIND, true>(px, tx_);
-                    const bf16x8 af = frag(xs + ((s + HL + dy) * AW + trow + HL + dx) * WG_XS + wave * 16 + (t & 3) * 4,
-                                           16 * WG_XS);
+                    const bf16x8 af = frag(xs + ((s + dy) * AW + trow + dx) * WG_XS + wave * 16 + (t & 3) * 4, 16 * WG_XS);
 #pragma unroll
                     for (int nb = 0; nb < NBW; ++nb)
                         acc[base + ty_ * nx + tx_][nb] =
@@ -933,29 +930,20 @@ extern "C" int pcd_conv2d_3x3_nhwc_bn(const void *x, int x_cs, int batch, int he
     const double xb = ((double)batch * height * width - 1) * x_cs * 2 + (double)cin * 2;
     if (xb >= 4294966000.0) return PCD_ERR_UNSUPPORTED;
     const size_t wb_bytes = (size_t)((cout + 63) / 64) * (cin / 32) * W_BYTES;   // bytes of the pack the kernel reads
-    const int wb = pcd_opt(PCD_OPT_CONV2D_WB);   // (1: 28-35 % of the MFMA peak, 2: 21-27 %)
-    const size_t lds = 2 * (size_t)IN_BYTES + (size_t)(wb == 1 ? 1 : 2) * (size_t)W_BYTES;
+    // (one weight stage: 28-35 % of the MFMA peak; double-buffered weights, one workgroup per CU: 21-27 %)
+    const size_t lds = 2 * (size_t)IN_BYTES + (size_t)W_BYTES;
     static bool raised = false;
     if (!raised) {
-        if (hipFuncSetAttribute((const void *)conv2d_3x3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(2 * IN_BYTES + 2 * W_BYTES)) != hipSuccess ||
-            hipFuncSetAttribute((const void *)conv2d_3x3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(2 * IN_BYTES + W_BYTES)) != hipSuccess)
+        if (hipFuncSetAttribute((const void *)conv2d_3x3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+            hipSuccess)
             return PCD_ERR_LAUNCH;
         raised = true;
     }
     const int tiles = batch * ((height + TP - 1) / TP) * ((width + TP - 1) / TP);
     dim3 grid((unsigned)tiles, (unsigned)((cout + 63) / 64));
-    if (wb == 1)
-        conv2d_3x3_kernel<1><<<grid, 256, lds, (hipStream_t)stream>>>((const unsigned short *)x, batch, height, width, cin,
-                                                                     (const uint4 *)packed_w, cout, bias,
-                                                                     (unsigned short *)y, (unsigned)xb, (unsigned)wb_bytes,
-                                                                     x_cs, y_cs, bn);
-    else
-        conv2d_3x3_kernel<2><<<grid, 256, lds, (hipStream_t)stream>>>((const unsigned short *)x, batch, height, width, cin,
-                                                                     (const uint4 *)packed_w, cout, bias,
-                                                                     (unsigned short *)y, (unsigned)xb, (unsigned)wb_bytes,
-                                                                     x_cs, y_cs, bn);
+    conv2d_3x3_kernel<1><<<grid, 256, lds, (hipStream_t)stream>>>((const unsigned short *)x, batch, height, width, cin,
+                                                                 (const uint4 *)packed_w, cout, bias, (unsigned short *)y,
+                                                                 (unsigned)xb, (unsigned)wb_bytes, x_cs, y_cs, bn);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }
@@ -1071,17 +1059,14 @@ extern "C" int pcd_conv2d_wgrad_3x3_nhwc(const void *x, int x_cs, const void *dy
 }
 
 
-// Weight gradient of the plane operators (forward pack modes 2 / 4 / 6 of pcd_conv2d_planes_nhwc).  `fine` / `coarse`: the
-// two maps of the layer ([b][hf][wf][cf] and [b][hc][wc][cc] bf16, contiguous) -- mode 2: x / dy; modes 4, 6: dy / x.
-// Slabs [cc][k * k][cf] f32 (finish with pcd_sparse_conv_wgrad_reduce_batched: kvol = k * k, cin = cf, cout = cc, layout 1
-// gives the torch parameter's layout for all three: Conv2d [cout][cin][3][3], ConvTranspose2d [cin][cout][k][k]).
+// Weight gradient of the plane operators (forward pack modes 4 / 6 of pcd_conv2d_planes_nhwc: the ConvTranspose2d layers).
+// `fine` / `coarse`: the two maps of the layer, dy / x ([b][hf][wf][cf] and [b][hc][wc][cc] bf16, contiguous).  Slabs
+// [cc][k * k][cf] f32 (finish with pcd_sparse_conv_wgrad_reduce_batched: kvol = k * k, cin = cf, cout = cc, layout 1 gives
+// the ConvTranspose2d parameter's layout [cin][cout][k][k]).  Mode 2, the stride-2 conv (9 accumulator sets + 4 plane
+// stagings per tile, one workgroup per CU), measured SLOWER than the pair kernels over dense pair lists (99-152 vs 80 us):
+// not covered.
 extern "C" int pcd_conv2d_wgrad_planes_splits(int mode, int batch, int hc, int wc, int cf, int cc) {
-    if ((mode != 2 && mode != 4 && mode != 6) || batch <= 0 || hc <= 0 || wc <= 0 || cf <= 0 || cc <= 0 || cf % 64 || cc % 32)
-        return 0;
-    // mode 2 (stride-2 conv: 9 accumulator sets + 4 plane stagings per tile, one workgroup per CU) measures SLOWER than the
-    // pair kernels over dense pair lists (99-152 vs 80 us, tools/exp_wgrad_planes.py): not offered unless asked for
-    const int mode2 = pcd_opt(PCD_OPT_CONV2D_WGP_MODE2);
-    if (mode == 2 && !mode2) return 0;
+    if ((mode != 4 && mode != 6) || batch <= 0 || hc <= 0 || wc <= 0 || cf <= 0 || cc <= 0 || cf % 64 || cc % 32) return 0;
     const int tiles = batch * ((hc + WG_TH - 1) / WG_TH) * ((wc + WG_TW - 1) / WG_TW);
     const int chunks = (cf / 64) * (cc % 64 == 0 ? cc / 64 : cc / 32);
     const int target = pcd_opt(PCD_OPT_CONV2D_WGP_BLOCKS);
@@ -1095,10 +1080,9 @@ extern "C" int pcd_conv2d_wgrad_planes_splits(int mode, int batch, int hc, int w
 template <int KIND, int NBW>
 static void launch_wgrad_planes(const void *fine, int hf, int wf, int cf, const void *coarse, int batch, int hc, int wc, int cc,
                                 int splits, void *slabs, hipStream_t st) {
-    constexpr int HL = KIND == K_C3S2 ? 1 : 0;
     const int n_cc = cc / (NBW * 16), chunks = (cf / 64) * n_cc;
     const int grid = (splits * chunks + 7) / 8 * 8;
-    const size_t lds = (size_t)((WG_TH + 2 * HL) * (WG_TW + 2 * HL) * WG_XS + WG_TH * WG_TW * WgYs<NBW * 16>::value) * 2;
+    const size_t lds = (size_t)(WG_TH * WG_TW * WG_XS + WG_TH * WG_TW * WgYs<NBW * 16>::value) * 2;
     conv2d_wgrad_planes_kernel<KIND, NBW><<<grid, 256, lds, st>>>(
         (const unsigned short *)fine, hf, wf, cf, (const unsigned short *)coarse, batch, hc, wc, cc, splits, chunks, n_cc,
         (float *)slabs, (unsigned)((size_t)batch * hf * wf * cf * 2), (unsigned)((size_t)batch * hc * wc * cc * 2));
@@ -1110,10 +1094,8 @@ extern "C" int pcd_conv2d_wgrad_planes_nhwc(int mode, const void *fine, int hf, 
     const int splits = pcd_conv2d_wgrad_planes_splits(mode, batch, hc, wc, cf, cc);
     if (splits <= 0) return PCD_ERR_UNSUPPORTED;
     if (!fine || !coarse || !slabs) return PCD_ERR_INVALID_ARG;
-    const int kk = mode == 2 ? 9 : (mode == 4 ? 4 : 1);
-    if (mode == 2 ? (hc != (hf - 1) / 2 + 1 || wc != (wf - 1) / 2 + 1)
-                  : (mode == 4 ? (hf != 2 * hc || wf != 2 * wc) : (hf != hc || wf != wc)))
-        return PCD_ERR_INVALID_ARG;
+    const int kk = mode == 4 ? 4 : 1;
+    if (mode == 4 ? (hf != 2 * hc || wf != 2 * wc) : (hf != hc || wf != wc)) return PCD_ERR_INVALID_ARG;
     if (slab_bytes < (size_t)splits * cc * kk * cf * sizeof(float)) return PCD_ERR_WORKSPACE;
     if ((double)batch * hf * wf * cf * 2 >= 4294966000.0 || (double)batch * hc * wc * cc * 2 >= 4294966000.0)
         return PCD_ERR_UNSUPPORTED;
@@ -1122,7 +1104,7 @@ extern "C" int pcd_conv2d_wgrad_planes_nhwc(int mode, const void *fine, int hf, 
 #define PCD_WGP(K)                                                                                                      \
     if (wide) launch_wgrad_planes<K, 4>(fine, hf, wf, cf, coarse, batch, hc, wc, cc, splits, slabs, st);                \
     else launch_wgrad_planes<K, 2>(fine, hf, wf, cf, coarse, batch, hc, wc, cc, splits, slabs, st);
-    if (mode == 2) { PCD_WGP(K_C3S2) } else if (mode == 4) { PCD_WGP(K_K2S2) } else { PCD_WGP(K_K1) }
+    if (mode == 4) { PCD_WGP(K_K2S2) } else { PCD_WGP(K_K1) }
 #undef PCD_WGP
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;

@@ -1806,7 +1806,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(RedJobs J) {
 // splits = ranges of INPUT rows (pmax = number of input rows = row stride of `pairs`)
 // (layers that are cut into >= 4 channel chunks already have 4x the workgroups: twice the rows per split there,
 // measured 79 -> 72 us at 128 x 128 channels)
-static bool wgrad128_enabled() { return pcd_opt(PCD_OPT_WG128) != 0; }
 static int wgrad128_chunks() {   // equal-pair chunks of wgrad128_kernel: two workgroups per CU
     // (768 = three per CU was the isolated optimum; in the step 512 wins by 0.6 % -- 3.424 vs 3.447 ms, 384 / 640: 3.436 /
     //  3.451 -- a third less tile traffic for the reduction: 512 x 64 KiB per layer)
@@ -1814,7 +1813,8 @@ static int wgrad128_chunks() {   // equal-pair chunks of wgrad128_kernel: two wo
     if (v < 8) v = 8;
     return (v + 7) / 8 * 8;
 }
-static bool wgrad128_use(int cin, int cout) { return cin == 128 && cout == 128 && wgrad128_enabled(); }
+// (option "wg128" = 0: the generic kernel -- the only one for 128 x 128 layers with padded x rows, kvol > 343 or the class form)
+static bool wgrad128_use(int cin, int cout) { return cin == 128 && cout == 128 && pcd_opt(PCD_OPT_WG128) != 0; }
 
 static void wgrad_plan(int pmax, int cin, int cout, int *splits, int *rows_per_split) {
     const int chunks = pcd_div_up(cin, 64) * pcd_div_up(cout, 64);
@@ -1926,45 +1926,37 @@ static int gg_dispatch(const void *x, int n_rows_in, int c_in, const void *packe
     // whole step 4.32 -> 4.19 ms at B = 4.  4 steps ahead, 16 or 64 rows per wave, or 4-step weight stages are
     // slower (4.21-4.63); choosing 16 rows per wave for layers with few rows (< 48k) was also slower
     // (B = 1 / 2: 432 / 676 -> 457 / 712 frames/s without that rule).
-    // Wide layers (C_in = 64 / 128, C_out = 64 / 128): the LDS-DMA kernel (ggw_kernel).  Rows per workgroup follow the
-    // row count so that the tiles of the LARGEST layers of a level fill the 256 CUs in whole rounds.
-    const int ggw_mode = pcd_opt(PCD_OPT_GGW);
+    // Wide layers (C_in = 128, C_out = 64 / 128): the LDS-DMA kernel (ggw_kernel).  Rows per workgroup follow the row count
+    // so that the tiles of the LARGEST layers of a level fill the 256 CUs in whole rounds.
     // (C_in = 64: measured equal to the fragment-loading kernel, 55 us at 115 k rows -- both at the texture-address
-    //  limit of one 1-KiB instruction per ~32 clk; only PCD_GGW >= 2 routes it here)
+    //  limit of one 1-KiB instruction per ~32 clk)  Option "ggw" = 0 keeps C_in = 128 on the generic kernel: the only one
+    // for packed tables and for kernel volumes whose ggw tiles need more than 160 KB of LDS (kvol > 52).
+    const bool wide = pcd_opt(PCD_OPT_GGW) && c_in == 128 && (c_out == 64 || c_out == 128) && x_bytes <= 0xFFFF0000u;
     const bool is_dgrad = dir_hint >= 0 ? dir_hint != 0 : (flip_k || (bnr && bnr->mode == 2));
     if (tiles_only && tiles_only[0] == -12345) {       // variant query (pcd_sparse_conv_gather_gemm_variant)
-        const int m = pcd_opt(PCD_OPT_GGW);
-        tiles_only[0] = (m && (c_in == 128 || (c_in == 64 && m >= 2 && m <= 4)) && (c_out == 64 || c_out == 128) &&
-                         x_bytes <= 0xFFFF0000u && !(is_dgrad && m == 6)) ? 1 : 0;
+        tiles_only[0] = wide ? 1 : 0;
         return PCD_OK;
     }
-    // PCD_GGW: 0 = off, 1 = on (default), 2..4 = on with MI rows-per-wave forced (also for C_in = 64), 6 = forward only
-    if (ggw_mode && (c_in == 128 || (c_in == 64 && ggw_mode >= 2 && ggw_mode <= 4)) && (c_out == 64 || c_out == 128) &&
-        x_bytes <= 0xFFFF0000u && !(is_dgrad && ggw_mode == 6)) {
+    if (wide) {
         if (nbr_packed) return PCD_ERR_UNSUPPORTED;        // (the LDS-DMA kernel stages full tables only)
         const unsigned w_bytes = (unsigned)wbytes;
-        int mi = (ggw_mode >= 2 && ggw_mode <= 4) ? ggw_mode : ((c_in == 128 && n_rows_out <= 256 * 192 * 5 / 4) ? 3 : 2)   /* (capacities are 1.25 x the row counts) */;
+        int mi = n_rows_out <= 256 * 192 * 5 / 4 ? 3 : 2;   /* (capacities are 1.25 x the row counts) */
         // SubM 3x3x3 over z-fastest rows at 128 -> 128 channels: x through windows (ggwin_kernel; same tiles, same BatchNorm rows)
 #ifdef PCD_EXPERIMENTS
-        if (zfast && !tiles_only && pcd_opt(PCD_OPT_GGWIN) && c_in == 128 && c_out == 128 && kvol == 27 && mi == 3)
+        if (zfast && !tiles_only && pcd_opt(PCD_OPT_GGWIN) && c_out == 128 && kvol == 27 && mi == 3)
             return launch_ggwin<8, 3>(x, packed_w, bias, nbr, nbr_stride, flip_k, n_rows_out, n_rows_out_dev, y, y_dtype, x_bytes,
                                       w_bytes, st, addend, bnr);
 #endif
         // Few rows (one round of 128-row tiles fits the chip): the FORWARD conv takes 128-row tiles -- 36-38 us isolated against
         // 42-44 at 21-32 k rows (tools/exp_ggw.py) and nothing runs beside levels 3-4 of the forward pass; the data gradient
         // keeps 192 rows: its workgroups leave ~45 % of the CUs to the weight-gradient kernel running beside it, and with
-        // 128-row tiles everywhere the training step was 7 % SLOWER (3.35 against 3.12 ms).  Option "ggw_mi": 2 / 3 = forced.
+        // 128-row tiles everywhere the training step was 7 % SLOWER (3.35 against 3.12 ms).
         // (not with option "ggwin": that kernel and its tile count are built on 192 rows)
-        if (mi == 3 && !is_dgrad && c_in == 128 && n_rows_out <= 256 * 128 * 5 / 4 && !pcd_opt(PCD_OPT_GGWIN)) mi = 2;
-        if (pcd_opt(PCD_OPT_GGW_MI) == 2 || pcd_opt(PCD_OPT_GGW_MI) == 3) mi = pcd_opt(PCD_OPT_GGW_MI);
+        if (mi == 3 && !is_dgrad && n_rows_out <= 256 * 128 * 5 / 4 && !pcd_opt(PCD_OPT_GGWIN)) mi = 2;
 #define GGW_ARGS x, packed_w, bias, nbr, nbr_stride, kvol, flip_k, n_rows_out, n_rows_out_dev, y, y_dtype, x_bytes, w_bytes, st, addend, bnr, tiles_only
-        // two consumer waves per SIMD (ggw_kernel CW = 2) at 128 -> 128, 192-row tiles: option "ggw_cw" (1 = the one-consumer form)
-        if (c_in == 128 && c_out == 128 && mi == 3 && pcd_opt(PCD_OPT_GGW_CW) == 2) return launch_ggw<8, 2, 3, 3, 2>(GGW_ARGS);
-#define GGW_MI(NBV, SOFFV)                                                         \
-        (mi == 3 ? launch_ggw<NBV, SOFFV, 3, 3>(GGW_ARGS) : launch_ggw<NBV, SOFFV, 2, 3>(GGW_ARGS))
-        if (c_in == 64) return c_out == 64 ? GGW_MI(4, 1) : GGW_MI(8, 1);
-        return c_out == 64 ? GGW_MI(4, 2) : GGW_MI(8, 2);
-#undef GGW_MI
+        // 128 -> 128 with 192-row tiles: two consumer waves per SIMD (ggw_kernel CW = 2)
+        if (c_out == 128) return mi == 3 ? launch_ggw<8, 2, 3, 3, 2>(GGW_ARGS) : launch_ggw<8, 2, 2, 3>(GGW_ARGS);
+        return mi == 3 ? launch_ggw<4, 2, 3, 3>(GGW_ARGS) : launch_ggw<4, 2, 2, 3>(GGW_ARGS);
 #undef GGW_ARGS
     }
     const int flip_arg = (flip_k ? 1 : 0) | (nbr_packed ? 2 : 0);     // (the kernel's `flip` argument: bit 0 = flipped k, bit 1 = packed table)
@@ -1973,25 +1965,14 @@ static int gg_dispatch(const void *x, int n_rows_in, int c_in, const void *packe
         case 1: {
             // 16 channels (level 1).  With key-ordered voxel rows (pcd_voxelize_hard_sorted) 32 rows per wave and one
             // step of look-ahead win: whole step 3.46 -> 3.42 ms (<1,2,2,0> 3.43, <1,4,*,0> 3.47-3.48, <1,1,1/4,0> 3.46);
-            // rows in first-appearance order preferred <1,1,2,0> (PCD_GG1=0).
-            const int v1 = pcd_opt(PCD_OPT_GG1);
-            if (resident) return v1 ? launch_gg<1, 2, 1, 0>(GG_ARGS) : launch_gg<1, 1, 2, 0>(GG_ARGS);
-            return launch_gg<1, 1, 2, 4>(GG_ARGS);
+            // rows in first-appearance order preferred <1,1,2,0>.
+            return resident ? launch_gg<1, 2, 1, 0>(GG_ARGS) : launch_gg<1, 1, 2, 4>(GG_ARGS);
         }
         case 2:
             // (32 channels, staged: <2,2,2,2> / <2,2,2,4> / <2,4,2,2> / <2,2,4,4> / <2,4,1,2> measured 4.20-4.34 vs 4.18)
-            if (resident) {
-                // (the one resident 32-output-channel layer left on this kernel is the strided 16 -> 32 conv: option "gg2"
-                //  selects look-ahead / rows per wave for it)
-                switch (pcd_opt(PCD_OPT_GG2)) {
-                    case 1: return launch_gg<2, 2, 2, 0>(GG_ARGS);
-                    case 2: return launch_gg<2, 1, 2, 0>(GG_ARGS);
-                    case 3: return launch_gg<2, 4, 1, 0>(GG_ARGS);
-                    case 4: return launch_gg<2, 1, 4, 0>(GG_ARGS);
-                    default: return launch_gg<2, 2, 1, 0>(GG_ARGS);
-                }
-            }
-            return launch_gg<2, 2, 1, 2>(GG_ARGS);
+            // (the one resident 32-output-channel layer left on this kernel is the strided 16 -> 32 conv: <2,2,2,0>, <2,1,2,0>,
+            //  <2,4,1,0>, <2,1,4,0> measured within the noise of <2,2,1,0>)
+            return resident ? launch_gg<2, 2, 1, 0>(GG_ARGS) : launch_gg<2, 2, 1, 2>(GG_ARGS);
         case 4:
             return resident ? launch_gg<4, 2, 2, 0>(GG_ARGS) : launch_gg<4, 2, 2, 2>(GG_ARGS);
         case 8:
@@ -2148,7 +2129,7 @@ extern "C" int pcd_sparse_conv_wgrad_v2(const void *x, int n_x, const int32_t *n
 // the input rows (pcd_rulebook_conv_cm_build / pcd_rulebook_conv_classes: perm, vstart_dev) and the neighbour table nbr_in
 // [kvol][nbr_stride] (see WgClasses).  Same slabs, same reduction job (pcd_sparse_conv_wgrad_reduce*, pmax = n_x) and -- the
 // pairs being the same pairs in the same order, plus zero rows where an output is missing -- the same values as
-// pcd_sparse_conv_wgrad_v2 over the rulebook's pair lists, to fp32 summation order.  kvol <= 27; not for 128 x 128 channels (PCD_ERR_UNSUPPORTED).
+// pcd_sparse_conv_wgrad_v2 over the rulebook's pair lists, to fp32 summation order.  kvol <= 27; not for 128 x 128 channels (PCD_ERR_UNSUPPORTED) unless option "wg128" = 0.
 extern "C" int pcd_sparse_conv_wgrad_classes(const void *x, int n_x, const int32_t *n_x_dev, int cin_pad, int cin,
                                              const void *dy, int n_dy, int cout, const int32_t *nbr_in, int nbr_stride,
                                              const int *ksize_host, const int *stride_host, const int *dil_host,

@@ -454,6 +454,8 @@ __global__ __launch_bounds__(256) void vox_emit_kernel(
     int cx, cy, cz;
     voxel_coord(xyz, G, cx, cy, cz);
     if (cw) {      // z-fastest rows through the column map: first row of the BEV column + the set z bits below
+                   // (unreachable since the option that selected this per-point form was retired: the column-map
+                   //  voxeliser always emits through vox_emit_rows_kernel; kept so that this kernel's code is unchanged)
         const u32 key = bev_key(b, cy, cx, G.gy, pitch);
         const int col = cm_col(cw[key >> 5], key, ncol_cap);
         if (col < 0) return;                       // (column beyond the capacity: its rows are dropped like any row beyond it)
@@ -918,28 +920,21 @@ static int voxelize_hard_impl(const float *points, int n_points, int point_strid
             PCD_RETURN_IF_LAUNCH_FAILED();
         }
     }
-    if (n_points > 0 && cm && pcd_opt(PCD_OPT_VOX_EMIT_ROWS)) {
+    if (n_points > 0 && cm) {
         // (256 columns ~ 800 rows per workgroup, three rows per thread one after the other: 118 us in the graph and a step of
         //  3.07 ms; 64 columns per workgroup -- one row per thread, four times the workgroups -- 74 us and 3.11 ms: the kernel runs
         //  beside level 2 of the forward pass, and what it costs the step is the CUs it takes from the window kernels there, not
         //  its own duration.  The per-point form: 66 us, 3.09 ms.)
-#define VOX_EMIT_ROWS(COLS)                                                                                                   \
-    vox_emit_rows_kernel<COLS><<<pcd_div_up(CB.ncol_cap, COLS), 256, 0, st>>>(                                                 \
-        points, point_stride, feat_offset, num_features, G, max_points, L, keys, best, tcap - 1, voxels, coords, num_points,   \
-        mean_f32, (unsigned short *)mean_bf16, mean_bf16_stride, cap, CB.cr, colkey, CB.ncols, CB.ncol_cap, CB.pitch)
-        switch (pcd_opt(PCD_OPT_VOX_EMIT_ROWS)) {        // (option value = columns per workgroup; 1 = 256)
-            case 64: VOX_EMIT_ROWS(64); break;
-            case 128: VOX_EMIT_ROWS(128); break;
-            default: VOX_EMIT_ROWS(256); break;
-        }
-#undef VOX_EMIT_ROWS
+        vox_emit_rows_kernel<256><<<pcd_div_up(CB.ncol_cap, 256), 256, 0, st>>>(
+            points, point_stride, feat_offset, num_features, G, max_points, L, keys, best, tcap - 1, voxels, coords, num_points,
+            mean_f32, (unsigned short *)mean_bf16, mean_bf16_stride, cap, CB.cr, colkey, CB.ncols, CB.ncol_cap, CB.pitch);
     } else if (n_points > 0) {
         vox_emit_kernel<<<nb, 256, 0, st>>>(points, n_points, point_stride, feat_offset,
                                             num_features, frame_offsets, batch, G, max_points, L, best,
                                             pt_slot, rank, frame_rank0, frame_base, voxel_counts,
                                             voxels, coords, num_points, mean_f32,
                                             (unsigned short *)mean_bf16, mean_bf16_stride, cap, bitmap, chunk_prefix,
-                                            cm ? CB.cw : nullptr, cm ? CB.cr : nullptr, cm ? CB.ncol_cap : 0, cm ? CB.pitch : 0);
+                                            nullptr, nullptr, 0, 0);
     }
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;

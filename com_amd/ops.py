@@ -1675,9 +1675,9 @@ def conv2d_wgrad(x, dy, cout=None, out=None, defer=None):
     return dw
 
 
-# Dense weight-gradient kernels for the plane operators (stride-2 conv, deconvs): built, bit-checked against the pair
-# kernels -- and NOT faster in the step (tools/exp_wgp_blocks.sh: 7.81-7.85 vs 7.79 ms with the pair kernels; isolated the
-# k = stride deconvs gain, 31 / 60 vs 76 us at 512 workgroups, the stride-2 conv loses, 99 vs 80 us): off unless asked for.
+# Dense weight-gradient kernels for the plane operators (deconvs): built, bit-checked against the pair kernels -- and NOT
+# faster in the step (tools/exp_wgp_blocks.sh: 7.81-7.85 vs 7.79 ms with the pair kernels; isolated the k = stride deconvs
+# gain, 31 / 60 vs 76 us at 512 workgroups; the stride-2 conv's form lost, 99 vs 80 us, and is not built): off unless asked for.
 CONV2D_WGRAD_PLANES = False
 
 
@@ -1686,14 +1686,15 @@ def conv2d_wgrad_planes_splits(mode_f, B, hc, wc, cf, cc):
 
 
 def conv2d_wgrad_planes(mode_f, fine, coarse, out=None, defer=None):
-    """dW of the plane operators in the torch parameter's layout (f32): mode 2 (Conv2d 3 / stride 2): fine = x, coarse = dy
-    -> [cout, cin, 3, 3]; modes 4 / 6 (ConvTranspose2d k = stride = 2 / 1): fine = dy, coarse = x -> [cin, cout, k, k].
-    Both maps [B, h, w, c] bf16 contiguous.  Caller checks conv2d_wgrad_planes_splits(...) > 0 first."""
+    """dW of the transposed plane operators in the torch parameter's layout (f32): modes 4 / 6 (ConvTranspose2d
+    k = stride = 2 / 1): fine = dy, coarse = x -> [cin, cout, k, k] (the stride-2 Conv2d, mode 2, is not covered: its
+    weight gradient runs on the pair kernels).  Both maps [B, h, w, c] bf16 contiguous.  Caller checks
+    conv2d_wgrad_planes_splits(...) > 0 first."""
     _require_cuda(fine, coarse)
     assert fine.dtype == torch.bfloat16 and coarse.dtype == torch.bfloat16 and fine.is_contiguous() and coarse.is_contiguous()
     B, hf, wf, cf = fine.shape
     _, hc, wc, cc = coarse.shape
-    k = {2: 3, 4: 2, 6: 1}[mode_f]
+    k = {4: 2, 6: 1}[mode_f]
     lib = L.lib()
     splits = lib.pcd_conv2d_wgrad_planes_splits(mode_f, B, hc, wc, cf, cc)
     assert splits > 0

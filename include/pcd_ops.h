@@ -73,8 +73,8 @@ int pcd_stream_capture_id(void *stream, unsigned long long *id_out);
  * Explicit and inspectable (no environment reads anywhere in the library): pcd_set_option returns PCD_ERR_INVALID_ARG for an
  * unknown key.  Process-wide, not synchronised: set them before the first call that uses them.  (No reference counterpart.)
  *   "gg_resident_kb" 32   packed weight up to this size stays resident in LDS in gather_gemm_kernel
- *   "ggw" 1               LDS-DMA gather-GEMM for C_in = 128 (0 off, 2..4: rows-per-wave forced also for C_in = 64, 6: forward only)
- *   "gg1" 1               16-channel gather-GEMM variant (1: 32 rows per wave)
+ *   "ggw" 1               LDS-DMA gather-GEMM (ggw_kernel) for C_in = 128, C_out = 64 / 128 (0: gather_gemm_kernel, the only
+ *                         kernel for those widths over a packed table or with kvol > 52)
  *   "subm_window" 23      window gather-GEMM for SubM 3x3x3 layers over PCD_ROWS_YXZ rows: bit 0 = 64 channels, bit 1 = 32,
  *                         bit 2 = 16, bit 3 = 128 (EXPERIMENTS builds; off: its dense 27-offset MFMA work makes it slower than the
  *                         step-skipping generic kernel there, 61.6 vs 49.0 us), bit 4 = layers with FEWER input than output
@@ -82,14 +82,11 @@ int pcd_stream_capture_id(void *stream, unsigned long long *id_out);
  *                         (0: generic kernels) -- read by the host-side layer, the C entry points take any of these widths
  *   "subm_window_wgrad" 6 the same bits for the window weight gradient (pcd_sparse_conv_subm_window_wgrad); 64 channels off:
  *                         its 80 partial slabs (35 MB per layer) cost the training step more than the kernel saves
- *   "wg128" 1             equal-pair weight-gradient kernel at 128 x 128 channels
+ *   "wg128" 1             equal-pair weight-gradient kernel at 128 x 128 channels (0: the generic kernel, the only one there
+ *                         for padded x rows (cin_pad != 128), kvol > 343 and pcd_sparse_conv_wgrad_classes)
  *   "wg128_chunks" 512    its workgroup count
  *   "wg_rows" 6144        row-range split of the generic weight-gradient kernel
- *   "conv2d_wb" 1, "conv2d_wg_blocks" 128, "conv2d_wgp_mode2" 0, "conv2d_wgp_blocks" 512   dense 3x3 conv variants
- *   "vox_emit_rows" 1     pcd_voxelize_hard_yxz writes its output rows in row order (a workgroup per 256 columns of the map; 64 / 128:
- *                         that many columns per workgroup; 0 = one thread per point, rows scattered: the round-4 form, same results)
- *   "ggw_cw" 2            consumer waves per SIMD of the wide gather-GEMM at 128 -> 128 channels, 192-row tiles (1 = one, the round-4 form)
- *   "ggw_mi" 0            rows per workgroup / 64 of the wide gather-GEMM: 0 = by rule (forward convs of small levels 2, else 3), 2 / 3 forced
+ *   "conv2d_wg_blocks" 128, "conv2d_wgp_blocks" 512   workgroups of the dense 3x3 / plane weight-gradient kernels
  *   "fps_g" 0             workgroups per frame of the cooperative farthest point sampling (0: from the device's CU count)
  *   "gg_dbg" 0, "ggw_dbg" 0, "win_dbg" 0   ablation bit masks of the gather-GEMM kernels (profiling only)
  *   "ggwin" 0             (EXPERIMENTS build only, pcd_ops_experiments.h) 1: 128 -> 128 SubM layers through ggwin_kernel
@@ -97,6 +94,7 @@ int pcd_stream_capture_id(void *stream, unsigned long long *id_out);
  *                         bit 2 = 16 channels.  Set it before the first plan is built: plans, packs and launches of a width must agree
  *   "subm_window_grid" 256   workgroups of a window launch (a multiple of 8, <= 256); fewer leave CUs to other streams --
  *                         measured: no gain (240 / 224 / 192: 0 / -0.5 / -1 % in the step)
+ *   "vox_grid" 0          workgroup cap of the voxeliser's point passes (hash insert; column-map marks) (0: one per 256 points)
  *   "cm_direct_blocks" 4096   column-map builds: up to this many scan blocks add up the block sums themselves, beyond it a
  *                             spine launch runs (tests lower it to reach the spine path on small inputs) */
 int pcd_set_option(const char *key, int value);
@@ -519,7 +517,7 @@ int pcd_sparse_conv_wgrad_v2(const void *x, int n_x, const int32_t *n_x_dev, int
  * the pairs of offset k are {(i, nbr_in[k][i]) : i in class(k)} -- read off `perm` / `vstart_dev` (pcd_rulebook_conv_cm_build /
  * pcd_rulebook_conv_classes) and nbr_in [kvol][nbr_stride]; a missing output gathers a zero row.  Same workspace
  * (pcd_sparse_conv_wgrad_workspace_bytes(kvol, cin, cout, n_x)), same reduction (pmax = n_x); the result equals
- * pcd_sparse_conv_wgrad_v2's over the rulebook's pair lists to fp32 summation order (a cut output holds a slot with a zero row).  kvol <= 27, at most 8 classes, not 128 x 128 channels. */
+ * pcd_sparse_conv_wgrad_v2's over the rulebook's pair lists to fp32 summation order (a cut output holds a slot with a zero row).  kvol <= 27, at most 8 classes, not 128 x 128 channels (unless option "wg128" = 0). */
 int pcd_sparse_conv_wgrad_classes(const void *x, int n_x, const int32_t *n_x_dev, int cin_pad, int cin, const void *dy,
                                   int n_dy, int cout, const int32_t *nbr_in, int nbr_stride, const int *ksize_host,
                                   const int *stride_host, const int *dil_host, const int32_t *perm,
@@ -1025,9 +1023,10 @@ int pcd_conv2d_3x3_nhwc_bn(const void *x, int x_cs, int batch, int height, int w
 int pcd_conv2d_wgrad_3x3_splits(int batch, int height, int width, int cin, int cout);
 int pcd_conv2d_wgrad_3x3_nhwc(const void *x, int x_cs, const void *dy, int batch, int height, int width, int cin, int cout,
                               void *slabs, size_t slab_bytes, void *stream);
-/* ... and of the plane operators below (forward pack modes 2 / 4 / 6): `fine` / `coarse` = the layer's two maps (mode 2: x / dy;
- * modes 4, 6: dy / x), contiguous bf16; slabs [cc][k * k][cf] f32 -> pcd_sparse_conv_wgrad_reduce_batched (kvol = k * k,
- * cin = cf, cout = cc, layout 1 = the torch parameter's layout for Conv2d AND ConvTranspose2d).  cf % 64 == 0, cc % 32 == 0. */
+/* ... and of the transposed plane operators below (forward pack modes 4 / 6; mode 2, the stride-2 conv, is not covered:
+ * 0 splits, use the pair form): `fine` / `coarse` = the layer's two maps (dy / x), contiguous bf16; slabs [cc][k * k][cf] f32
+ * -> pcd_sparse_conv_wgrad_reduce_batched (kvol = k * k, cin = cf, cout = cc, layout 1 = the ConvTranspose2d parameter's
+ * layout).  cf % 64 == 0, cc % 32 == 0. */
 int pcd_conv2d_wgrad_planes_splits(int mode, int batch, int hc, int wc, int cf, int cc);
 int pcd_conv2d_wgrad_planes_nhwc(int mode, const void *fine, int hf, int wf, int cf, const void *coarse, int batch, int hc,
                                  int wc, int cc, void *slabs, size_t slab_bytes, void *stream);

@@ -32,6 +32,24 @@ def test_library_exports_every_declared_symbol():
     assert lib.pcd_error_string(-3).decode().startswith("batch")
 
 
+def test_header_lists_exactly_the_tuning_options_of_the_library():
+    """The option list in pcd_ops.h names the same keys as the table in capi.hip, and the library accepts each of them."""
+    from com_amd import _lib
+    header = open(os.path.join(ROOT, "include", "pcd_ops.h")).read()
+    block = header[header.index("---- tuning options"):header.index("int pcd_set_option(")]
+    listed = set(re.findall(r'^ \*   (?:"[a-z0-9_]+" -?\d+,? ?)*"([a-z0-9_]+)" -?\d+', block, flags=re.M))
+    listed |= set(re.findall(r'"([a-z0-9_]+)" -?\d+,', block))
+    capi = open(os.path.join(ROOT, "com_amd", "csrc", "capi.hip")).read()
+    table = capi[capi.index("g_opts[PCD_OPT_COUNT]"):]
+    table = table[:table.index("};")]
+    keys = set(re.findall(r'\{"([a-z0-9_]+)", -?\d+\}', table))
+    assert len(keys) >= 10 and listed == keys, (sorted(listed - keys), sorted(keys - listed))
+    value = ctypes.c_int()
+    for key in keys:
+        assert _lib.lib().pcd_get_option(key.encode(), ctypes.byref(value)) == 0, key
+    assert _lib.lib().pcd_get_option(b"no_such_option", ctypes.byref(value)) != 0
+
+
 def test_experiment_kernels_stay_out_of_the_default_library():
     """include/pcd_ops_experiments.h declares the entry points of the measured-slower kernels; the DEFAULT build must not export
     them (they are compiled only by `make EXPERIMENTS=1` into com_amd/lib_experiments/), the ctypes layer binds them when present."""

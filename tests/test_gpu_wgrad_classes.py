@@ -269,6 +269,45 @@ def test_compact_strided_tables_feed_all_three_kernels_and_expand_to_the_full_ta
     assert ran >= 14
 
 
+def test_128_channel_switches_reach_the_generic_kernels(pcd_option):
+    """Options "ggw" / "wg128" = 0 send 128-channel layers to the generic kernels, the only ones for a packed output-side table
+    (ggw_kernel stages full tables: PCD_ERR_UNSUPPORTED) and for the weight-gradient forms wgrad128_kernel does not take:
+    the packed forward then equals the default kernel over the full table bit for bit, the generic weight gradient equals
+    wgrad128_kernel to fp32 summation order."""
+    from com_amd import ops, _lib as L
+    rng = np.random.default_rng(128)
+    D, H, W, batch = 21, 48, 64, 2
+    idx = np.unique(np.stack([rng.integers(0, batch, 8000), rng.integers(0, D, 8000), rng.integers(0, H, 8000),
+                              rng.integers(0, W, 8000)], 1).astype(np.int32), axis=0)
+    idx_t = torch.from_numpy(_sorted_yxz(idx)).to(DEV)
+    n = idx_t.shape[0]
+    cmap = ops.colmap_from_rows(idx_t, batch, [D, H, W])
+    geo = dict(k=(3, 3, 3), s=(2, 2, 2), p=(1, 1, 1))
+    m = O.rulebook_conv(idx, (D, H, W), geo["k"], geo["s"], geo["p"])["n_out"]
+    full, comp = _compact_pair(ops, idx_t, batch, (D, H, W), geo, cmap, None, ("conv", "c128"), m + 50)
+    assert comp.nbr_out_packed is not None
+    g = torch.Generator(device="cpu").manual_seed(7)
+    x = torch.randn((n, 128), generator=g).to(DEV).bfloat16()
+    w = (torch.randn((128, 27, 128), generator=g) * 0.05).to(DEV)
+    pf = ops.pack_weight(w, 0)
+    assert ops.gather_gemm_is_wide(n, 128, 27, full.n_out, 128)
+    y_wide = ops.gather_gemm(x, pf, None, full.nbr_out, 27, False, full.n_out, 128, torch.bfloat16, n_dev=full.n_out_dev)
+    with pytest.raises(L.PcdError):
+        ops.gather_gemm(x, pf, None, comp.nbr_out_packed, 27, False, comp.n_out, 128, torch.bfloat16, n_dev=comp.n_out_dev,
+                        nbr_packed=True)
+    pcd_option("ggw", 0)
+    assert not ops.gather_gemm_is_wide(n, 128, 27, full.n_out, 128)
+    y_packed = ops.gather_gemm(x, pf, None, comp.nbr_out_packed, 27, False, comp.n_out, 128, torch.bfloat16,
+                               n_dev=comp.n_out_dev, nbr_packed=True)
+    assert torch.equal(y_wide[:m].view(torch.int16), y_packed[:m].view(torch.int16))
+    dy = torch.randn((full.n_out, 128), generator=g).to(DEV).bfloat16()
+    dw_eq = ops.wgrad(x, 128, dy, None, None, 27, rb=full)
+    pcd_option("wg128", 0)
+    dw_gen = ops.wgrad(x, 128, dy, None, None, 27, rb=full)
+    assert bool(torch.isfinite(dw_gen).all())
+    assert float((dw_eq - dw_gen).abs().max()) <= 2e-5 * (float(dw_eq.abs().max()) + 1e-6)
+
+
 def test_profile_records_of_a_compact_build_count_the_same_pairs(monkeypatch):
     """ops.PROFILE (what bench.py's eager leg and tools/regime.py read): the record of a compact build carries the pair count of
     the full build (taken from the packed table's presence bits), the packed forward's record too."""
