@@ -7,11 +7,13 @@ VoxelResBackBone8x forward (9 rulebook builds, 21 sparse convs, BN/ReLU/residual
 BEV scatter -> loss -> backward (dgrad + wgrad of every conv, BEV gather) -> DDP gradient all-reduce
 (N > 1, RCCL over xGMI) -> grad-norm clip (centerpoint.yaml:96) -> Adam step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` (dominant kernel,
-timed live with HIP events on the launch stream) and, at N = 1, `cpu_baseline` (the CPU oracle port:
-every conv fwd+bwd, rulebook and BatchNorm of ONE whole frame, median of 3 passes) and `full_model`
-(the complete CenterPoint step with the COM curriculum head -- BaseBEVBackbone + CenterHead towers +
-COM targets / losses -- measured by a child run of `bench.py --dense-head --com`).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's
+headline needs: set-up, warm-up, the timed steps, `--dump-outputs` / `--dump-state`, the line.  `--full`
+measures the rest as well and adds it to the line: `h2d_inclusive` and `ragged` (two more timed loops),
+`roofline` (dominant kernel, timed live with HIP events on the launch stream) and, at N = 1, its rulebook
+regime, `seam_path`, `cpu_baseline` (the CPU oracle port: every conv fwd+bwd, rulebook and BatchNorm of
+the batch, median of 3 passes), `stage2`, and the child runs `full_model` (the complete CenterPoint step
+with the COM curriculum head, `bench.py --dense-head --com`), `config5_300k` and `n_gt_1_form`.
 """
 import argparse
 import gc
@@ -46,6 +48,9 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=4, help="frames per GPU (centerpoint.yaml:78)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every secondary measurement (each --no-* switch leaves one out); "
+                         "without it only the headline is measured")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--stage-times", action="store_true", help="print per-stage GPU times to stderr")
@@ -79,7 +84,8 @@ def parse():
     ap.add_argument("--no-full-model", action="store_true", help="skip the child run that measures the full CenterPoint + COM step")
     ap.add_argument("--no-n-gt-1", action="store_true", help="skip the two child runs that measure the N > 1 execution form on one GPU")
     ap.add_argument("--no-seam-path", action="store_true", help="skip the stock-eager / fused-eager / captured comparison")
-    ap.add_argument("--light", action="store_true", help="only the timed loop: every --no-* switch at once (experiment scripts)")
+    ap.add_argument("--light", action="store_true",
+                    help="only the timed loop, even with --full: every --no-* switch at once (experiment scripts)")
     ap.add_argument("--launch-timeout", type=float, default=900.0,
                     help="N > 1 without a launcher: seconds after which this process stops the ranks it started and fails")
     ap.add_argument("--rank-timeout", type=float, default=840.0,
@@ -91,7 +97,7 @@ def parse():
     ap.add_argument("--selftest-launch", action="store_true",
                     help="CPU plumbing test of the launcher / result assembly: gloo ranks, no GPU work")
     a = ap.parse_args()
-    if a.light:
+    if a.light or not a.full:
         a.no_cpu_baseline = a.no_roofline = a.no_h2d = a.no_ragged = a.no_stage2 = a.no_full_model = a.no_fp8 = True
         a.no_regime = a.no_n_gt_1 = a.no_seam_path = True
     return a
@@ -869,13 +875,11 @@ def measure_regime():
 def measure_full_model(args, flags=("--dense-head", "--com"), what=None, extra_env=None):
     """`full_model`: the complete CenterPoint-VoxelNet + COM-head training step (what a user of the reference would
     run), measured by a CHILD process (`bench.py --dense-head --com`, same batch / steps) after this process's own
-    loops have finished; the child is a new process, nothing is exec'ed over this one.  (`config5_300k` reuses this
-    with `--config5`.)"""
+    loops have finished; the child is a new process, nothing is exec'ed over this one, and it is a plain run (no
+    `--full`).  (`config5_300k` reuses this with `--config5`.)"""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), *flags, "--gpus", "1", "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--batch", str(args.batch), "--distinct-batches", str(args.distinct_batches),
-           "--no-cpu-baseline", "--no-roofline", "--no-h2d", "--no-ragged", "--no-full-model", "--no-stage2", "--no-fp8", "--no-regime",
-           "--no-n-gt-1", "--no-seam-path"]
+           "--warmup", str(args.warmup), "--batch", str(args.batch), "--distinct-batches", str(args.distinct_batches)]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)

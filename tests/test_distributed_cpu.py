@@ -193,6 +193,27 @@ def test_bench_refuses_a_world_size_that_is_not_gpus():
 
 
 @pytest.mark.timeout(120)
+def test_plain_bench_run_skips_every_secondary_measurement():
+    """`bench.py` without --full measures the headline only; --full runs every secondary measurement, a --no-* switch
+    leaves one of them out and --light all of them.  (A child process: importing bench.py sets HIP runtime variables.)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, sys\nimport bench\nout = []\n"
+            "for argv in ([], ['--full'], ['--full', '--no-h2d'], ['--full', '--light']):\n"
+            "    sys.argv = ['bench.py'] + argv\n"
+            "    out.append({k: v for k, v in vars(bench.parse()).items() if k.startswith('no_')})\n"
+            "print(json.dumps(out))\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=100)
+    assert r.returncode == 0, r.stderr[-2000:]
+    plain, full, no_h2d, light = json.loads(r.stdout.strip().splitlines()[-1])
+    assert len(plain) >= 10 and all(plain.values()) and all(light.values())
+    assert not any(full.values())
+    assert [k for k, v in no_h2d.items() if v] == ["no_h2d"]
+
+
+@pytest.mark.timeout(120)
 def test_launcher_propagates_a_failing_rank(tmp_path):
     import sys
     from com_amd import dist as cdist

@@ -111,7 +111,7 @@ def test_h2d_inclusive_leg_runs_in_both_forms(tmp_path):
     e = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PCD_H2D_PULL"):
         e.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--batch", "2", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2", "--batch", "2", "--no-cpu-baseline",
            "--no-roofline", "--no-ragged", "--no-full-model", "--no-stage2", "--no-fp8", "--no-seam-path", "--no-n-gt-1", "--distinct-batches", "3", "--gpus", "1"]
     for env, form in (({"PCD_H2D_CANDIDATES": "2"}, "copy stream"), ({"PCD_H2D_PULL": "1"}, "pulled by a kernel")):
         r = subprocess.run(cmd, env={**e, **env}, capture_output=True, text=True, timeout=900)
