@@ -10,7 +10,6 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libpcdops_hip.so")
-EXPERIMENTS_LIB_PATH = os.path.join(_HERE, "lib_experiments", "libpcdops_hip.so")     # `make -C com_amd/csrc EXPERIMENTS=1`
 CSRC = os.path.join(_HERE, "csrc")
 
 PCD_F32 = 0
@@ -112,8 +111,6 @@ PROTOTYPES = {
     "pcd_conv2d_wgrad_3x3_nhwc": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "pcd_conv2d_3x3_tiles": (_i, [_i, _i, _i]),
     "pcd_conv2d_3x3_nhwc_bn": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
-    "pcd_conv2d_wgrad_planes_splits": (_i, [_i, _i, _i, _i, _i, _i]),
-    "pcd_conv2d_wgrad_planes_nhwc": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "pcd_conv2d_planes_nhwc": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "pcd_sparse_conv_gather_gemm_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "pcd_sparse_conv_wgrad_f32": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
@@ -285,17 +282,6 @@ class PcdComCurriculum(ctypes.Structure):
                 ("conf_classes", ctypes.c_int), ("conf_groups", ctypes.c_int)]
 
 
-# include/pcd_ops_experiments.h: present only in a library built with `make EXPERIMENTS=1` (measured-slower kernels kept for
-# reproduction); bound when exported, never required
-EXPERIMENT_PROTOTYPES = {
-    "pcd_sparse_conv_pairs_seg_bytes": (_sz, [_i, _i]),
-    "pcd_sparse_conv_pairs_seg": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
-    "pcd_sparse_conv_pairs_tiles": (_i, [_i, _i, _i, _i]),
-    "pcd_sparse_conv_pairs": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "pcd_sparse_conv_gather_gemm_zfast": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp,
-                                         _vp]),
-}
-
 PCD_COM_CLUSTER_X5 = 0
 
 
@@ -331,11 +317,6 @@ def lib():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in EXPERIMENT_PROTOTYPES.items():
-            fn = getattr(handle, name, None)
-            if fn is not None:
-                fn.restype = res
-                fn.argtypes = args
         # (tuning options are set through set_option -- bench.py / tools/ forward PCD_OPT_<KEY> environment variables with
         #  tools/env_switches.py; neither this module nor the library reads the environment)
         _lib = handle
@@ -343,25 +324,9 @@ def lib():
 
 
 def use_experiments_library():
-    """Tools that reproduce the measured-slower kernels (tools/exp_ggwin.py, tools/exp_pconv.py): load the EXPERIMENTS build
-    instead of the default library -- call it before the first op of the process."""
-    global LIB_PATH
-    if _lib is not None:
-        raise PcdError("use_experiments_library() must come before the first call into the library")
-    if not os.path.exists(EXPERIMENTS_LIB_PATH):
-        raise PcdError(f"{EXPERIMENTS_LIB_PATH} not found: make -C com_amd/csrc EXPERIMENTS=1")
-    LIB_PATH = EXPERIMENTS_LIB_PATH
-
-
-_has_experiments = None
-
-
-def has_experiments():
-    """True if the loaded library exports the entry points of include/pcd_ops_experiments.h."""
-    global _has_experiments
-    if _has_experiments is None:
-        _has_experiments = all(hasattr(lib(), name) for name in EXPERIMENT_PROTOTYPES)
-    return _has_experiments
+    """The second library of measured-slower kernels was retired: there is nothing to load.  Kept so
+    that a caller that still asks for it (PCD_TEST_EXPERIMENTS=1 in tests/conftest.py) gets this error."""
+    raise PcdError("the EXPERIMENTS build was retired: its kernels measured slower and are no longer compiled (DESIGN.md 4.4)")
 
 
 def set_option(key, value):

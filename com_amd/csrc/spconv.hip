@@ -911,10 +911,6 @@ static int launch_ggw(const void *x, const void *wp, const float *bias, const in
     return PCD_OK;
 }
 
-#ifdef PCD_EXPERIMENTS
-#include "experiments/spconv_kernels.inc"     // ggwin_kernel (128-channel window/stream hybrid), pconv_kernel (pair-driven strided convs)
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // Data gradient of a STRIDED conv over rows grouped by parity class (pcd_rulebook_conv_classes): a workgroup's
 // rows all share the residues ((c + p) mod s) of the three axes, hence the same 1..8 usable offsets (of 27 for
@@ -1897,8 +1893,7 @@ extern "C" int pcd_pack_weights_batched(const void *table, int n, int total_bloc
 static int gg_dispatch(const void *x, int n_rows_in, int c_in, const void *packed_w, const float *bias,
                        const int32_t *nbr, int nbr_stride, int kvol, int flip_k, int n_rows_out,
                        const int32_t *n_rows_out_dev, int c_out, void *y, int y_dtype, const void *addend,
-                       const PcdBnReduce *bnr, int *tiles_only, void *stream, int dir_hint = -1, int zfast = 0,
-                       int nbr_packed = 0) {
+                       const PcdBnReduce *bnr, int *tiles_only, void *stream, int dir_hint = -1, int nbr_packed = 0) {
     if (n_rows_out < 0 || kvol <= 0 || c_in <= 0 || c_out <= 0) return PCD_ERR_INVALID_ARG;
     if (nbr_packed && (flip_k || kvol % 3 != 0)) return PCD_ERR_INVALID_ARG;
     if (y_dtype != PCD_BF16 && y_dtype != PCD_F32) return PCD_ERR_INVALID_ARG;
@@ -1941,18 +1936,11 @@ static int gg_dispatch(const void *x, int n_rows_in, int c_in, const void *packe
         if (nbr_packed) return PCD_ERR_UNSUPPORTED;        // (the LDS-DMA kernel stages full tables only)
         const unsigned w_bytes = (unsigned)wbytes;
         int mi = n_rows_out <= 256 * 192 * 5 / 4 ? 3 : 2;   /* (capacities are 1.25 x the row counts) */
-        // SubM 3x3x3 over z-fastest rows at 128 -> 128 channels: x through windows (ggwin_kernel; same tiles, same BatchNorm rows)
-#ifdef PCD_EXPERIMENTS
-        if (zfast && !tiles_only && pcd_opt(PCD_OPT_GGWIN) && c_out == 128 && kvol == 27 && mi == 3)
-            return launch_ggwin<8, 3>(x, packed_w, bias, nbr, nbr_stride, flip_k, n_rows_out, n_rows_out_dev, y, y_dtype, x_bytes,
-                                      w_bytes, st, addend, bnr);
-#endif
         // Few rows (one round of 128-row tiles fits the chip): the FORWARD conv takes 128-row tiles -- 36-38 us isolated against
         // 42-44 at 21-32 k rows (tools/exp_ggw.py) and nothing runs beside levels 3-4 of the forward pass; the data gradient
         // keeps 192 rows: its workgroups leave ~45 % of the CUs to the weight-gradient kernel running beside it, and with
         // 128-row tiles everywhere the training step was 7 % SLOWER (3.35 against 3.12 ms).
-        // (not with option "ggwin": that kernel and its tile count are built on 192 rows)
-        if (mi == 3 && !is_dgrad && n_rows_out <= 256 * 128 * 5 / 4 && !pcd_opt(PCD_OPT_GGWIN)) mi = 2;
+        if (mi == 3 && !is_dgrad && n_rows_out <= 256 * 128 * 5 / 4) mi = 2;
 #define GGW_ARGS x, packed_w, bias, nbr, nbr_stride, kvol, flip_k, n_rows_out, n_rows_out_dev, y, y_dtype, x_bytes, w_bytes, st, addend, bnr, tiles_only
         // 128 -> 128 with 192-row tiles: two consumer waves per SIMD (ggw_kernel CW = 2)
         if (c_out == 128) return mi == 3 ? launch_ggw<8, 2, 3, 3, 2>(GGW_ARGS) : launch_ggw<8, 2, 2, 3>(GGW_ARGS);
@@ -2001,12 +1989,8 @@ extern "C" int pcd_sparse_conv_gather_gemm_packed(const void *x, int n_rows_in, 
                                                   int y_dtype, const void *addend, const PcdBnReduce *bn_reduce, void *stream) {
     PCD_ENTER();
     return gg_dispatch(x, n_rows_in, c_in, packed_w, bias, (const int32_t *)nbr_out_packed, nbr_stride, kvol, 0, n_rows_out,
-                       n_rows_out_dev, c_out, y, y_dtype, addend, bn_reduce, nullptr, stream, 0, 0, 1);
+                       n_rows_out_dev, c_out, y, y_dtype, addend, bn_reduce, nullptr, stream, 0, 1);
 }
-
-#ifdef PCD_EXPERIMENTS
-#include "experiments/spconv_entries.inc"     // pcd_sparse_conv_gather_gemm_zfast, pcd_sparse_conv_pairs*
-#endif
 
 extern "C" int pcd_sparse_conv_gather_gemm_tiles_dir(int n_rows_in, int c_in, int kvol, int n_rows_out, int c_out,
                                                       int is_dgrad) {

@@ -23,7 +23,7 @@
 // Results equal gather_gemm_kernel's up to the fp32 summation order (offsets are summed per wave slice, then across slices).
 // The data gradient runs through the same launch with the mode-1 weight pack (transposed, offsets reversed: the k flip of the
 // rulebook view lives in the pack).  The WEIGHT gradient of these layers runs over the same tiles: subm_wgrad_win_kernel below.
-// Widths: 16 / 32 / 64 (and 128, slower than ggw_kernel: off) -- WinCfg instances; tile shares of equal cost: win_split_kernel.
+// Widths: 16 / 32 / 64 (a 128-channel configuration measured slower than ggw_kernel and was retired) -- WinCfg instances; tile shares of equal cost: win_split_kernel.
 #include <type_traits>
 
 #include "common.h"
@@ -91,8 +91,8 @@ __host__ __device__ constexpr size_t win_hdr_off(int ntiles) { return win_prefix
 __host__ __device__ constexpr size_t win_tab_off(int ntiles) { return win_hdr_off(ntiles) + (size_t)ntiles * 32; }
 
 // Wave roles: wave = (cb, rg, oq) -- output-channel block of 32, group of row blocks, slice of the 27 offsets.
-// CQN > 1: the output channels are dealt to CQN workgroups per share of the tiles (128 channels: the weights of 32 output
-// channels fill the registers of a workgroup) -- each loads the same windows and writes its COUTW columns of y.
+// CQN > 1: the output channels are dealt to CQN workgroups per share of the tiles (the retired 128-channel configuration: the
+// weights of 32 output channels fill the registers of a workgroup) -- each loads the same windows and writes its COUTW columns of y.
 // NW_ = waves per workgroup: 8 (one 512-thread workgroup per CU) or 4 (round 6: 256 threads, <= 80 KB of LDS -- TWO per CU, so that
 // a workgroup of another stream that holds part of a CU delays half a CU's worth of this launch instead of all of it).
 template <int CIN_, int NCB_, int NRG_, int NOQ_, int T_, int R_, int CQN_ = 1, int NW_ = 8>
@@ -176,9 +176,6 @@ using Win16 = WinCfg<16, 1, 8, 1, 256, 640>;     // 16 -> 16: waves = 8 row bloc
 // 4-wave configurations (option "subm_window_half": bit 1 = 32 channels, bit 2 = 16): the same wave roles on half the rows
 using Win32h = WinCfg<32, 1, 2, 2, 64, 176, 1, 4>;
 using Win16h = WinCfg<16, 1, 4, 1, 128, 320, 1, 4>;
-#ifdef PCD_EXPERIMENTS      // (make EXPERIMENTS=1; 61.6 us against ggw_kernel's 49.0 at level 4 -- DESIGN.md 4.1: not in the default library)
-using Win128 = WinCfg<128, 1, 1, 8, 32, 64, 4>;  // 128 -> 128: 4 workgroups x 32 output channels; waves = 8 offset slices (4 each)
-#endif
 
 // c_in -> configuration (square layers): f(Cfg{}) with the matching type, `none` otherwise
 template <class F, class N>
@@ -188,9 +185,6 @@ static inline auto win_dispatch(int c_in, int c_out, F &&f, N none) -> decltype(
         case 64: return f(Win64{});
         case 32: return (pcd_opt(PCD_OPT_SUBM_WINDOW_HALF) & 2) ? f(Win32h{}) : f(Win32{});
         case 16: return (pcd_opt(PCD_OPT_SUBM_WINDOW_HALF) & 4) ? f(Win16h{}) : f(Win16{});
-#ifdef PCD_EXPERIMENTS
-        case 128: return f(Win128{});
-#endif
         default: return none;
     }
 }
@@ -467,10 +461,6 @@ __device__ __forceinline__ void win_pack_any(const float *__restrict__ w, int ci
         if (e < win_pack_elems<Win64>()) win_pack_one<Win64>(w, mode, e, out, cin_real);
     } else if (cin == 32) {
         if (e < win_pack_elems<Win32>()) win_pack_one<Win32>(w, mode, e, out, cin_real);
-#ifdef PCD_EXPERIMENTS
-    } else if (cin == 128) {
-        if (e < win_pack_elems<Win128>()) win_pack_one<Win128>(w, mode, e, out);
-#endif
     } else {
         if (e < win_pack_elems<Win16>()) win_pack_one<Win16>(w, mode, e, out, cin_real);
     }
@@ -1543,7 +1533,7 @@ extern "C" int pcd_sparse_conv_subm_window_wgrad(const void *x, const void *dy, 
                                                  int nbr_stride, const int32_t *n_rows_dev, const void *plan, void *slab,
                                                  size_t slab_bytes, void *stream) {
     PCD_ENTER();
-    if (n_rows < 0 || !win_supported(c, c) || c > 64) return PCD_ERR_UNSUPPORTED;
+    if (n_rows < 0 || !win_supported(c, c)) return PCD_ERR_UNSUPPORTED;
     const size_t need = (size_t)pcd_subm_window_wgrad_splits(c) * 27 * c * c * sizeof(float);
     if (!slab || slab_bytes < need) return PCD_ERR_WORKSPACE;
     if (n_rows == 0) {
@@ -1554,9 +1544,6 @@ extern "C" int pcd_sparse_conv_subm_window_wgrad(const void *x, const void *dy, 
     if (!x || !dy || !nbr || !plan || nbr_stride < n_rows) return PCD_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     return win_dispatch(c, c, [&](auto cfg) {
-        if constexpr (decltype(cfg)::CIN <= 64)         // (the 128-channel configuration of EXPERIMENTS builds has no weight-gradient kernel)
-            return launch_wgrad_win<decltype(cfg)>(x, dy, n_rows, nbr, nbr_stride, n_rows_dev, plan, (float *)slab, st);
-        else
-            return (int)PCD_ERR_UNSUPPORTED;
+        return launch_wgrad_win<decltype(cfg)>(x, dy, n_rows, nbr, nbr_stride, n_rows_dev, plan, (float *)slab, st);
     }, (int)PCD_ERR_UNSUPPORTED);
 }

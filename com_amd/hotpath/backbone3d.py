@@ -70,22 +70,21 @@ class SparseBasicBlock(spconv.SparseModule):
 
 
 class _RulebookPrefetcher:
-    event_per_rulebook = False     # (one event per rulebook instead of per unit -- measured: no difference)
-
     def __init__(self, units, x0, side):
         self.units, self.t, self.side, self.next = units, x0, side, 0
+        self.unit0_stream = None       # (the stream unit 0 was built on: _BackboneBase._prefetch_rulebooks)
         self.after_units = x0.indice_dict.pop("__after_units__", None)
         self.hook_at = x0.indice_dict.pop("__after_units_at__", None)
 
-    def advance(self, inline=False, stream=None):
-        """inline: build the unit on the CURRENT stream (no event: its consumers are ordered behind it anyway);
-        stream: build it on that stream instead of the prefetcher's own."""
+    def advance(self, stream=None):
+        """Build the next unit on `stream` (default: the prefetcher's own) and record one event its consumers wait on.
+        (One event per rulebook instead of per unit measured no different.)"""
         if self.next >= len(self.units):
             return
         unit = self.units[self.next]
         self.next += 1
         side = stream if stream is not None else self.side
-        with torch.cuda.stream(torch.cuda.current_stream() if inline else side):
+        with torch.cuda.stream(side):
             t = self.t
             built = []
             for conv in unit:
@@ -96,17 +95,11 @@ class _RulebookPrefetcher:
                 if getattr(rb, "ready_event", None) is None:
                     built.append(rb)
                     self._window_plan(conv, rb)
-                    self._pair_plan(conv, rb)
-                    if not inline and self.event_per_rulebook:
-                        # the strided conv that opens a level waits for ITS rulebook only, not for the SubM rulebook (+ window
-                        # plan) of the level behind it in the same unit
-                        rb.ready_event = torch.cuda.Event()
-                        rb.ready_event.record(side)
                 if not conv.subm:
                     t = SparseConvTensor(t.features, out_idx, out_shape, t.batch_size, indice_dict=t.indice_dict,
                                          num_rows=rb.n_out_dev)
             self.t = t
-            if built and not inline and not self.event_per_rulebook:
+            if built:
                 ev = torch.cuda.Event()
                 ev.record(side)
                 for rb in built:
@@ -130,7 +123,7 @@ class _RulebookPrefetcher:
         hook, self.after_units = self.after_units, None
         side = self.side
         with torch.cuda.stream(side):
-            u0 = getattr(self, "unit0_stream", None)
+            u0 = self.unit0_stream
             if u0 is not None and u0 is not side:
                 # unit 0 (the level-1 SubM rulebook) reads the voxeliser's coordinates and rank map on ITS OWN stream: the
                 # hook may overwrite them, so this stream is ordered behind unit 0's reads first (in a captured graph
@@ -156,19 +149,6 @@ class _RulebookPrefetcher:
         tables = not bf16 or any(not c.window_capable() or getattr(c, "fp8_train", None) is not None
                                  or (c._needs_backward(t) and not Fsp._window_wgrad(c.out_channels)) for c in group)
         return w, tables
-
-    @staticmethod
-    def _pair_plan(conv, rb):
-        """The segment tables of the pair-driven strided kernel (ops.pair_conv_plan caches them on the rulebook), here on the
-        rulebook stream instead of in front of the conv that needs them."""
-        from .. import ops
-        if conv.subm or rb._pairs is None:
-            return
-        cin = ops.pow2_ge8(conv.in_channels)
-        if ops.pair_conv_usable(rb, cin, conv.out_channels):
-            ops.pair_conv_plan(rb, 0)
-        if ops.pair_conv_usable(rb, conv.out_channels, cin):
-            ops.pair_conv_plan(rb, 1)
 
     @staticmethod
     def _window_plan(conv, rb):
@@ -222,8 +202,6 @@ class _BackboneBase(nn.Module):
     # None: the hook runs right behind the last rulebook unit; "conv2" / "conv3" / "conv4": additionally not before the main
     # chain has finished that level (the hook's kernels then run beside the levels after it)
     after_rulebooks_at = None
-    first_unit_inline = False      # measured: see _prefetch_rulebooks
-    unit0_own_stream = True
     # rulebook units issued before the first conv; each unit's first consumer issues one more
     prefetch_depth = 2
 
@@ -250,24 +228,17 @@ class _BackboneBase(nn.Module):
         x0.indice_dict["__prefetcher__"] = pf
         depth = max(1, int(self.prefetch_depth))
         side.wait_stream(cur)
-        if self.first_unit_inline:
-            # (experiment, off) the level-1 rulebook on the MAIN stream.  Device-clock stamps show the first conv of the step
-            # starting 210-260 us into the forward although its rulebook is ready at 24 us (the hipGraph executor runs it
-            # behind the next unit's kernels); built inline it finishes at 63 us and the forward ends 84 us earlier -- but
-            # the rulebook units, now beside the gather kernels from the start, finish 90-200 us later and the step is the
-            # same: 3.44 vs 3.42 ms without stamps (tools/exp_rb_inline.sh)
-            pf.advance(inline=True)
-            depth -= 1
-        if self.unit0_own_stream and not self.first_unit_inline:
-            # The level-1 SubM rulebook (unit 0: all the first conv waits for) on a short branch of its own; the other units do
-            # not read it (unit 1 = the strided build over the level-1 coordinates), so they fork from the main stream too.  As
-            # children of unit 0's last node they held the first conv back: the graph executor ran it behind the whole of unit 1
-            # (first conv at 0.27 ms with its rulebook ready at 0.06).
-            u0 = Fsp._side_stream(dev, "rulebook0")
-            u0.wait_stream(cur)
-            pf.advance(stream=u0)
-            pf.unit0_stream = u0
-            depth -= 1
+        # The level-1 SubM rulebook (unit 0: all the first conv waits for) on a short branch of its own; the other units do
+        # not read it (unit 1 = the strided build over the level-1 coordinates), so they fork from the main stream too.  As
+        # children of unit 0's last node they held the first conv back: the graph executor ran it behind the whole of unit 1
+        # (first conv at 0.27 ms with its rulebook ready at 0.06).  (Building unit 0 on the MAIN stream instead let the first
+        # conv start earlier, but the other units then ran beside the gather kernels from the start and finished later: the
+        # step was no faster, 3.44 vs 3.42 ms.)
+        u0 = Fsp._side_stream(dev, "rulebook0")
+        u0.wait_stream(cur)
+        pf.advance(stream=u0)
+        pf.unit0_stream = u0
+        depth -= 1
         for _ in range(depth):
             pf.advance()
         if getattr(self, "_packed_ahead", False):              # pack_after_update() ran since the last update
@@ -365,7 +336,7 @@ class _BackboneBase(nn.Module):
             pf = x0.indice_dict.pop("__prefetcher__")
             pf.run_hook(after_stream=torch.cuda.current_stream())      # (a hook point that came before the last unit was issued)
             torch.cuda.current_stream().wait_stream(pf.side)
-            if getattr(pf, "unit0_stream", None) is not None:
+            if pf.unit0_stream is not None:
                 torch.cuda.current_stream().wait_stream(pf.unit0_stream)
         batch_dict.update({'encoded_spconv_tensor': out, 'encoded_spconv_tensor_stride': 8})
         batch_dict.update({'multi_scale_3d_features': {

@@ -14,11 +14,10 @@ import torch.nn as nn
 from .. import ops
 
 ENABLED = True
-# BatchNorm sums in the dense convs' epilogues (PcdBnReduce modes 1 / 2 of pcd_conv2d_3x3_nhwc_bn): bit 0 = forward
-# statistics, bit 1 = backward reductions on the data-gradient launch.  Measured in the full step
-# (tools/exp_dense_bn_epi.sh, 2 x 80 replays): off 7.84, forward 7.79, backward 7.89, both 7.86 ms -- the backward form
-# re-reads the BatchNorm's input and output tile in the data-gradient epilogue and loses; only the forward one is on.
-DENSE_BN_EPILOGUE = 1
+# The following BatchNorm's statistics are taken in the dense conv's epilogue (PcdBnReduce mode 1 of pcd_conv2d_3x3_nhwc_bn)
+# whenever spconv.functional.FUSE_BN_REDUCTIONS holds.  Measured in the full step (2 x 80 replays): off 7.84, forward
+# 7.79 ms.  The backward reductions on the data-gradient launch (mode 2) were retired: they re-read the BatchNorm's input
+# and output tile in that epilogue and lost, 7.89 ms alone and 7.86 with the forward form.
 _PAIRS = {}
 
 
@@ -162,10 +161,9 @@ class _Conv3x3Function(torch.autograd.Function):
     pack_f / pack_d: packs made ahead (Conv3x3Packs), or None: packed here."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, pack_f, pack_d, bn_follows=False, bn_link=None):
+    def forward(ctx, x, weight, bias, pack_f, pack_d, bn_follows=False):
         # x: [B, C, H, W] bf16, channels_last storage
         # bn_follows: a training-mode BatchNorm consumes the output -> its statistics are taken in this launch's epilogue
-        # bn_link: x IS the output of a fused BatchNorm -> its backward reductions ride on our data-gradient launch
         from ..spconv import functional as Fsp
         xn = x.detach().permute(0, 2, 3, 1)
         assert xn.is_contiguous()
@@ -176,7 +174,7 @@ class _Conv3x3Function(torch.autograd.Function):
             b = torch.nn.functional.pad(b, (0, cp - cout))
         if pack_f is None:
             pack_f = ops.conv2d_pack_weight(weight, 0)
-        stats = ops.BnReduce(1) if (bn_follows and Fsp.FUSE_BN_REDUCTIONS and cp == cout and (DENSE_BN_EPILOGUE & 1)) else None
+        stats = ops.BnReduce(1) if (bn_follows and Fsp.FUSE_BN_REDUCTIONS and cp == cout) else None
         y = ops.conv2d_3x3_nhwc(xn, pack_f, cp, b, bn_reduce=stats)
         if cp != cout:
             y = y[..., :cout].contiguous()
@@ -184,7 +182,6 @@ class _Conv3x3Function(torch.autograd.Function):
         ctx.has_bias, ctx.cout = bias is not None, cout
         ctx.weight_param = weight if isinstance(weight, nn.Parameter) else None
         ctx.bias_param = bias if isinstance(bias, nn.Parameter) else None
-        ctx.bn_link = bn_link if (Fsp.FUSE_BN_REDUCTIONS and (DENSE_BN_EPILOGUE & 2)) else None
         out = y.permute(0, 3, 1, 2)
         if stats is not None and stats.partial is not None:
             out._pcd_stats = stats
@@ -208,14 +205,7 @@ class _Conv3x3Function(torch.autograd.Function):
 
         def dgrad():
             pd = pack_d if pack_d is not None else ops.conv2d_pack_weight(weight, 1)
-            link, red = ctx.bn_link, None
-            if link is not None and link.x.shape == (B * H * W, cin):
-                red = ops.BnReduce(2, relu=link.relu, x=link.x, y=xn.reshape(-1, cin) if link.relu else None,
-                                   mean=link.mean, invstd=link.invstd)
-            dxn = ops.conv2d_3x3_nhwc(dyn, pd, cin, bn_reduce=red)
-            if red is not None and red.partial is not None:
-                link.result = (dxn.view(-1, cin), red.partial, red.rows)
-            return dxn.permute(0, 3, 1, 2)
+            return ops.conv2d_3x3_nhwc(dyn, pd, cin).permute(0, 3, 1, 2)
 
         def wgrad(direct):
             if ops.conv2d_wgrad_splits(B, H, W, cin, cp) > 0:      # the dense kernel (no pair lists)
@@ -242,7 +232,7 @@ class _Conv3x3Function(torch.autograd.Function):
 
         dx, dw, db = _scheduled_backward(ctx.needs_input_grad[0], want_w, want_b, wp, bp, True, dgrad, wgrad, bsum,
                                          (xn, dyn))
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None
 
 
 class Conv3x3(nn.Conv2d):
@@ -262,14 +252,13 @@ class Conv3x3(nn.Conv2d):
     def forward(self, x):
         if not self._fast(x):
             return super().forward(x)
-        link = getattr(x, "_pcd_bn_link", None)
         if x.dtype != torch.bfloat16:
-            x, link = x.to(torch.bfloat16), None
+            x = x.to(torch.bfloat16)
         if not x.is_contiguous(memory_format=torch.channels_last):
-            x, link = x.contiguous(memory_format=torch.channels_last), None
+            x = x.contiguous(memory_format=torch.channels_last)
         pf, pd = self._take_packs()
         follows = bool(self.bn_follows and self.training and torch.is_grad_enabled())
-        return _Conv3x3Function.apply(x, self.weight, self.bias, pf, pd, follows, link)
+        return _Conv3x3Function.apply(x, self.weight, self.bias, pf, pd, follows)
 
     def _take_packs(self):
         pf = pd = None
@@ -320,12 +309,6 @@ class _ConvPlanesFunction(torch.autograd.Function):
             return ops.conv2d_planes_nhwc(mode_f + 1, dyn, pd, cin, (H, W)).permute(0, 3, 1, 2)
 
         def wgrad(direct):
-            fine, coarse = (xn, dyn) if mode_f == 2 else (dyn, xn)
-            if ops.conv2d_wgrad_planes_splits(mode_f, B, coarse.shape[1], coarse.shape[2], fine.shape[3], coarse.shape[3]) > 0:
-                if direct:                                        # the dense kernel (no pair lists)
-                    ops.conv2d_wgrad_planes(mode_f, fine, coarse, out=wp.grad, defer=Fsp._WGRAD_JOBS)
-                    return None
-                return ops.conv2d_wgrad_planes(mode_f, fine, coarse).to(weight.dtype)
             pairs, num = _plane_pairs(mode_f, B, H, W, xn.device)
             if mode_f == 2:       # gathered rows = x (contraction c = cin), accumulated rows = dy (o = cout)
                 a, ca, b_, cb = xn.reshape(-1, cin), cin, dyn.reshape(-1, cout), cout
@@ -612,11 +595,7 @@ class BatchNormReLU2d(nn.BatchNorm2d):
                     rows._pcd_stats = st
                 y = Fsp.batch_norm_act(self, rows, None, self.relu, out=out_rows)
                 self.wrote_out = out_rows is not None
-                res = y.view(B, H, W, C).permute(0, 3, 1, 2)
-                link = getattr(y, "_pcd_bn_link", None)       # ... and the conv behind can take the backward reductions
-                if link is not None:
-                    res._pcd_bn_link = link
-                return res
+                return y.view(B, H, W, C).permute(0, 3, 1, 2)
         if getattr(self, "_defer_nbt", False) and self.training and self.num_batches_tracked is not None:
             self.num_batches_tracked.sub_(1)         # bump_bn_counters() already counted this call
         y = super().forward(x)

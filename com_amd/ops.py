@@ -1182,11 +1182,9 @@ def gather_gemm_is_wide(n_rows_in, c_in, kvol, n_rows_out, c_out, is_dgrad=False
 
 
 def gather_gemm(x, packed_w, bias, nbr, kvol, flip_k, n_rows_out, c_out, out_dtype, n_dev=None, addend=None,
-                bn_reduce=None, zfast=False, nbr_packed=False):
+                bn_reduce=None, nbr_packed=False):
     """y[o] = bias + sum_k x[nbr[k'][o]] @ W[k] (+ addend[o])  (output-stationary; forward and dgrad).
-    nbr_packed: `nbr` is a strided rulebook's packed output-side table (Rulebook.nbr_out_packed, [kvol / 3, n_out]).
-    zfast: `nbr` is a SubM 3x3x3 table over rows numbered z-fastest (ROWS_YXZ) -- the 128-channel layers then stage x
-    through row windows (ggwin_kernel) instead of gathering 27 slots per row; same result within one bf16 ulp."""
+    nbr_packed: `nbr` is a strided rulebook's packed output-side table (Rulebook.nbr_out_packed, [kvol / 3, n_out])."""
     _require_cuda(x, packed_w, nbr)
     assert x.dtype == torch.bfloat16 and x.is_contiguous() and nbr.is_contiguous()
     y = torch.empty((n_rows_out, c_out), dtype=out_dtype, device=x.device)
@@ -1214,82 +1212,18 @@ def gather_gemm(x, packed_w, bias, nbr, kvol, flip_k, n_rows_out, c_out, out_dty
         dg = int(bool(flip_k) or (bn_reduce is not None and bn_reduce.mode == 2))
         variant = L.lib().pcd_sparse_conv_gather_gemm_variant(x.shape[0], x.shape[1], kvol, n_rows_out, c_out, dg)
         kname = {1: "ggw_kernel"}.get(variant, kname)
-        if variant == 1 and zfast and x.shape[1] == c_out == 128 and kvol == 27 and L.get_option("ggwin") \
-                and n_rows_out <= 256 * 192 * 5 // 4:
-            kname = "ggwin_kernel"
-    # (the z-fastest entry point exists in EXPERIMENTS builds only: pcd_ops_experiments.h)
-    entry = L.lib().pcd_sparse_conv_gather_gemm_zfast if (zfast and L.has_experiments()) else L.lib().pcd_sparse_conv_gather_gemm
     with _Timed(f"{kname}<NB={c_out // 16}> {x.shape[1]}->{c_out} K={kvol}", meta):
         if nbr_packed:
-            assert not flip_k and not zfast and nbr.shape[0] * 3 == kvol
+            assert not flip_k and nbr.shape[0] * 3 == kvol
             L.check(L.lib().pcd_sparse_conv_gather_gemm_packed(
                 L.ptr(x), x.shape[0], x.shape[1], L.ptr(packed_w), L.ptr(bias), L.ptr(nbr), nbr.shape[1], kvol, n_rows_out,
                 L.ptr(n_dev), c_out, L.ptr(y), _dtype_code(y), L.ptr(addend), _byref(bnr), L.stream_ptr()),
                 "pcd_sparse_conv_gather_gemm_packed")
             return y
-        L.check(entry(L.ptr(x), x.shape[0], x.shape[1], L.ptr(packed_w), L.ptr(bias), L.ptr(nbr), nbr.shape[1], kvol,
-                      int(flip_k), n_rows_out, L.ptr(n_dev), c_out, L.ptr(y), _dtype_code(y), L.ptr(addend), _byref(bnr),
-                      L.stream_ptr()), "pcd_sparse_conv_gather_gemm")
-    return y
-
-
-# ---- pair-driven strided convs over z-fastest rows (pconv_kernel) ------------------------------------------------------
-# strided 16 <-> 32-channel convs of z-fastest chains through their indice pairs (one gather per PAIR instead of 27 slots per
-# row).  Parity-green, measured SLOWER: 80 / 42 us (forward / data gradient, isolated) against 34 / 30 for the gather kernels,
-# 1267 against 1296 frames/s in the step -- two dependent memory latencies per group of four 16-pair chunks at two waves per
-# SIMD; off
-PAIR_CONV = False
-
-
-def pair_conv_usable(rb, c_mov, c_sta):
-    """The pair-driven kernel serves this strided rulebook: rows z-fastest (pairs sorted by both rows), pair lists built,
-    widths (16, 32) or (32, 16)."""
-    return (PAIR_CONV and L.has_experiments() and not rb.subm and rb.kvol == 27 and getattr(rb, "order", None) == ROWS_YXZ
-            and rb._pairs is not None and (int(c_mov), int(c_sta)) in ((16, 32), (32, 16)))
-
-
-def pair_conv_plan(rb, direction):
-    """seg[k][tile] of `rb` for the forward (0: tiles of output rows) / data gradient (1: tiles of input rows); cached."""
-    cache = rb.__dict__.setdefault("_pconv_seg", {})
-    if direction not in cache:
-        lib = L.lib()
-        n_stat = rb.n_out if direction == 0 else rb.n_in
-        seg = torch.empty((max(int(lib.pcd_sparse_conv_pairs_seg_bytes(n_stat, rb.kvol)) // 4, 1),), dtype=torch.int32,
-                          device=rb._pairs.device)
-        L.check(lib.pcd_sparse_conv_pairs_seg(L.ptr(rb._pairs), rb._pairs.shape[2], L.ptr(rb._pair_num), rb.kvol, int(direction),
-                                              n_stat, L.ptr(seg), L.stream_ptr()), "pcd_sparse_conv_pairs_seg")
-        cache[direction] = seg
-    return cache[direction]
-
-
-def pair_conv(x, packed_w, bias, rb, direction, c_sta, out_dtype, addend=None, bn_reduce=None):
-    """Strided conv through its indice pairs: direction 0 forward (x = input features, packed_w = pack_weight(w, 0)),
-    1 data gradient (x = dy, packed_w = pack_weight(w, 1)); returns [n_stat, c_sta]."""
-    _require_cuda(x, packed_w)
-    assert x.dtype == torch.bfloat16 and x.is_contiguous()
-    n_stat = rb.n_out if direction == 0 else rb.n_in
-    n_stat_dev = rb.n_out_dev if direction == 0 else rb.n_in_dev
-    seg = pair_conv_plan(rb, direction)
-    y = torch.empty((n_stat, c_sta), dtype=out_dtype, device=x.device)
-    if addend is not None:
-        assert addend.shape == y.shape and addend.dtype == y.dtype and addend.is_contiguous() and addend.is_cuda
-    lib = L.lib()
-    c_mov = x.shape[1]
-
-    def meta():
-        pairs = int(rb._pair_num.sum().item())
-        return dict(bytes=(x.shape[0] * c_mov + n_stat * c_sta) * 2 + 8 * pairs + 27 * c_mov * c_sta * 2,
-                    flops=2 * pairs * c_mov * c_sta, rows=n_stat, pairs=pairs)
-
-    bnr = None
-    if bn_reduce is not None:
-        bnr = bn_reduce._struct(_tiles(lib.pcd_sparse_conv_pairs_tiles(n_stat, c_mov, c_sta, rb.kvol), "pcd_sparse_conv_pairs_tiles"),
-                                c_sta, x.device)
-    with _Timed(f"pconv_kernel<{c_mov},{c_sta}> {'dgrad' if direction else 'fwd'} K=27", meta):
-        L.check(lib.pcd_sparse_conv_pairs(L.ptr(x), x.shape[0], c_mov, L.ptr(packed_w), L.ptr(bias), L.ptr(rb._pairs),
-                                          rb._pairs.shape[2], L.ptr(seg), rb.kvol, int(direction), n_stat, L.ptr(n_stat_dev), c_sta,
-                                          L.ptr(y), _dtype_code(y), L.ptr(addend), _byref(bnr), L.stream_ptr()),
-                "pcd_sparse_conv_pairs")
+        L.check(L.lib().pcd_sparse_conv_gather_gemm(
+            L.ptr(x), x.shape[0], x.shape[1], L.ptr(packed_w), L.ptr(bias), L.ptr(nbr), nbr.shape[1], kvol, int(flip_k), n_rows_out,
+            L.ptr(n_dev), c_out, L.ptr(y), _dtype_code(y), L.ptr(addend), _byref(bnr), L.stream_ptr()),
+            "pcd_sparse_conv_gather_gemm")
     return y
 
 
@@ -1668,44 +1602,6 @@ def conv2d_wgrad(x, dy, cout=None, out=None, defer=None):
         L.check(lib.pcd_conv2d_wgrad_3x3_nhwc(L.ptr(x), x_cs, L.ptr(dy), B, H, W, cin, cp, L.ptr(slab), slab.numel() * 4,
                                               L.stream_ptr()), "pcd_conv2d_wgrad_3x3_nhwc")
     job = (slab, dw, 9, cin, cp, 1, splits, 1, cout if cout != cp else 0)
-    if defer is not None:
-        defer.append(job)
-    else:
-        wgrad_reduce_batched([job])
-    return dw
-
-
-# Dense weight-gradient kernels for the plane operators (deconvs): built, bit-checked against the pair kernels -- and NOT
-# faster in the step (tools/exp_wgp_blocks.sh: 7.81-7.85 vs 7.79 ms with the pair kernels; isolated the k = stride deconvs
-# gain, 31 / 60 vs 76 us at 512 workgroups; the stride-2 conv's form lost, 99 vs 80 us, and is not built): off unless asked for.
-CONV2D_WGRAD_PLANES = False
-
-
-def conv2d_wgrad_planes_splits(mode_f, B, hc, wc, cf, cc):
-    return L.lib().pcd_conv2d_wgrad_planes_splits(mode_f, B, hc, wc, cf, cc) if (CONV2D_WGRAD and CONV2D_WGRAD_PLANES) else 0
-
-
-def conv2d_wgrad_planes(mode_f, fine, coarse, out=None, defer=None):
-    """dW of the transposed plane operators in the torch parameter's layout (f32): modes 4 / 6 (ConvTranspose2d
-    k = stride = 2 / 1): fine = dy, coarse = x -> [cin, cout, k, k] (the stride-2 Conv2d, mode 2, is not covered: its
-    weight gradient runs on the pair kernels).  Both maps [B, h, w, c] bf16 contiguous.  Caller checks
-    conv2d_wgrad_planes_splits(...) > 0 first."""
-    _require_cuda(fine, coarse)
-    assert fine.dtype == torch.bfloat16 and coarse.dtype == torch.bfloat16 and fine.is_contiguous() and coarse.is_contiguous()
-    B, hf, wf, cf = fine.shape
-    _, hc, wc, cc = coarse.shape
-    k = {4: 2, 6: 1}[mode_f]
-    lib = L.lib()
-    splits = lib.pcd_conv2d_wgrad_planes_splits(mode_f, B, hc, wc, cf, cc)
-    assert splits > 0
-    slab = torch.empty((splits * cc * k * k * cf,), dtype=torch.float32, device=fine.device)
-    dw = out if _usable_out(out, cc * k * k * cf) else torch.empty((cc, cf, k, k), dtype=torch.float32, device=fine.device)
-    with _Timed(f"conv2d_wgrad_planes_kernel<{mode_f}> {cf}x{cc} {hc}x{wc}",
-                lambda: dict(bytes=(fine.numel() + coarse.numel()) * 2 + slab.numel() * 4,
-                             flops=2 * k * k * B * hc * wc * cf * cc, rows=B * hc * wc, pairs=0)):
-        L.check(lib.pcd_conv2d_wgrad_planes_nhwc(mode_f, L.ptr(fine), hf, wf, cf, L.ptr(coarse), B, hc, wc, cc, L.ptr(slab),
-                                                 slab.numel() * 4, L.stream_ptr()), "pcd_conv2d_wgrad_planes_nhwc")
-    job = (slab, dw, k * k, cf, cc, 1, splits, 1, 0)
     if defer is not None:
         defer.append(job)
     else:

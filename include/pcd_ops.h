@@ -57,7 +57,8 @@ extern "C" {
 #define PCD_ROWS_YXZ 1
 
 /* ---- library info -------------------------------------------------------------------------- */
-int pcd_version(void);                    /* 10000*major + 100*minor + patch */
+int pcd_version(void);                    /* 10000*major + 100*minor + patch; 0.2.0: the two entry points of the
+                                             plane-form dense weight gradient left the ABI */
 const char *pcd_error_string(int code);
 const char *pcd_build_arch(void);         /* "gfx950" */
 /* text of the HIP runtime error behind the calling thread's last PCD_ERR_LAUNCH */
@@ -76,8 +77,8 @@ int pcd_stream_capture_id(void *stream, unsigned long long *id_out);
  *   "ggw" 1               LDS-DMA gather-GEMM (ggw_kernel) for C_in = 128, C_out = 64 / 128 (0: gather_gemm_kernel, the only
  *                         kernel for those widths over a packed table or with kvol > 52)
  *   "subm_window" 23      window gather-GEMM for SubM 3x3x3 layers over PCD_ROWS_YXZ rows: bit 0 = 64 channels, bit 1 = 32,
- *                         bit 2 = 16, bit 3 = 128 (EXPERIMENTS builds; off: its dense 27-offset MFMA work makes it slower than the
- *                         step-skipping generic kernel there, 61.6 vs 49.0 us), bit 4 = layers with FEWER input than output
+ *                         bit 2 = 16, bit 3 = 128 (retired: its dense 27-offset MFMA work made it slower than the
+ *                         step-skipping generic kernel there, 61.6 vs 49.0 us; ignored), bit 4 = layers with FEWER input than output
  *                         channels run on zero-padded rows (conv_input 5 -> 16; forward + weight gradient, no data gradient)
  *                         (0: generic kernels) -- read by the host-side layer, the C entry points take any of these widths
  *   "subm_window_wgrad" 6 the same bits for the window weight gradient (pcd_sparse_conv_subm_window_wgrad); 64 channels off:
@@ -86,10 +87,9 @@ int pcd_stream_capture_id(void *stream, unsigned long long *id_out);
  *                         for padded x rows (cin_pad != 128), kvol > 343 and pcd_sparse_conv_wgrad_classes)
  *   "wg128_chunks" 512    its workgroup count
  *   "wg_rows" 6144        row-range split of the generic weight-gradient kernel
- *   "conv2d_wg_blocks" 128, "conv2d_wgp_blocks" 512   workgroups of the dense 3x3 / plane weight-gradient kernels
+ *   "conv2d_wg_blocks" 128 workgroups of the dense 3x3 weight-gradient kernel
  *   "fps_g" 0             workgroups per frame of the cooperative farthest point sampling (0: from the device's CU count)
  *   "gg_dbg" 0, "ggw_dbg" 0, "win_dbg" 0   ablation bit masks of the gather-GEMM kernels (profiling only)
- *   "ggwin" 0             (EXPERIMENTS build only, pcd_ops_experiments.h) 1: 128 -> 128 SubM layers through ggwin_kernel
  *   "subm_window_half" 0  4-wave window configurations (256 threads, <= 80 KB of LDS: two workgroups per CU): bit 1 = 32 channels,
  *                         bit 2 = 16 channels.  Set it before the first plan is built: plans, packs and launches of a width must agree
  *   "subm_window_grid" 256   workgroups of a window launch (a multiple of 8, <= 256); fewer leave CUs to other streams --
@@ -1023,13 +1023,6 @@ int pcd_conv2d_3x3_nhwc_bn(const void *x, int x_cs, int batch, int height, int w
 int pcd_conv2d_wgrad_3x3_splits(int batch, int height, int width, int cin, int cout);
 int pcd_conv2d_wgrad_3x3_nhwc(const void *x, int x_cs, const void *dy, int batch, int height, int width, int cin, int cout,
                               void *slabs, size_t slab_bytes, void *stream);
-/* ... and of the transposed plane operators below (forward pack modes 4 / 6; mode 2, the stride-2 conv, is not covered:
- * 0 splits, use the pair form): `fine` / `coarse` = the layer's two maps (dy / x), contiguous bf16; slabs [cc][k * k][cf] f32
- * -> pcd_sparse_conv_wgrad_reduce_batched (kvol = k * k, cin = cf, cout = cc, layout 1 = the ConvTranspose2d parameter's
- * layout).  cf % 64 == 0, cc % 32 == 0. */
-int pcd_conv2d_wgrad_planes_splits(int mode, int batch, int hc, int wc, int cf, int cc);
-int pcd_conv2d_wgrad_planes_nhwc(int mode, const void *fine, int hf, int wf, int cf, const void *coarse, int batch, int hc,
-                                 int wc, int cc, void *slabs, size_t slab_bytes, void *stream);
 /* The other three layers of BaseBEVBackbone (base_bev_backbone.py:36-75; MIOpen in the reference), forward and data
  * gradient, as per-parity-plane stencils on the same tiles.  pack modes (pcd_conv2d_pack_weight / _packed_weight_bytes /
  * the batched table take them too; cin / cout are the LAYER's channel counts, the weight is the torch parameter):

@@ -27,7 +27,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(handle, name), f"{name} declared in pcd_ops.h but not exported"
     assert sorted(_lib.PROTOTYPES) == declared, "ctypes prototypes out of sync with the header"
     lib = _lib.lib()
-    assert lib.pcd_version() >= 100
+    assert lib.pcd_version() >= 200
     assert lib.pcd_build_arch() == b"gfx950"
     assert lib.pcd_error_string(-3).decode().startswith("batch")
 
@@ -50,24 +50,26 @@ def test_header_lists_exactly_the_tuning_options_of_the_library():
     assert _lib.lib().pcd_get_option(b"no_such_option", ctypes.byref(value)) != 0
 
 
-def test_experiment_kernels_stay_out_of_the_default_library():
-    """include/pcd_ops_experiments.h declares the entry points of the measured-slower kernels; the DEFAULT build must not export
-    them (they are compiled only by `make EXPERIMENTS=1` into com_amd/lib_experiments/), the ctypes layer binds them when present."""
+def test_retired_kernels_are_out_of_the_library():
+    """The measured-slower kernels were retired: the library exports none of their entry points (the
+    five of the former EXPERIMENTS build and the two of the plane-form dense weight gradient), has no 128-channel window
+    configuration, and rejects their option keys like any unknown key."""
     from com_amd import _lib
-    text = open(os.path.join(ROOT, "include", "pcd_ops_experiments.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(pcd_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(_lib.EXPERIMENT_PROTOTYPES) and len(declared) == 5
-    default = ctypes.CDLL(os.path.join(ROOT, "com_amd", "lib", "libpcdops_hip.so"))
-    for name in declared:
-        assert not hasattr(default, name), f"{name} is an experiment: it must not be in the default library"
-    default.pcd_subm_window_tile_rows.restype = ctypes.c_int
-    assert default.pcd_subm_window_tile_rows(128, 128) == 0 and default.pcd_subm_window_tile_rows(64, 64) > 0
-    # (the optional build, when it is there and not older than the default one)
-    if os.path.exists(_lib.EXPERIMENTS_LIB_PATH) and os.path.getmtime(_lib.EXPERIMENTS_LIB_PATH) >= os.path.getmtime(_lib.LIB_PATH):
-        exp = ctypes.CDLL(_lib.EXPERIMENTS_LIB_PATH)
-        for name in declared + _declared_symbols():
-            assert hasattr(exp, name), name
+    default = ctypes.CDLL(_lib.LIB_PATH)
+    retired = ["pcd_sparse_conv_gather_gemm_zfast", "pcd_sparse_conv_pairs", "pcd_sparse_conv_pairs_seg",
+               "pcd_sparse_conv_pairs_seg_bytes", "pcd_sparse_conv_pairs_tiles",
+               "pcd_conv2d_wgrad_planes_splits", "pcd_conv2d_wgrad_planes_nhwc"]
+    for name in retired:
+        assert not hasattr(default, name), f"{name} was retired: it must not be in the library"
+    assert not set(retired) & set(_declared_symbols())
+    lib = _lib.lib()
+    assert lib.pcd_subm_window_tile_rows(128, 128) == 0 and lib.pcd_subm_window_tile_rows(64, 64) > 0
+    value = ctypes.c_int()
+    for key in (b"ggwin", b"conv2d_wgp_blocks"):
+        assert lib.pcd_get_option(key, ctypes.byref(value)) != 0, key
+        assert lib.pcd_set_option(key, 1) != 0, key
+    with pytest.raises(_lib.PcdError):
+        _lib.use_experiments_library()
 
 
 def test_header_structs_match_ctypes_mirrors(tmp_path):
