@@ -8,3 +8,4 @@ from .vfe import DynamicMeanVFE, DynamicPillarVFE, MeanVFE, PillarVFE  # noqa: F
 from .dense2d import BaseBEVBackbone, CenterHeadTowers, SeparateHead  # noqa: F401
 from .center_head import CenterHead  # noqa: F401
 from .curriculum_head import CurriculumCenterHead, CurriculumCenterHead_x5  # noqa: F401
+from .anchor_head import AnchorGenerator, AnchorHeadSingle, ResidualCoder  # noqa: F401

@@ -1,0 +1,422 @@
+"""`AnchorHeadSingle` -- the dense head of PointPillars, SECOND and the first stage of PV-RCNN
+(pcdet/models/dense_heads/anchor_head_single.py, anchor_head_template.py; `DENSE_HEAD.NAME: AnchorHeadSingle` in
+tools/cfgs/waymo_models/{pointpillar_1x,second,pv_rcnn}.yaml) as a registry drop-in: same constructor arguments, parameter
+names (`conv_cls`, `conv_box`, `conv_dir_cls`: a reference state dict loads with strict=True) and `forward(data_dict)`
+contract, with target assignment, the three losses + their gradients and the box decoding on the device
+(com_amd/csrc/anchorhead.hip; C ABI `pcd_anchor_*`): no host loop over frames and classes, no [N, M] IoU matrix, no
+`nonzero()`, no `.item()` -- forward + get_loss + backward can sit in a captured graph.
+
+Scope: AxisAlignedTargetAssigner (MATCH_HEIGHT False, POS_FRACTION < 0, NORM_BY_NUM_EXAMPLES False) + ResidualCoder
+(7 codes) + WeightedSmoothL1Loss + direction classifier.  Everything else the reference's template can be configured to is
+refused at construction with a PcdError that names the key."""
+import ctypes
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import _lib as L
+from .dense2d import _get
+
+KIND_FLOATS = 10      # include/pcd_ops.h: PCD_ANCHOR_KIND_FLOATS
+CLASS_FLOATS = 4      # include/pcd_ops.h: PCD_ANCHOR_CLASS_FLOATS
+MAX_KINDS = 32        # include/pcd_ops.h: PCD_ANCHOR_MAX_KINDS
+
+
+class AnchorGenerator:
+    """anchor_generator.py:4-60 with host arithmetic only (no `.cuda()`): the same list of [1, H, W, sizes, rotations, 7]
+    float32 tensors, bit for bit."""
+
+    def __init__(self, anchor_range, anchor_generator_config):
+        self.anchor_generator_cfg = anchor_generator_config
+        self.anchor_range = anchor_range
+        self.anchor_sizes = [c['anchor_sizes'] for c in anchor_generator_config]
+        self.anchor_rotations = [c['anchor_rotations'] for c in anchor_generator_config]
+        self.anchor_heights = [c['anchor_bottom_heights'] for c in anchor_generator_config]
+        self.align_center = [_get(c, 'align_center', False) for c in anchor_generator_config]
+        assert len(self.anchor_sizes) == len(self.anchor_rotations) == len(self.anchor_heights)
+        self.num_of_anchor_sets = len(self.anchor_sizes)
+
+    def shift_tables(self, grid_size, align_center):
+        """(x_shifts [W], y_shifts [H]) of one anchor set: float32 aranges over the range (:25-39)."""
+        r = self.anchor_range
+        if align_center:
+            x_stride, y_stride = (r[3] - r[0]) / grid_size[0], (r[4] - r[1]) / grid_size[1]
+            x_offset, y_offset = x_stride / 2, y_stride / 2
+        else:
+            x_stride, y_stride = (r[3] - r[0]) / (grid_size[0] - 1), (r[4] - r[1]) / (grid_size[1] - 1)
+            x_offset, y_offset = 0, 0
+        xs = torch.arange(r[0] + x_offset, r[3] + 1e-5, step=x_stride, dtype=torch.float32)
+        ys = torch.arange(r[1] + y_offset, r[4] + 1e-5, step=y_stride, dtype=torch.float32)
+        return xs, ys
+
+    def generate_anchors(self, grid_sizes):
+        assert len(grid_sizes) == self.num_of_anchor_sets
+        all_anchors, num_anchors_per_location = [], []
+        for grid_size, sizes, rotations, heights, align in zip(grid_sizes, self.anchor_sizes, self.anchor_rotations,
+                                                               self.anchor_heights, self.align_center):
+            num_anchors_per_location.append(len(rotations) * len(sizes) * len(heights))
+            xs, ys = self.shift_tables(grid_size, align)
+            zs = torch.tensor(heights, dtype=torch.float32)
+            sz = torch.tensor(sizes, dtype=torch.float32).view(-1, 3)
+            rot = torch.tensor(rotations, dtype=torch.float32)
+            a = torch.empty((zs.numel(), ys.numel(), xs.numel(), sz.shape[0], rot.numel(), 7), dtype=torch.float32)
+            a[..., 0] = xs.view(1, 1, -1, 1, 1)
+            a[..., 1] = ys.view(1, -1, 1, 1, 1)
+            a[..., 2] = zs.view(-1, 1, 1, 1, 1)
+            a[..., 3:6] = sz.view(1, 1, 1, -1, 1, 3)
+            a[..., 6] = rot.view(1, 1, 1, 1, -1)
+            a[..., 2] += a[..., 5] / 2                       # bottom height -> box centre (:58)
+            all_anchors.append(a)
+        return all_anchors, num_anchors_per_location
+
+
+class ResidualCoder:
+    """box_coder_utils.py:5-77 (7 codes, no sin/cos angle) for callers that use it directly."""
+
+    def __init__(self, code_size=7, encode_angle_by_sincos=False, **kwargs):
+        if encode_angle_by_sincos:
+            raise L.PcdError("ResidualCoder: encode_angle_by_sincos is not supported")
+        self.code_size = code_size
+        self.encode_angle_by_sincos = False
+
+    @staticmethod
+    def encode_torch(boxes, anchors):
+        a = torch.cat([anchors[..., :3], torch.clamp_min(anchors[..., 3:6], 1e-5), anchors[..., 6:]], dim=-1)
+        g = torch.cat([boxes[..., :3], torch.clamp_min(boxes[..., 3:6], 1e-5), boxes[..., 6:]], dim=-1)
+        diagonal = torch.sqrt(a[..., 3:4] ** 2 + a[..., 4:5] ** 2)
+        xy = (g[..., 0:2] - a[..., 0:2]) / diagonal
+        z = (g[..., 2:3] - a[..., 2:3]) / a[..., 5:6]
+        return torch.cat([xy, z, torch.log(g[..., 3:6] / a[..., 3:6]), g[..., 6:] - a[..., 6:]], dim=-1)
+
+    @staticmethod
+    def decode_torch(box_encodings, anchors):
+        t, a = box_encodings, anchors
+        diagonal = torch.sqrt(a[..., 3:4] ** 2 + a[..., 4:5] ** 2)
+        xy = t[..., 0:2] * diagonal + a[..., 0:2]
+        z = t[..., 2:3] * a[..., 5:6] + a[..., 2:3]
+        return torch.cat([xy, z, torch.exp(t[..., 3:6]) * a[..., 3:6], t[..., 6:] + a[..., 6:]], dim=-1)
+
+
+def _limit_period(val, offset=0.5, period=np.pi):
+    """common_utils.py:21-24"""
+    return val - torch.floor(val / period + offset) * period
+
+
+def anchor_tables(anchor_generator_cfg, class_names, anchor_range, grid_size_xy):
+    """The device tables of pcd_anchor_* (include/pcd_ops.h) as host float32 tensors: kinds [A, 10], classes [C, 4],
+    shifts [C, W + H], from the host generator's own values (so that the device sees the reference's anchors bit for bit)."""
+    gen = AnchorGenerator(anchor_range, anchor_generator_cfg)
+    strides = {int(c['feature_map_stride']) for c in anchor_generator_cfg}
+    if len(strides) != 1:
+        raise L.PcdError(f"AnchorHeadSingle: feature_map_stride differs between anchor classes ({sorted(strides)})")
+    fm = np.asarray(grid_size_xy[:2]) // strides.pop()
+    W, H = int(fm[0]), int(fm[1])
+    kinds, classes, shifts = [], [], []
+    for slot, cfg in enumerate(anchor_generator_cfg):
+        if len(cfg['anchor_bottom_heights']) != 1:
+            raise L.PcdError("AnchorHeadSingle: anchor_bottom_heights needs exactly one height per class")
+        if cfg['class_name'] not in class_names:
+            raise L.PcdError(f"AnchorHeadSingle: anchor class_name {cfg['class_name']!r} is not in class_names")
+        xs, ys = gen.shift_tables((W, H), gen.align_center[slot])
+        if xs.numel() != W or ys.numel() != H:
+            raise L.PcdError(f"AnchorHeadSingle: anchor grid {xs.numel()} x {ys.numel()}, feature map {W} x {H}")
+        shifts.append(torch.cat([xs, ys]))
+        classes.append([float(cfg['matched_threshold']), float(cfg['unmatched_threshold']),
+                        float(list(class_names).index(cfg['class_name']) + 1), 0.0])
+        bottom = torch.tensor(cfg['anchor_bottom_heights'], dtype=torch.float32)
+        for size in cfg['anchor_sizes']:
+            for rot in cfg['anchor_rotations']:
+                s = torch.tensor(size, dtype=torch.float32)
+                r = torch.tensor([rot], dtype=torch.float32)
+                zc = bottom + s[2:3] / 2
+                swap = ~(_limit_period(r, 0.5, np.pi).abs() < np.pi / 4)                 # box_utils.py:322-323
+                half = (s[[1, 0]] if bool(swap) else s[[0, 1]]) / 2
+                sc = torch.clamp_min(s, 1e-5)
+                diag = torch.sqrt(sc[0:1] ** 2 + sc[1:2] ** 2)
+                kinds.append(torch.cat([s, r, zc, torch.tensor([float(slot)]), half, diag, torch.zeros(1)]))
+    if len(kinds) > MAX_KINDS:
+        raise L.PcdError(f"AnchorHeadSingle: {len(kinds)} anchors per location, at most {MAX_KINDS}")
+    return (torch.stack(kinds).float().contiguous(), torch.tensor(classes, dtype=torch.float32),
+            torch.stack(shifts).float().contiguous(), H, W)
+
+
+def _strides3(tensors):
+    """element strides {batch, channel, y, x} of three [B, H, W, C] views (a missing map repeats the first)."""
+    vals = []
+    for t in tensors:
+        t = tensors[0] if t is None else t
+        s = t.stride()
+        vals += [s[0], s[3], s[1], s[2]]
+    return (ctypes.c_longlong * 12)(*vals)
+
+
+def _dt(t):
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise L.PcdError(f"anchor head: prediction maps must be float32 or bfloat16, got {t.dtype}")
+    return L.PCD_F32 if t.dtype == torch.float32 else L.PCD_BF16
+
+
+class AnchorTables:
+    """The three device tables + the static settings the kernels take."""
+
+    def __init__(self, kinds, classes, shifts, H, W, num_class, num_dir_bins, dir_offset, dir_limit_offset):
+        self.kinds, self.classes, self.shifts, self.H, self.W = kinds, classes, shifts, H, W
+        self.A, self.C = int(kinds.shape[0]), int(classes.shape[0])
+        self.num_class, self.num_dir_bins = int(num_class), int(num_dir_bins)
+        self.dir_offset, self.dir_limit_offset = float(dir_offset), float(dir_limit_offset)
+
+    def to(self, device):
+        return AnchorTables(self.kinds.to(device), self.classes.to(device), self.shifts.to(device), self.H, self.W,
+                            self.num_class, self.num_dir_bins, self.dir_offset, self.dir_limit_offset)
+
+
+def assign_targets(tab, gt_boxes):
+    """pcd_anchor_assign_targets: the reference's `all_targets_dict` (box_cls_labels int32 [B, N], box_reg_targets
+    [B, N, 7], reg_weights [B, N]) + num_pos int32 [B] and box_gt_index int32 [B, N] (the box of each positive)."""
+    if not gt_boxes.is_cuda:
+        raise L.PcdError("AnchorHeadSingle.assign_targets needs a HIP device tensor (there is no CPU fallback)")
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 8:
+        raise L.PcdError(f"AnchorHeadSingle.assign_targets: gt_boxes {tuple(gt_boxes.shape)}, want [B, M, 8]")
+    gt = gt_boxes.contiguous().float()
+    B, M = int(gt.shape[0]), int(gt.shape[1])
+    N = tab.H * tab.W * tab.A
+    dev = gt.device
+    lib = L.lib()
+    labels = torch.empty((B, N), dtype=torch.int32, device=dev)
+    targets = torch.empty((B, N, 7), dtype=torch.float32, device=dev)
+    weights = torch.empty((B, N), dtype=torch.float32, device=dev)
+    gt_index = torch.empty((B, N), dtype=torch.int32, device=dev)
+    num_pos = torch.empty((B,), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(int(lib.pcd_anchor_assign_workspace_bytes(B, M)), 256),), dtype=torch.uint8, device=dev)
+    L.check(lib.pcd_anchor_assign_targets(L.ptr(gt) if M else None, B, M, L.ptr(tab.kinds), tab.A, L.ptr(tab.classes), tab.C,
+                                          L.ptr(tab.shifts), tab.H, tab.W, L.ptr(labels), L.ptr(targets), L.ptr(weights),
+                                          L.ptr(gt_index), L.ptr(num_pos), L.ptr(ws), ws.numel(), L.stream_ptr()),
+            "pcd_anchor_assign_targets")
+    return {'box_cls_labels': labels, 'box_reg_targets': targets, 'reg_weights': weights, 'num_pos': num_pos,
+            'box_gt_index': gt_index}
+
+
+def _split(preds, tab, has_dir):
+    """the cls / box / dir channel blocks of the fused [B, H, W, C] prediction tensor (views)."""
+    nc, nb = tab.A * tab.num_class, tab.A * 7
+    nd = tab.A * tab.num_dir_bins if has_dir else 0
+    if preds.dim() != 4 or preds.shape[1] != tab.H or preds.shape[2] != tab.W or preds.shape[3] != nc + nb + nd:
+        raise L.PcdError(f"anchor head: predictions {tuple(preds.shape)}, want [B, {tab.H}, {tab.W}, {nc + nb + nd}]")
+    return preds[..., :nc], preds[..., nc:nc + nb], (preds[..., nc + nb:] if has_dir else None)
+
+
+class _AnchorLoss(torch.autograd.Function):
+    """get_loss through pcd_anchor_loss_forward / _backward: 2 + 1 launches for the three losses and the gradient of
+    the fused prediction tensor."""
+
+    @staticmethod
+    def forward(ctx, preds, labels, targets, num_pos, code_weights, tab, has_dir, weights):
+        if not preds.is_cuda:
+            raise L.PcdError("AnchorHeadSingle.get_loss needs HIP device tensors (there is no CPU fallback)")
+        cls, box, dr = _split(preds, tab, has_dir)
+        B = int(preds.shape[0])
+        lib = L.lib()
+        out = torch.empty((4,), dtype=torch.float32, device=preds.device)
+        ws = torch.empty((max(int(lib.pcd_anchor_loss_workspace_bytes(B, tab.H, tab.W, tab.A)), 256),), dtype=torch.uint8,
+                         device=preds.device)
+        L.check(lib.pcd_anchor_loss_forward(
+            L.ptr(cls), L.ptr(box), L.ptr(dr), _dt(preds), _strides3([cls, box, dr]), L.ptr(labels), L.ptr(targets),
+            L.ptr(num_pos), B, tab.H, tab.W, tab.A, tab.num_class, tab.num_dir_bins, L.ptr(tab.kinds), L.ptr(code_weights),
+            weights[0], weights[1], weights[2], tab.dir_offset, L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr()),
+            "pcd_anchor_loss_forward")
+        ctx.save_for_backward(preds, labels, targets, num_pos, code_weights)
+        ctx.meta = (tab, has_dir, weights)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_out):
+        preds, labels, targets, num_pos, code_weights = ctx.saved_tensors
+        tab, has_dir, weights = ctx.meta
+        d_preds = torch.empty_strided(preds.shape, preds.stride(), dtype=preds.dtype, device=preds.device)
+        cls, box, dr = _split(preds, tab, has_dir)
+        d_cls, d_box, d_dr = _split(d_preds, tab, has_dir)
+        g = g_loss.detach().to(torch.float32).reshape(1).contiguous()
+        L.check(L.lib().pcd_anchor_loss_backward(
+            L.ptr(cls), L.ptr(box), L.ptr(dr), L.ptr(d_cls), L.ptr(d_box), L.ptr(d_dr), _dt(preds),
+            _strides3([cls, box, dr]), L.ptr(labels), L.ptr(targets), L.ptr(num_pos), int(preds.shape[0]), tab.H, tab.W,
+            tab.A, tab.num_class, tab.num_dir_bins, L.ptr(tab.kinds), L.ptr(code_weights), weights[0], weights[1],
+            weights[2], tab.dir_offset, L.ptr(g), L.stream_ptr()), "pcd_anchor_loss_backward")
+        return d_preds, None, None, None, None, None, None, None
+
+
+def anchor_loss(preds, targets_dict, tab, code_weights, cls_weight, loc_weight, dir_weight, has_dir=True):
+    """(rpn_loss, out) with out = device f32 [rpn_loss, rpn_loss_cls, rpn_loss_loc, rpn_loss_dir]; `preds` is the fused
+    [B, H, W, A * (num_class + 7 + bins)] tensor (cls, box, dir channel blocks; any strides, f32 or bf16)."""
+    return _AnchorLoss.apply(preds, targets_dict['box_cls_labels'], targets_dict['box_reg_targets'], targets_dict['num_pos'],
+                             code_weights, tab, bool(has_dir), (float(cls_weight), float(loc_weight), float(dir_weight)))
+
+
+def decode_boxes(tab, cls_preds, box_preds, dir_cls_preds=None):
+    """pcd_anchor_decode: (batch_cls_preds f32 [B, N, num_class], batch_box_preds f32 [B, N, 7]) from [B, H, W, C] maps."""
+    if not cls_preds.is_cuda:
+        raise L.PcdError("AnchorHeadSingle.generate_predicted_boxes needs HIP device tensors (there is no CPU fallback)")
+    maps = [cls_preds, box_preds, dir_cls_preds]
+    if any(m is not None and (m.dtype != cls_preds.dtype or m.dim() != 4 or m.shape[:3] != cls_preds.shape[:3]) for m in maps):
+        raise L.PcdError("anchor head: the three prediction maps must share dtype and [B, H, W]")
+    B = int(cls_preds.shape[0])
+    if (cls_preds.shape[1], cls_preds.shape[2]) != (tab.H, tab.W) or cls_preds.shape[3] != tab.A * tab.num_class \
+            or box_preds.shape[3] != tab.A * 7 or (dir_cls_preds is not None and dir_cls_preds.shape[3] != tab.A * tab.num_dir_bins):
+        raise L.PcdError(f"anchor head: prediction maps {tuple(cls_preds.shape)} / {tuple(box_preds.shape)} do not match "
+                         f"the {tab.H} x {tab.W} x {tab.A} anchors")
+    N = tab.H * tab.W * tab.A
+    boxes = torch.empty((B, N, 7), dtype=torch.float32, device=cls_preds.device)
+    scores = torch.empty((B, N, tab.num_class), dtype=torch.float32, device=cls_preds.device)
+    L.check(L.lib().pcd_anchor_decode(
+        L.ptr(cls_preds), L.ptr(box_preds), L.ptr(dir_cls_preds), _dt(cls_preds), _strides3(maps), B, tab.H, tab.W, tab.A,
+        tab.C, tab.num_class, tab.num_dir_bins, L.ptr(tab.kinds), L.ptr(tab.shifts), tab.dir_offset, tab.dir_limit_offset,
+        L.ptr(boxes), L.ptr(scores), L.stream_ptr()), "pcd_anchor_decode")
+    return scores, boxes
+
+
+def post_processing(batch_dict, post_process_cfg, num_class=None):
+    """The single-head, class-agnostic-NMS branch of Detector3DTemplate.post_processing (detector3d_template.py:178-290
+    with model_nms_utils.py:6-25) over com_amd.iou3d_nms: the reference's list of pred_boxes / pred_scores / pred_labels
+    dicts.  (Eager, with the reference's read-backs; a static, capturable form is not part of this module.)"""
+    from .center_head import class_agnostic_nms
+    nms_cfg = _get(post_process_cfg, 'NMS_CONFIG')
+    if _get(nms_cfg, 'MULTI_CLASSES_NMS', False):
+        raise L.PcdError("anchor head post_processing: MULTI_CLASSES_NMS is not supported")
+    pred_dicts = []
+    for index in range(int(batch_dict['batch_size'])):
+        box_preds = batch_dict['batch_box_preds'][index]
+        cls_preds = batch_dict['batch_cls_preds'][index]
+        src_cls_preds = cls_preds
+        if not batch_dict.get('cls_preds_normalized', False):
+            cls_preds = torch.sigmoid(cls_preds)
+        scores, label_preds = torch.max(cls_preds, dim=-1)
+        label_preds = label_preds + 1
+        selected, selected_scores = class_agnostic_nms(scores, box_preds, nms_cfg,
+                                                       score_thresh=_get(post_process_cfg, 'SCORE_THRESH', None))
+        if _get(post_process_cfg, 'OUTPUT_RAW_SCORE', False):
+            selected_scores = torch.max(src_cls_preds, dim=-1)[0][selected]
+        pred_dicts.append({'pred_boxes': box_preds[selected], 'pred_scores': selected_scores,
+                           'pred_labels': label_preds[selected]})
+    return pred_dicts
+
+
+class AnchorHeadSingle(nn.Module):
+    """anchor_head_single.py:7-76 + anchor_head_template.py (module docstring).  get_loss() returns (rpn_loss, tb_dict)
+    with DEVICE scalars in tb_dict."""
+
+    def __init__(self, model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range,
+                 predict_boxes_when_training=True, **kwargs):
+        super().__init__()
+        self.model_cfg, self.num_class, self.class_names = model_cfg, int(num_class), list(class_names)
+        self.predict_boxes_when_training = predict_boxes_when_training
+        ta = _get(model_cfg, 'TARGET_ASSIGNER_CONFIG')
+        loss_cfg = _get(model_cfg, 'LOSS_CONFIG')
+        self._refuse(model_cfg, ta, loss_cfg)
+        self.use_multihead = False
+        self.box_coder = ResidualCoder(num_dir_bins=_get(ta, 'NUM_DIR_BINS', 6), **(_get(ta, 'BOX_CODER_CONFIG', None) or {}))
+        ag_cfg = _get(model_cfg, 'ANCHOR_GENERATOR_CONFIG')
+        grid_xy = np.asarray(grid_size)[:2]
+        gen = AnchorGenerator(point_cloud_range, ag_cfg)
+        self.anchors, per_location = gen.generate_anchors([grid_xy // c['feature_map_stride'] for c in ag_cfg])
+        self.num_anchors_per_location = sum(per_location)
+        self.use_dir = _get(model_cfg, 'USE_DIRECTION_CLASSIFIER', None) is not None
+        self.num_dir_bins = int(_get(model_cfg, 'NUM_DIR_BINS', 2)) if self.use_dir else 1
+        kinds, classes, shifts, H, W = anchor_tables(ag_cfg, self.class_names, point_cloud_range, grid_xy)
+        assert kinds.shape[0] == self.num_anchors_per_location
+        self._tables_host = AnchorTables(kinds, classes, shifts, H, W, self.num_class, self.num_dir_bins,
+                                         _get(model_cfg, 'DIR_OFFSET', 0.0) if self.use_dir else 0.0,
+                                         _get(model_cfg, 'DIR_LIMIT_OFFSET', 0.0) if self.use_dir else 0.0)
+        self._tables = {}
+        lw = _get(loss_cfg, 'LOSS_WEIGHTS')
+        if len(lw['code_weights']) != 7:
+            raise L.PcdError(f"AnchorHeadSingle: LOSS_WEIGHTS.code_weights needs 7 values, got {len(lw['code_weights'])}")
+        self.loss_weights = (float(lw['cls_weight']), float(lw['loc_weight']), float(lw.get('dir_weight', 0.0)))
+        self.register_buffer('code_weights', torch.tensor(lw['code_weights'], dtype=torch.float32), persistent=False)
+        self.forward_ret_dict = {}
+        A = self.num_anchors_per_location
+        self.conv_cls = nn.Conv2d(input_channels, A * self.num_class, kernel_size=1)
+        self.conv_box = nn.Conv2d(input_channels, A * self.box_coder.code_size, kernel_size=1)
+        self.conv_dir_cls = nn.Conv2d(input_channels, A * self.num_dir_bins, kernel_size=1) if self.use_dir else None
+        self.init_weights()
+
+    @staticmethod
+    def _refuse(model_cfg, ta, loss_cfg):
+        """the configurations outside the scope of the kernels: a PcdError that names the key"""
+        def no(key, why):
+            raise L.PcdError(f"AnchorHeadSingle: {key} {why} is not supported by the HIP anchor head")
+        if _get(model_cfg, 'USE_MULTIHEAD', False):
+            no('USE_MULTIHEAD', '= True')
+        if _get(ta, 'NAME') != 'AxisAlignedTargetAssigner':
+            no('TARGET_ASSIGNER_CONFIG.NAME', f"= {_get(ta, 'NAME')!r}")
+        if _get(ta, 'MATCH_HEIGHT', False):
+            no('MATCH_HEIGHT', '= True')
+        if _get(ta, 'POS_FRACTION', -1.0) >= 0:
+            no('POS_FRACTION', '>= 0 (random sampling)')
+        if _get(ta, 'NORM_BY_NUM_EXAMPLES', False):
+            no('NORM_BY_NUM_EXAMPLES', '= True')
+        if _get(ta, 'BOX_CODER', 'ResidualCoder') != 'ResidualCoder':
+            no('BOX_CODER', f"= {_get(ta, 'BOX_CODER')!r}")
+        if (_get(ta, 'BOX_CODER_CONFIG', None) or {}).get('encode_angle_by_sincos', False):
+            no('encode_angle_by_sincos', '= True')
+        if _get(loss_cfg, 'REG_LOSS_TYPE', None) not in (None, 'WeightedSmoothL1Loss'):
+            no('REG_LOSS_TYPE', f"= {_get(loss_cfg, 'REG_LOSS_TYPE')!r}")
+
+    def init_weights(self):
+        """anchor_head_single.py:36-39"""
+        pi = 0.01
+        nn.init.constant_(self.conv_cls.bias, -np.log((1 - pi) / pi))
+        nn.init.normal_(self.conv_box.weight, mean=0, std=0.001)
+
+    def tables(self, device):
+        key = str(device)
+        if key not in self._tables:
+            self._tables[key] = self._tables_host.to(device)
+        return self._tables[key]
+
+    def assign_targets(self, gt_boxes):
+        """anchor_head_template.py:89-100 -> axis_aligned_target_assigner.py:36-210, three launches for the batch."""
+        return assign_targets(self.tables(gt_boxes.device), gt_boxes)
+
+    def get_loss(self):
+        """anchor_head_template.py:220-227"""
+        f = self.forward_ret_dict
+        loss, out = anchor_loss(f['preds'], f, self.tables(f['preds'].device), self.code_weights, *self.loss_weights,
+                                has_dir=self.use_dir)
+        tb_dict = {'rpn_loss_cls': out[1], 'rpn_loss_loc': out[2], 'rpn_loss': out[0]}
+        if self.use_dir:
+            tb_dict['rpn_loss_dir'] = out[3]
+        return loss, tb_dict
+
+    def generate_predicted_boxes(self, batch_size, cls_preds, box_preds, dir_cls_preds=None):
+        """anchor_head_template.py:229-276"""
+        assert cls_preds.shape[0] == batch_size
+        return decode_boxes(self.tables(cls_preds.device), cls_preds, box_preds, dir_cls_preds)
+
+    def forward(self, data_dict):
+        """anchor_head_single.py:41-76.  The three 1 x 1 convs run as ONE product over the channels-last map: the
+        [B, H, W, C] prediction maps of the reference are channel blocks of its result (views, no permute copies)."""
+        x = data_dict['spatial_features_2d']
+        convs = [self.conv_cls, self.conv_box] + ([self.conv_dir_cls] if self.use_dir else [])
+        weight = torch.cat([c.weight.flatten(1) for c in convs], dim=0)
+        bias = torch.cat([c.bias for c in convs], dim=0)
+        preds = F.linear(x.permute(0, 2, 3, 1), weight.to(x.dtype), bias.to(x.dtype))
+        tab = self._tables_host
+        cls_preds, box_preds, dir_cls_preds = _split(preds, tab, self.use_dir)
+        self.forward_ret_dict = {'preds': preds, 'cls_preds': cls_preds, 'box_preds': box_preds}
+        if self.use_dir:
+            self.forward_ret_dict['dir_cls_preds'] = dir_cls_preds
+        if self.training:
+            self.forward_ret_dict.update(self.assign_targets(gt_boxes=data_dict['gt_boxes']))
+        if not self.training or self.predict_boxes_when_training:
+            with torch.no_grad():
+                batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(
+                    batch_size=data_dict['batch_size'], cls_preds=cls_preds, box_preds=box_preds, dir_cls_preds=dir_cls_preds)
+            data_dict['batch_cls_preds'] = batch_cls_preds
+            data_dict['batch_box_preds'] = batch_box_preds
+            data_dict['cls_preds_normalized'] = False
+        return data_dict
+
+    def post_processing(self, batch_dict, post_process_cfg):
+        return post_processing(batch_dict, post_process_cfg)

@@ -719,6 +719,67 @@ int pcd_centerhead_loss_backward(const void *hm, void *d_hm, int hm_dtype, const
                                  const float *out, const float *grad_out, void *stream);
 
 /* ============================================================================================
+ * (f3) AnchorHeadSingle on the device (the dense head of PointPillars, SECOND and the first stage of PV-RCNN:
+ *      tools/cfgs/waymo_models/{pointpillar_1x,second,pv_rcnn}.yaml) -- com_amd/csrc/anchorhead.hip.
+ *      AxisAlignedTargetAssigner (MATCH_HEIGHT False, POS_FRACTION < 0, NORM_BY_NUM_EXAMPLES False) + ResidualCoder (7 codes)
+ *      + WeightedSmoothL1Loss + direction classifier.  Every entry point takes a stream, allocates nothing, reads nothing
+ *      back and launches a fixed number of kernels (3 / 2 / 1 / 1).
+ *
+ *   Anchors are described, never stored: anchor n of a frame is (y, x, kind) = (n / (W * A), n / A % W, n % A) -- the
+ *   reference's (y, x, class, size, rotation) order, i.e. the channel order of conv_cls -- with
+ *     kinds   device f32 [A][PCD_ANCHOR_KIND_FLOATS]: dx, dy, dz, heading, z of the centre (bottom height + dz / 2),
+ *             class slot, half extents along x and y of the axis-aligned BEV box (box_utils.py:322-324 evaluated on the
+ *             host), diagonal sqrt(dx^2 + dy^2), 0;  A <= PCD_ANCHOR_MAX_KINDS
+ *     classes device f32 [n_classes][PCD_ANCHOR_CLASS_FLOATS]: matched_threshold, unmatched_threshold, 1-based class id
+ *             of the ground-truth boxes that compete for this class's anchors, 0;  n_classes <= PCD_ANCHOR_MAX_CLASSES
+ *     shifts  device f32 [n_classes][W + H]: the host generator's x table, then its y table (anchor_generator.py:34-39),
+ *             so that the device uses bit-identical anchor coordinates and not a re-derived origin + i * stride
+ *   Prediction maps: [B, H, W, C] views addressed through element strides {batch, channel, y, x} (three rows: cls, box,
+ *   dir), one dtype (PCD_F32 / PCD_BF16) for the three, arithmetic in fp32; channel of (kind k, item j) = k * items + j.
+ *
+ *   pcd_anchor_assign_targets  axis_aligned_target_assigner.py:36-210 for the whole batch and all classes.
+ *     gt_boxes [B][M][8] f32 (x, y, z, dx, dy, dz, heading, 1-based class id; zero rows = padding, anywhere).
+ *     box_cls_labels int32 [B][N] (-1 ignore, 0 background, class id), box_reg_targets f32 [B][N][7] (ResidualCoder.
+ *     encode_torch at the positives, 0 elsewhere), reg_weights f32 [B][N], gt_index int32 [B][N] (the box a positive
+ *     regresses to = its arg-max box, -1 elsewhere; may be NULL), num_pos int32 [B].  Nearest-BEV IoU in fp32 in the
+ *     reference's operation order without contraction; per anchor the maximum over its class's boxes (lowest index on
+ *     ties); every anchor whose IoU with a box EQUALS that box's non-zero maximum is positive with ITS OWN arg-max box
+ *     (:155-158); maximum >= matched: positive; else < unmatched: background; else ignore.
+ *   pcd_anchor_loss_forward   anchor_head_template.py:102-227: out[0] = rpn_loss, [1] = rpn_loss_cls, [2] = rpn_loss_loc,
+ *     [3] = rpn_loss_dir (weighted, device f32[4]).  Sums: per-workgroup partials, then one ordered pass (no float atomics).
+ *     num_class == 1: class-agnostic labels (:114-116).  dir_preds NULL: no direction classifier.
+ *   pcd_anchor_loss_backward  gradients with respect to the three maps (same layout and dtype, every element written)
+ *     for an upstream gradient *grad_out (device scalar).
+ *   pcd_anchor_decode         generate_predicted_boxes (:229-276): batch_box_preds f32 [B][N][7] (ResidualCoder.
+ *     decode_torch + the direction-bin correction), batch_cls_preds f32 [B][N][num_class] (the logits).
+ * ============================================================================================ */
+#define PCD_ANCHOR_KIND_FLOATS 10
+#define PCD_ANCHOR_CLASS_FLOATS 4
+#define PCD_ANCHOR_MAX_KINDS 32
+#define PCD_ANCHOR_MAX_CLASSES 16
+size_t pcd_anchor_assign_workspace_bytes(int batch, int n_boxes);
+int pcd_anchor_assign_targets(const float *gt_boxes, int batch, int n_boxes, const float *kinds, int n_kinds,
+                              const float *classes, int n_classes, const float *shifts, int height, int width,
+                              int *box_cls_labels, float *box_reg_targets, float *reg_weights, int *gt_index, int *num_pos,
+                              void *workspace, size_t workspace_bytes, void *stream);
+size_t pcd_anchor_loss_workspace_bytes(int batch, int height, int width, int n_kinds);
+int pcd_anchor_loss_forward(const void *cls_preds, const void *box_preds, const void *dir_preds, int dtype,
+                            const long long *strides_host /*[3][4]*/, const int *box_cls_labels,
+                            const float *box_reg_targets, const int *num_pos, int batch, int height, int width, int n_kinds,
+                            int num_class, int num_dir_bins, const float *kinds, const float *code_weights /*device [7]*/,
+                            float cls_weight, float loc_weight, float dir_weight, float dir_offset, float *out /*device [4]*/,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int pcd_anchor_loss_backward(const void *cls_preds, const void *box_preds, const void *dir_preds, void *d_cls, void *d_box,
+                             void *d_dir, int dtype, const long long *strides_host, const int *box_cls_labels,
+                             const float *box_reg_targets, const int *num_pos, int batch, int height, int width, int n_kinds,
+                             int num_class, int num_dir_bins, const float *kinds, const float *code_weights, float cls_weight,
+                             float loc_weight, float dir_weight, float dir_offset, const float *grad_out, void *stream);
+int pcd_anchor_decode(const void *cls_preds, const void *box_preds, const void *dir_preds, int dtype,
+                      const long long *strides_host, int batch, int height, int width, int n_kinds, int n_classes,
+                      int num_class, int num_dir_bins, const float *kinds, const float *shifts, float dir_offset,
+                      float dir_limit_offset, float *batch_box_preds, float *batch_cls_preds, void *stream);
+
+/* ============================================================================================
  * (f2, BASELINE config 3) The COM curriculum head on the device.  Replaces, for one head and the whole batch:
  *   pcd_com_cluster_groups   CurriculumCenterHead.cluster         pcdet/models/dense_heads/curriculum_center_head.py:414-459
  *   pcd_com_assign_targets   assign_targets / assign_target_of_single_head  same file :108-307 (+ centernet_utils.py:46-106)
