@@ -188,16 +188,6 @@ __global__ __launch_bounds__(256) void anc_assign_kernel(const float *gt, const 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ld_el(const void *p, int dt, long long off) {
-    return dt == PCD_F32 ? ((const float *)p)[off] : bf16_bits_to_f32(((const unsigned short *)p)[off]);
-}
-__device__ __forceinline__ void st_el(void *p, int dt, long long off, float v) {
-    if (dt == PCD_F32)
-        ((float *)p)[off] = v;
-    else
-        ((unsigned short *)p)[off] = f32_to_bf16_bits(v);
-}
-
 struct AncMaps {            // the three prediction maps (and their gradients): element strides {batch, channel, y, x}
     const void *p[3];
     void *g[3];
@@ -260,10 +250,10 @@ __global__ __launch_bounds__(256) void anc_loss_kernel(AncMaps m, AncLossCfg c, 
         for (int j = 0; j < c.num_class; ++j) {
             const long long off = base[0] + (long long)(k * c.num_class + j) * m.s[0][1];
             if (label < 0) {
-                if (GRAD) st_el(m.g[0], m.dtype, off, 0.f);
+                if (GRAD) store_el(m.g[0], m.dtype, off, 0.f);
                 continue;
             }
-            const float xv = ld_el(m.p[0], m.dtype, off);
+            const float xv = load_el(m.p[0], m.dtype, off);
             const float t = (j == tcls) ? 1.f : 0.f;
             const float p = 1.f / (1.f + expf(-xv));
             const float aw = t * 0.25f + (1.f - t) * 0.75f;
@@ -274,7 +264,7 @@ __global__ __launch_bounds__(256) void anc_loss_kernel(AncMaps m, AncLossCfg c, 
             } else {
                 const float dpt = (1.f - 2.f * t) * p * (1.f - p);
                 const float g = aw * (2.f * pt * dpt * bce + pt * pt * (p - t));
-                st_el(m.g[0], m.dtype, off, g * up * c.cls_w);
+                store_el(m.g[0], m.dtype, off, g * up * c.cls_w);
             }
         }
         // ---- regression: smooth-L1, beta 1/9, with the sin-difference substitution on the heading (:141-148, :192-193)
@@ -283,10 +273,10 @@ __global__ __launch_bounds__(256) void anc_loss_kernel(AncMaps m, AncLossCfg c, 
         for (int j = 0; j < 7; ++j) {
             const long long off = base[1] + (long long)(k * 7 + j) * m.s[1][1];
             if (!pos) {
-                if (GRAD) st_el(m.g[1], m.dtype, off, 0.f);
+                if (GRAD) store_el(m.g[1], m.dtype, off, 0.f);
                 continue;
             }
-            const float pv = ld_el(m.p[1], m.dtype, off), tv = tg[j], cw = code_weights[j];
+            const float pv = load_el(m.p[1], m.dtype, off), tv = tg[j], cw = code_weights[j];
             float in = pv, ta = tv, din = 1.f;
             if (j == 6) {
                 const float sp = sinf(pv), cp = cosf(pv), sn = sinf(tv), cs = cosf(tv);
@@ -301,7 +291,7 @@ __global__ __launch_bounds__(256) void anc_loss_kernel(AncMaps m, AncLossCfg c, 
                 l_loc += (ad < beta ? 0.5f * (ad * ad) / beta : ad - 0.5f * beta) * w;
             } else {
                 const float dl = ad < beta ? diff / beta : (diff > 0.f ? 1.f : -1.f);
-                st_el(m.g[1], m.dtype, off, nan_t ? 0.f : dl * din * cw * up * c.loc_w);
+                store_el(m.g[1], m.dtype, off, nan_t ? 0.f : dl * din * cw * up * c.loc_w);
             }
         }
         // ---- direction: cross entropy on the heading bin (:150-164, :202-216; loss_utils.py:452-469)
@@ -309,7 +299,7 @@ __global__ __launch_bounds__(256) void anc_loss_kernel(AncMaps m, AncLossCfg c, 
             const int nb = c.num_bins;
             if (!pos) {
                 if (GRAD)
-                    for (int j = 0; j < nb; ++j) st_el(m.g[2], m.dtype, base[2] + (long long)(k * nb + j) * m.s[2][1], 0.f);
+                    for (int j = 0; j < nb; ++j) store_el(m.g[2], m.dtype, base[2] + (long long)(k * nb + j) * m.s[2][1], 0.f);
             } else {
                 const float rot_gt = tg[6] + s_kind[k * ANC_KIND_F + K_ROT];
                 const float v = rot_gt - c.dir_offset;
@@ -321,7 +311,7 @@ __global__ __launch_bounds__(256) void anc_loss_kernel(AncMaps m, AncLossCfg c, 
 #pragma unroll
                 for (int j = 0; j < ANC_MAX_BINS; ++j)
                     if (j < nb) {
-                        lg[j] = ld_el(m.p[2], m.dtype, base[2] + (long long)(k * nb + j) * m.s[2][1]);
+                        lg[j] = load_el(m.p[2], m.dtype, base[2] + (long long)(k * nb + j) * m.s[2][1]);
                         mx = fmaxf(mx, lg[j]);
                     }
                 float se = 0.f, lb = 0.f;
@@ -338,7 +328,7 @@ __global__ __launch_bounds__(256) void anc_loss_kernel(AncMaps m, AncLossCfg c, 
 #pragma unroll
                     for (int j = 0; j < ANC_MAX_BINS; ++j)
                         if (j < nb)
-                            st_el(m.g[2], m.dtype, base[2] + (long long)(k * nb + j) * m.s[2][1],
+                            store_el(m.g[2], m.dtype, base[2] + (long long)(k * nb + j) * m.s[2][1],
                                   (expf(lg[j] - lse) - (j == bin ? 1.f : 0.f)) * up * c.dir_w);
                 }
             }
@@ -393,10 +383,10 @@ __global__ __launch_bounds__(256) void anc_decode_kernel(AncMaps m, AncDecodeCfg
     for (int q = 0; q < 3; ++q) base[q] = (long long)b * m.s[q][0] + (long long)y * m.s[q][2] + (long long)x * m.s[q][3];
     const size_t o = (size_t)b * N + n;
     for (int j = 0; j < c.num_class; ++j)
-        cls_out[o * c.num_class + j] = ld_el(m.p[0], m.dtype, base[0] + (long long)(k * c.num_class + j) * m.s[0][1]);
+        cls_out[o * c.num_class + j] = load_el(m.p[0], m.dtype, base[0] + (long long)(k * c.num_class + j) * m.s[0][1]);
     float t[7];
 #pragma unroll
-    for (int j = 0; j < 7; ++j) t[j] = ld_el(m.p[1], m.dtype, base[1] + (long long)(k * 7 + j) * m.s[1][1]);
+    for (int j = 0; j < 7; ++j) t[j] = load_el(m.p[1], m.dtype, base[1] + (long long)(k * 7 + j) * m.s[1][1]);
     float r[7];                                                          // box_coder_utils.py:54-77
     r[0] = t[0] * a.diag + a.xa;
     r[1] = t[1] * a.diag + a.ya;
@@ -407,9 +397,9 @@ __global__ __launch_bounds__(256) void anc_decode_kernel(AncMaps m, AncDecodeCfg
     r[6] = t[6] + a.ra;
     if (m.p[2]) {                                                        // anchor_head_template.py:258-269
         int lab = 0;
-        float mx = ld_el(m.p[2], m.dtype, base[2] + (long long)(k * c.num_bins) * m.s[2][1]);
+        float mx = load_el(m.p[2], m.dtype, base[2] + (long long)(k * c.num_bins) * m.s[2][1]);
         for (int j = 1; j < c.num_bins; ++j) {
-            const float v = ld_el(m.p[2], m.dtype, base[2] + (long long)(k * c.num_bins + j) * m.s[2][1]);
+            const float v = load_el(m.p[2], m.dtype, base[2] + (long long)(k * c.num_bins + j) * m.s[2][1]);
             if (v > mx) {
                 mx = v;
                 lab = j;

@@ -15,44 +15,23 @@ __global__ __launch_bounds__(64) void assign_rows_kernel(const float *__restrict
                                                          long long *__restrict__ mask, int4 *__restrict__ draw) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const float *rows = gt + (size_t)b * n * G.code;
-    const int out_code = G.code;                              // ret_boxes rows: code - 1 + 1 values
     int count = 0;
     for (int base = 0; base < n && count < G.num_max; base += 64) {
         const int r = base + lane;
-        int local = 0;
-        if (r < n) {
-            const int cls = (int)rows[(size_t)r * G.code + G.code - 1];
-            local = (cls >= 0 && cls < 16) ? G.cls_map[cls] : 0;
-        }
+        const int local = assign_class(rows, r, n, G);
         int total;
         const int k = count + wave_rank(local > 0, total);
         count += total;
         if (local <= 0 || k >= G.num_max) continue;
         const float *q = rows + (size_t)r * G.code;
-        float cx = (q[0] - G.range_x) / G.vs_x / (float)G.stride;
-        float cy = (q[1] - G.range_y) / G.vs_y / (float)G.stride;
-        cx = fminf(fmaxf(cx, 0.0f), (float)G.W - 0.5f);
-        cy = fminf(fmaxf(cy, 0.0f), (float)G.H - 0.5f);
-        const int ix = (int)cx, iy = (int)cy;
-        const float dx = q[3] / G.vs_x / (float)G.stride, dy = q[4] / G.vs_y / (float)G.stride;
-        int radius = (int)gaussian_radius_f32(dx, dy, G.overlap);
-        radius = radius < G.min_radius ? G.min_radius : radius;
+        const AssignRow a = assign_row(q, G);
         const size_t at = (size_t)b * G.num_max + k;
         int4 d = make_int4(-1, 0, 0, 0);
-        if (dx > 0.0f && dy > 0.0f && ix >= 0 && ix <= G.W && iy >= 0 && iy <= G.H) {
-            inds[at] = (long long)iy * G.W + ix;
+        if (a.valid) {
+            inds[at] = (long long)a.iy * G.W + a.ix;
             mask[at] = 1;
-            float *o = ret_boxes + at * out_code;
-            o[0] = cx - (float)ix;
-            o[1] = cy - (float)iy;
-            o[2] = q[2];
-            o[3] = logf(q[3]);
-            o[4] = logf(q[4]);
-            o[5] = logf(q[5]);
-            o[6] = cosf(q[6]);
-            o[7] = sinf(q[6]);
-            for (int j = 8; j < out_code; ++j) o[j] = q[j - 1];
-            d = make_int4(local - 1, ix, iy, radius);
+            encode_box(q, a, G.code, ret_boxes + at * G.code);
+            d = make_int4(local - 1, a.ix, a.iy, a.radius);
         }
         draw[at] = d;
     }
@@ -79,12 +58,8 @@ extern "C" int pcd_centerhead_assign_targets(const float *gt_boxes, int batch, i
     if (!heatmap || !ret_boxes || !inds || !mask) return PCD_ERR_INVALID_ARG;
     if (n_boxes > 0 && !gt_boxes) return PCD_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < pcd_centerhead_assign_workspace_bytes(batch, num_max_objs)) return PCD_ERR_WORKSPACE;
-    AssignGeom G = {};
-    G.range_x = range_xy_host[0]; G.range_y = range_xy_host[1];
-    G.vs_x = voxel_size_xy_host[0]; G.vs_y = voxel_size_xy_host[1];
-    G.stride = feature_map_stride; G.W = fm_w; G.H = fm_h; G.num_max = num_max_objs; G.min_radius = min_radius;
-    G.code = code_size; G.head_classes = head_classes; G.overlap = gaussian_overlap;
-    for (int i = 0; i < n_class_map; ++i) G.cls_map[i] = class_map_host[i];
+    const AssignGeom G = assign_geom(range_xy_host, voxel_size_xy_host, feature_map_stride, fm_w, fm_h, num_max_objs,
+                                     min_radius, code_size, head_classes, gaussian_overlap, class_map_host, n_class_map);
     hipStream_t st = (hipStream_t)stream;
     int4 *draw = (int4 *)workspace;
     pcd_fill(heatmap, 0, (size_t)batch * head_classes * fm_h * fm_w * sizeof(float), st);
@@ -123,22 +98,14 @@ __global__ __launch_bounds__(256) void chl_forward_kernel(ChlMap hm, const float
     const long long total = (long long)B * C * H * W;
     double pos = 0.0, neg = 0.0, npos = 0.0, conf = 0.0;
     for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < (unsigned)total; e += CHL_BLOCKS * 256u) {
-        const int x = (int)(e % (unsigned)W);
-        unsigned t = e / (unsigned)W;
-        const int y = (int)(t % (unsigned)H);
-        t /= (unsigned)H;
-        const int c = (int)(t % (unsigned)C), b = (int)(t / (unsigned)C);
         const float g = gt[e];
-        float p = chl_sigmoid(chl_load(hm, b * hm.sb + c * hm.sc + y * hm.sh + x * hm.sw));
-        p = fminf(fmaxf(p, 1e-4f), 1.0f - 1e-4f);
+        const float p = chl_pred(hm, chl_at_linear(hm, e, C, H, W));
         if (g == 1.0f) {
-            const float q = 1.0f - p;
-            pos += (double)(logf(p) * (q * q));
+            pos += (double)focal_pos(p);
             npos += 1.0;
             conf += (double)p;
         } else if (g < 1.0f) {
-            const float w1 = 1.0f - g, w2 = w1 * w1;
-            neg += (double)(logf(1.0f - p) * (p * p) * (w2 * w2));
+            neg += (double)focal_neg(p, g);
         }
     }
     double *row = partial + (size_t)blockIdx.x * pstride;
@@ -147,40 +114,7 @@ __global__ __launch_bounds__(256) void chl_forward_kernel(ChlMap hm, const float
     if (threadIdx.x == 0) {
         row[0] = s0; row[1] = s1; row[2] = s2; row[3] = s3;
     }
-    // regression: workgroup b < B takes the objects of frame b (a thread per object, all code dimensions: the gathers of
-    // one object are independent loads), every workgroup writes its row (zeros beyond the frames)
-    double acc[CHL_MAX_DIM + 1];
-#pragma unroll
-    for (int d = 0; d <= CHL_MAX_DIM; ++d) acc[d] = 0.0;
-    if ((int)blockIdx.x < B) {
-        const int b = blockIdx.x;
-        for (int m0 = threadIdx.x; m0 < M; m0 += 256) {
-            const int o = b * M + m0;
-            const float mk = mask[o] != 0 ? 1.0f : 0.0f;
-            const long long pix = ind[o];
-            const int y = (int)(pix / W), x = (int)(pix % W);
-            acc[CHL_MAX_DIM] += (double)mk;
-            int d0 = 0;
-            for (int r = 0; r < regs.n; ++r) {
-                const ChlMap &m = regs.m[r];
-                for (int c = 0; c < m.c; ++c) {
-                    const float pr = chl_load(m, b * m.sb + c * m.sc + y * m.sh + x * m.sw);
-                    const float v = fabsf(pr * mk - target[(size_t)o * regs.dims + d0 + c] * mk);
-#pragma unroll
-                    for (int d = 0; d < CHL_MAX_DIM; ++d)      // (static register index)
-                        if (d == d0 + c) acc[d] += (double)v;
-                }
-                d0 += m.c;
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < CHL_MAX_DIM; ++d) {
-        const double t = chl_block_sum(acc[d], lds);
-        if (threadIdx.x == 0 && d < regs.dims) row[4 + d] = t;
-    }
-    const double nobj = chl_block_sum(acc[CHL_MAX_DIM], lds);
-    if (threadIdx.x == 0) row[4 + regs.dims] = nobj;
+    chl_reg_partials(regs, B, W, ind, mask, target, M, row + 4, lds);
 }
 
 // out[0] = loss, [1] = hm_loss, [2] = loc_loss, [3] = confidence, [4] = num_pos, [5] = num_obj, [6 .. 6 + dims) = L1 per dim
@@ -219,93 +153,18 @@ __global__ __launch_bounds__(256) void chl_backward_kernel(ChlMap hm, const floa
                                                            const float *__restrict__ grad_out, float cls_weight) {
     const long long total = (long long)B * C * H * W;
     const float scale = -cls_weight / fmaxf(out[4], 1.0f) * grad_out[0];
-    const long long hw = (long long)H * W;
     for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < (unsigned)total; e += gridDim.x * 256u) {
-        const int x = (int)(e % (unsigned)W);
-        unsigned t = e / (unsigned)W;
-        const int y = (int)(t % (unsigned)H);
-        t /= (unsigned)H;
-        const int c = (int)(t % (unsigned)C), b = (int)(t / (unsigned)C);
         const float g = gt[e];
-        const long long off = b * hm.sb + c * hm.sc + y * hm.sh + x * hm.sw;
-        const float s = chl_sigmoid(chl_load(hm, off));
+        const long long off = chl_at_linear(hm, e, C, H, W);
+        const float s = sigmoid_f32(chl_load(hm, off));
         const bool inside = s >= 1e-4f && s <= 1.0f - 1e-4f;
-        const float p = fminf(fmaxf(s, 1e-4f), 1.0f - 1e-4f);
+        const float p = focal_clamp(s);
         float dp = 0.0f;
-        if (g == 1.0f) {
-            const float q = 1.0f - p;
-            dp = q * q / p - 2.0f * q * logf(p);
-        } else if (g < 1.0f) {
-            const float w1 = 1.0f - g, w2 = w1 * w1;
-            dp = (-(p * p) / (1.0f - p) + 2.0f * p * logf(1.0f - p)) * (w2 * w2);
-        }
+        if (g == 1.0f) dp = focal_pos_grad(p);
+        else if (g < 1.0f) dp = focal_neg_grad(p, g);
         chl_store_grad(hm, off, inside ? scale * dp * (s * (1.0f - s)) : 0.0f);
     }
-    for (int r = 0; r < regs.n; ++r) {
-        const ChlMap &m = regs.m[r];
-        const long long n = (long long)B * m.c * hw;
-        for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < (unsigned)n; e += gridDim.x * 256u) {
-            const int x = (int)(e % (unsigned)W);
-            unsigned t = e / (unsigned)W;
-            const int y = (int)(t % (unsigned)H);
-            t /= (unsigned)H;
-            const int c = (int)(t % (unsigned)m.c), b = (int)(t / (unsigned)m.c);
-            chl_store_grad(m, b * m.sb + c * m.sc + y * m.sh + x * m.sw, 0.0f);
-        }
-    }
-}
-
-// A block per frame.  The masked objects are first compacted into LDS in object order (typically < 100 of the 500
-// slots); then one thread per object: the FIRST object of a pixel adds up the gradients of all objects of that pixel (in
-// object order) and stores them.
-__global__ __launch_bounds__(256) void chl_scatter_kernel(ChlRegs regs, int W, const long long *__restrict__ ind,
-                                                          const long long *__restrict__ mask,
-                                                          const float *__restrict__ target, int M,
-                                                          const float *__restrict__ code_weights,
-                                                          const float *__restrict__ out,
-                                                          const float *__restrict__ grad_out, float loc_weight) {
-    __shared__ int pix_s[CHL_MAX_OBJS];
-    __shared__ int obj_s[CHL_MAX_OBJS];
-    __shared__ int lds[4];
-    const int b = blockIdx.x;
-    int K = 0;
-    for (int base = 0; base < M; base += 256) {
-        const int m0 = base + threadIdx.x;
-        const bool on = m0 < M && mask[b * M + m0] != 0;
-        int total;
-        const int pos = K + block_exclusive_scan(on ? 1 : 0, lds, total);
-        if (on && pos < CHL_MAX_OBJS) {
-            pix_s[pos] = (int)ind[b * M + m0];
-            obj_s[pos] = b * M + m0;
-        }
-        K += total;
-    }
-    __syncthreads();
-    K = K < CHL_MAX_OBJS ? K : CHL_MAX_OBJS;
-    const float scale = loc_weight / fmaxf(out[5], 1.0f) * grad_out[0];
-    for (int k = threadIdx.x; k < K; k += 256) {
-        const int pix = pix_s[k];
-        bool first = true;
-        for (int j = 0; j < k; ++j) first = first && pix_s[j] != pix;
-        if (!first) continue;
-        const int y = pix / W, x = pix - y * W;
-        int d0 = 0;
-        for (int r = 0; r < regs.n; ++r) {
-            const ChlMap &mp = regs.m[r];
-            for (int c = 0; c < mp.c; ++c) {
-                const long long off = b * mp.sb + c * mp.sc + y * mp.sh + x * mp.sw;
-                const float pr = chl_load(mp, off);
-                float gsum = 0.0f;
-                for (int j = k; j < K; ++j) {
-                    if (pix_s[j] != pix) continue;
-                    const float diff = pr - target[(size_t)obj_s[j] * regs.dims + d0 + c];
-                    gsum += diff > 0.0f ? 1.0f : (diff < 0.0f ? -1.0f : 0.0f);
-                }
-                chl_store_grad(mp, off, scale * code_weights[d0 + c] * gsum);
-            }
-            d0 += mp.c;
-        }
-    }
+    chl_zero_reg_grads(regs, B, H, W);
 }
 
 }  // namespace
@@ -323,18 +182,16 @@ extern "C" int pcd_centerhead_loss_forward(const void *hm, int hm_dtype, const l
                                            const float *code_weights, float cls_weight, float loc_weight, float *out,
                                            void *workspace, size_t workspace_bytes, void *stream) {
     PCD_ENTER();
-    if (batch <= 0 || num_classes <= 0 || height <= 0 || width <= 0 || num_max_objs < 0 || !gt_heatmap || !out ||
-        !workspace || (num_max_objs > 0 && n_reg > 0 && (!inds || !masks || !target_boxes || !code_weights)))
+    if (num_max_objs < 0 || !workspace || (num_max_objs > 0 && n_reg > 0 && (!inds || !masks || !target_boxes || !code_weights)))
         return PCD_ERR_INVALID_ARG;
     ChlMap H_;
     ChlRegs R;
-    int rc = chl_pack(hm, nullptr, hm_dtype, hm_strides_host, num_classes, reg_ptrs_host, nullptr, reg_channels_host,
-                      reg_dtype, reg_strides_host, n_reg, &H_, &R);
+    int rc = chl_pack(batch, num_classes, height, width, gt_heatmap, out, hm, nullptr, hm_dtype, hm_strides_host,
+                      reg_ptrs_host, nullptr, reg_channels_host, reg_dtype, reg_strides_host, n_reg, &H_, &R);
     if (rc != PCD_OK) return rc;
     if (workspace_bytes < pcd_centerhead_loss_workspace_bytes(R.dims)) return PCD_ERR_WORKSPACE;
-    if ((double)batch * (num_classes > CHL_MAX_DIM ? num_classes : CHL_MAX_DIM) * height * width >= 4294967295.0)
-        return PCD_ERR_UNSUPPORTED;
-    if (num_max_objs > CHL_MAX_OBJS) return PCD_ERR_UNSUPPORTED;   // (the backward pass could not follow)
+    rc = chl_check_limits(batch, num_classes, height, width, num_max_objs, 4294967295.0);   // (M: the backward pass could not follow)
+    if (rc != PCD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int pstride = 4 + CHL_MAX_DIM + 2;
     chl_forward_kernel<<<CHL_BLOCKS, 256, 0, st>>>(H_, gt_heatmap, batch, num_classes, height, width, R, inds, masks,
@@ -354,27 +211,23 @@ extern "C" int pcd_centerhead_loss_backward(const void *hm, void *d_hm, int hm_d
                                             const float *code_weights, float cls_weight, float loc_weight,
                                             const float *out, const float *grad_out, void *stream) {
     PCD_ENTER();
-    if (batch <= 0 || num_classes <= 0 || height <= 0 || width <= 0 || num_max_objs < 0 || !gt_heatmap || !out ||
-        !grad_out || !d_hm || (n_reg > 0 && !reg_grads_host) ||
+    if (num_max_objs < 0 || !grad_out || !d_hm ||
         (num_max_objs > 0 && n_reg > 0 && (!inds || !masks || !target_boxes || !code_weights)))
         return PCD_ERR_INVALID_ARG;
     ChlMap H_;
     ChlRegs R;
-    int rc = chl_pack(hm, d_hm, hm_dtype, hm_strides_host, num_classes, reg_ptrs_host, reg_grads_host,
-                      reg_channels_host, reg_dtype, reg_strides_host, n_reg, &H_, &R);
+    int rc = chl_pack(batch, num_classes, height, width, gt_heatmap, out, hm, d_hm, hm_dtype, hm_strides_host,
+                      reg_ptrs_host, reg_grads_host, reg_channels_host, reg_dtype, reg_strides_host, n_reg, &H_, &R);
     if (rc != PCD_OK) return rc;
-    for (int r = 0; r < n_reg; ++r)
-        if (!reg_grads_host[r]) return PCD_ERR_INVALID_ARG;
-    if ((double)batch * (num_classes > CHL_MAX_DIM ? num_classes : CHL_MAX_DIM) * height * width >= 4294967295.0 ||
-        (double)height * width >= 2147483647.0)
-        return PCD_ERR_UNSUPPORTED;
-    if (num_max_objs > CHL_MAX_OBJS) return PCD_ERR_UNSUPPORTED;   // chl_scatter_kernel compacts a frame's objects in LDS
+    rc = chl_check_limits(batch, num_classes, height, width, num_max_objs, 4294967295.0);
+    if (rc != PCD_OK) return rc;
+    if ((double)height * width >= 2147483647.0) return PCD_ERR_UNSUPPORTED;   // (chl_scatter_kernel keeps pixels as int)
     hipStream_t st = (hipStream_t)stream;
     chl_backward_kernel<<<1024, 256, 0, st>>>(H_, gt_heatmap, batch, num_classes, height, width, R, out, grad_out,
                                               cls_weight);
     if (n_reg > 0 && num_max_objs > 0)
-        chl_scatter_kernel<<<batch, 256, 0, st>>>(R, width, inds, masks, target_boxes, num_max_objs, code_weights, out,
-                                                  grad_out, loc_weight);
+        chl_scatter_kernel<long long><<<batch, 256, 0, st>>>(R, width, inds, masks, target_boxes, num_max_objs,
+                                                             code_weights, out, grad_out, loc_weight);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }

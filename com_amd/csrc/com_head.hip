@@ -91,46 +91,26 @@ __global__ __launch_bounds__(64) void com_assign_rows_kernel(const float *__rest
     int count = 0;
     for (int base = 0; base < n && count < G.num_max; base += 64) {
         const int r = base + lane;
-        int local = 0;
-        if (r < n) {
-            const int cls = (int)rows[(size_t)r * G.code + G.code - 1];
-            local = (cls >= 0 && cls < 16) ? G.cls_map[cls] : 0;
-        }
+        const int local = assign_class(rows, r, n, G);
         int total;
         const int k = count + wave_rank(local > 0, total);
         count += total;
         if (local <= 0 || k >= G.num_max) continue;
         const float *q = rows + (size_t)r * G.code;
-        float cx = (q[0] - G.range_x) / G.vs_x / (float)G.stride;
-        float cy = (q[1] - G.range_y) / G.vs_y / (float)G.stride;
-        cx = fminf(fmaxf(cx, 0.0f), (float)G.W - 0.5f);
-        cy = fminf(fmaxf(cy, 0.0f), (float)G.H - 0.5f);
-        const int ix = (int)cx, iy = (int)cy;
-        const float dx = q[3] / G.vs_x / (float)G.stride, dy = q[4] / G.vs_y / (float)G.stride;
-        if (!(dx > 0.0f && dy > 0.0f && ix >= 0 && ix <= G.W && iy >= 0 && iy <= G.H)) continue;   // :168-172
+        const AssignRow a = assign_row(q, G);
+        if (!a.valid) continue;                                                                      // :168-172
         if (gate && npgt[(size_t)b * n + r] < min_points) continue;                                  // :178-179
-        int radius = (int)gaussian_radius_f32(dx, dy, G.overlap);
-        radius = radius < G.min_radius ? G.min_radius : radius;
         const size_t at = (size_t)b * G.num_max + k;
-        inds[at] = (long long)iy * G.W + ix;
+        inds[at] = (long long)a.iy * G.W + a.ix;
         mask[at] = 1.0f;
-        float *o = ret_boxes + at * G.code;
-        o[0] = cx - (float)ix;
-        o[1] = cy - (float)iy;
-        o[2] = q[2];
-        o[3] = logf(q[3]);
-        o[4] = logf(q[4]);
-        o[5] = logf(q[5]);
-        o[6] = cosf(q[6]);
-        o[7] = sinf(q[6]);
-        for (int j = 8; j < G.code; ++j) o[j] = q[j - 1];
+        encode_box(q, a, G.code, ret_boxes + at * G.code);
         long long *rm = radius_map + at * rmap_cols;
         rm[0] = local - 1;
-        rm[1] = ix;
-        rm[2] = iy;
-        rm[3] = radius;
+        rm[1] = a.ix;
+        rm[2] = a.iy;
+        rm[3] = a.radius;
         if (rmap_cols > 4) rm[4] = group ? group[(size_t)b * n + r] : 0;
-        draw[at] = make_int4(local - 1, ix, iy, radius);
+        draw[at] = make_int4(local - 1, a.ix, a.iy, a.radius);
     }
 }
 
@@ -146,8 +126,7 @@ constexpr int COM_BLOCKS = 256;
 constexpr int COM_PSTRIDE = 8 + CHL_MAX_DIM + 2;    // doubles per partial row
 
 __device__ __forceinline__ float com_pred(const ChlMap &hm, int b, int c, int y, int x) {
-    const float s = chl_sigmoid(chl_load(hm, b * hm.sb + c * hm.sc + y * hm.sh + x * hm.sw));
-    return fminf(fmaxf(s, 1e-4f), 1.0f - 1e-4f);
+    return chl_pred(hm, chl_at(hm, b, c, y, x));
 }
 
 // (UCL with the EMA threshold only) sum of pred at the positives / number of positives -> partial[blk][6..7]
@@ -158,11 +137,7 @@ __global__ __launch_bounds__(256) void com_conf_partials_kernel(ChlMap hm, const
     double conf = 0.0, nobj = 0.0;
     for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < total; e += COM_BLOCKS * 256u) {
         if (gt[e] != 1.0f) continue;
-        const int x = (int)(e % (unsigned)W);
-        unsigned t = e / (unsigned)W;
-        const int y = (int)(t % (unsigned)H);
-        t /= (unsigned)H;
-        conf += (double)com_pred(hm, (int)(t / (unsigned)C), (int)(t % (unsigned)C), y, x);
+        conf += (double)chl_pred(hm, chl_at_linear(hm, e, C, H, W));
         nobj += 1.0;
     }
     const double s0 = chl_block_sum(conf, lds), s1 = chl_block_sum(nobj, lds);
@@ -288,13 +263,11 @@ __global__ __launch_bounds__(256) void com_forward_kernel(ChlMap hm, const float
             const float g = gt[(size_t)b * chw + e];
             const float p = com_pred(hm, b, c, y, x);
             if (g == 1.0f) {
-                const float q = 1.0f - p;
-                p_col += (double)(logf(p) * (q * q));
+                p_col += (double)focal_pos(p);
                 i_col += 1.0;
                 conf += (double)p;
             } else if (g < 1.0f) {
-                const float w1 = 1.0f - g, w2 = w1 * w1;
-                n_col += (double)(logf(1.0f - p) * (p * p) * (w2 * w2));
+                n_col += (double)focal_neg(p, g);
             }
         }
         pos += p_col * mk;
@@ -309,38 +282,7 @@ __global__ __launch_bounds__(256) void com_forward_kernel(ChlMap hm, const float
         row[0] = s0; row[1] = s1; row[2] = s2; row[3] = s3; row[4] = s4;
     }
     // regression with the FLOAT box mask (loss_utils.py:1317-1345): |pred * m - target * m| per code dimension
-    double acc[CHL_MAX_DIM + 1];
-#pragma unroll
-    for (int d = 0; d <= CHL_MAX_DIM; ++d) acc[d] = 0.0;
-    if ((int)blockIdx.x < B) {
-        const int b = blockIdx.x;
-        for (int m0 = threadIdx.x; m0 < M; m0 += 256) {
-            const int o = b * M + m0;
-            const float mk = box_mask[o];
-            const long long pix = ind[o];
-            const int y = (int)(pix / W), x = (int)(pix % W);
-            acc[CHL_MAX_DIM] += (double)mk;
-            int d0 = 0;
-            for (int r = 0; r < regs.n; ++r) {
-                const ChlMap &m = regs.m[r];
-                for (int c = 0; c < m.c; ++c) {
-                    const float pr = chl_load(m, b * m.sb + c * m.sc + y * m.sh + x * m.sw);
-                    const float v = fabsf(pr * mk - target[(size_t)o * regs.dims + d0 + c] * mk);
-#pragma unroll
-                    for (int d = 0; d < CHL_MAX_DIM; ++d)
-                        if (d == d0 + c) acc[d] += (double)v;
-                }
-                d0 += m.c;
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < CHL_MAX_DIM; ++d) {
-        const double t = chl_block_sum(acc[d], lds);
-        if (threadIdx.x == 0 && d < regs.dims) row[8 + d] = t;
-    }
-    const double nbox = chl_block_sum(acc[CHL_MAX_DIM], lds);
-    if (threadIdx.x == 0) row[8 + regs.dims] = nbox;
+    chl_reg_partials(regs, B, W, ind, box_mask, target, M, row + 8, lds);
 }
 
 // out[0] = loss, [1] = hm_loss, [2] = loc_loss, [3] = avg_confidence, [4] = num_pos (mask-weighted; 0 selects the
@@ -442,7 +384,7 @@ __global__ __launch_bounds__(256) void com_finalize_kernel(const double *__restr
     }
 }
 
-// d loss / d hm logits; regression gradients zeroed here and filled by com_scatter_kernel
+// d loss / d hm logits; regression gradients zeroed here and filled by chl_scatter_kernel<float>
 __global__ __launch_bounds__(256) void com_backward_kernel(ChlMap hm, const float *__restrict__ gt,
                                                            const float *__restrict__ msum, int B, int C, int H, int W,
                                                            ChlRegs regs, const float *__restrict__ out,
@@ -452,7 +394,6 @@ __global__ __launch_bounds__(256) void com_backward_kernel(ChlMap hm, const floa
     const float npos = out[4];
     const bool has_pos = npos != 0.0f;
     const float scale = -cls_weight / (has_pos ? npos : 1.0f) * grad_out[0];
-    const long long hw = (long long)H * W;
     for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < total; e += gridDim.x * 256u) {
         const unsigned col = e % chw;
         const int x = (int)(col % (unsigned)W);
@@ -460,85 +401,17 @@ __global__ __launch_bounds__(256) void com_backward_kernel(ChlMap hm, const floa
         const int y = (int)(t % (unsigned)H);
         const int c = (int)(t / (unsigned)H), b = (int)(e / chw);
         const float g = gt[e];
-        const long long off = b * hm.sb + c * hm.sc + y * hm.sh + x * hm.sw;
-        const float s = chl_sigmoid(chl_load(hm, off));
+        const long long off = chl_at(hm, b, c, y, x);
+        const float s = sigmoid_f32(chl_load(hm, off));
         const bool inside = s >= 1e-4f && s <= 1.0f - 1e-4f;
-        const float p = fminf(fmaxf(s, 1e-4f), 1.0f - 1e-4f);
+        const float p = focal_clamp(s);
         const float mk = msum ? msum[col] : (float)B;
         float dp = 0.0f;
-        if (g == 1.0f) {
-            const float q = 1.0f - p;
-            dp = has_pos ? q * q / p - 2.0f * q * logf(p) : 0.0f;   // (num_pos == 0 branch: loss = -neg_loss only)
-        } else if (g < 1.0f) {
-            const float w1 = 1.0f - g, w2 = w1 * w1;
-            dp = (-(p * p) / (1.0f - p) + 2.0f * p * logf(1.0f - p)) * (w2 * w2);
-        }
+        if (g == 1.0f) dp = has_pos ? focal_pos_grad(p) : 0.0f;     // (num_pos == 0 branch: loss = -neg_loss only)
+        else if (g < 1.0f) dp = focal_neg_grad(p, g);
         chl_store_grad(hm, off, inside ? scale * dp * mk * (s * (1.0f - s)) : 0.0f);
     }
-    for (int r = 0; r < regs.n; ++r) {
-        const ChlMap &m = regs.m[r];
-        const long long n = (long long)B * m.c * hw;
-        for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < (unsigned)n; e += gridDim.x * 256u) {
-            const int x = (int)(e % (unsigned)W);
-            unsigned t = e / (unsigned)W;
-            const int y = (int)(t % (unsigned)H);
-            t /= (unsigned)H;
-            const int c = (int)(t % (unsigned)m.c), b = (int)(t / (unsigned)m.c);
-            chl_store_grad(m, b * m.sb + c * m.sc + y * m.sh + x * m.sw, 0.0f);
-        }
-    }
-}
-
-// like chl_scatter_kernel with float weights: d |pr m - t m| / d pr = sign(pr m - t m) m
-__global__ __launch_bounds__(256) void com_scatter_kernel(ChlRegs regs, int W, const long long *__restrict__ ind,
-                                                          const float *__restrict__ box_mask,
-                                                          const float *__restrict__ target, int M,
-                                                          const float *__restrict__ code_weights,
-                                                          const float *__restrict__ out,
-                                                          const float *__restrict__ grad_out, float loc_weight) {
-    __shared__ int pix_s[CHL_MAX_OBJS];
-    __shared__ int obj_s[CHL_MAX_OBJS];
-    __shared__ int lds[4];
-    const int b = blockIdx.x;
-    int K = 0;
-    for (int base = 0; base < M; base += 256) {
-        const int m0 = base + threadIdx.x;
-        const bool on = m0 < M && box_mask[b * M + m0] != 0.0f;
-        int total;
-        const int pos = K + block_exclusive_scan(on ? 1 : 0, lds, total);
-        if (on && pos < CHL_MAX_OBJS) {
-            pix_s[pos] = (int)ind[b * M + m0];
-            obj_s[pos] = b * M + m0;
-        }
-        K += total;
-    }
-    __syncthreads();
-    K = K < CHL_MAX_OBJS ? K : CHL_MAX_OBJS;
-    const float scale = loc_weight / fmaxf(out[5], 1.0f) * grad_out[0];
-    for (int k = threadIdx.x; k < K; k += 256) {
-        const int pix = pix_s[k];
-        bool first = true;
-        for (int j = 0; j < k; ++j) first = first && pix_s[j] != pix;
-        if (!first) continue;
-        const int y = pix / W, x = pix - y * W;
-        int d0 = 0;
-        for (int r = 0; r < regs.n; ++r) {
-            const ChlMap &mp = regs.m[r];
-            for (int c = 0; c < mp.c; ++c) {
-                const long long off = b * mp.sb + c * mp.sc + y * mp.sh + x * mp.sw;
-                const float pr = chl_load(mp, off);
-                float gsum = 0.0f;
-                for (int j = k; j < K; ++j) {
-                    if (pix_s[j] != pix) continue;
-                    const float mk = box_mask[obj_s[j]];
-                    const float diff = pr * mk - target[(size_t)obj_s[j] * regs.dims + d0 + c] * mk;
-                    gsum += diff > 0.0f ? mk : (diff < 0.0f ? -mk : 0.0f);
-                }
-                chl_store_grad(mp, off, scale * code_weights[d0 + c] * gsum);
-            }
-            d0 += mp.c;
-        }
-    }
+    chl_zero_reg_grads(regs, B, H, W);
 }
 
 static ComCur com_cur(const PcdComCurriculum *c, int has_rmap5) {
@@ -589,12 +462,8 @@ extern "C" int pcd_com_assign_targets(const float *gt_boxes, int batch, int n_bo
     if (!heatmap || !ret_boxes || !inds || !mask || !radius_map || !heatmap_mask) return PCD_ERR_INVALID_ARG;
     if (n_boxes > 0 && (!gt_boxes || (gate_min_points && !num_points_in_gt))) return PCD_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < pcd_com_assign_workspace_bytes(batch, num_max_objs)) return PCD_ERR_WORKSPACE;
-    AssignGeom G = {};
-    G.range_x = range_xy_host[0]; G.range_y = range_xy_host[1];
-    G.vs_x = voxel_size_xy_host[0]; G.vs_y = voxel_size_xy_host[1];
-    G.stride = feature_map_stride; G.W = fm_w; G.H = fm_h; G.num_max = num_max_objs; G.min_radius = min_radius;
-    G.code = code_size; G.head_classes = head_classes; G.overlap = gaussian_overlap;
-    for (int i = 0; i < n_class_map; ++i) G.cls_map[i] = class_map_host[i];
+    const AssignGeom G = assign_geom(range_xy_host, voxel_size_xy_host, feature_map_stride, fm_w, fm_h, num_max_objs,
+                                     min_radius, code_size, head_classes, gaussian_overlap, class_map_host, n_class_map);
     hipStream_t st = (hipStream_t)stream;
     int4 *draw = (int4 *)workspace;
     ComInit I = {heatmap, heatmap_mask, ret_boxes, mask, inds, radius_map, draw,
@@ -626,19 +495,17 @@ extern "C" int pcd_com_loss_forward(const void *hm, int hm_dtype, const long lon
                                     float *num_all, float *conf_epoch, float *num_epoch, void *workspace,
                                     size_t workspace_bytes, void *stream) {
     PCD_ENTER();
-    if (batch <= 0 || num_classes <= 0 || height <= 0 || width <= 0 || num_max_objs <= 0 || !gt_heatmap || !out ||
-        !workspace || !cur_host || !state || !inds || !box_mask || !target_boxes || !radius_map || !code_weights ||
-        (radius_map_cols != 4 && radius_map_cols != 5))
+    if (num_max_objs <= 0 || !workspace || !cur_host || !state || !inds || !box_mask || !target_boxes || !radius_map ||
+        !code_weights || (radius_map_cols != 4 && radius_map_cols != 5))
         return PCD_ERR_INVALID_ARG;
     ChlMap H_;
     ChlRegs R;
-    int rc = chl_pack(hm, nullptr, hm_dtype, hm_strides_host, num_classes, reg_ptrs_host, nullptr, reg_channels_host,
-                      reg_dtype, reg_strides_host, n_reg, &H_, &R);
+    int rc = chl_pack(batch, num_classes, height, width, gt_heatmap, out, hm, nullptr, hm_dtype, hm_strides_host,
+                      reg_ptrs_host, nullptr, reg_channels_host, reg_dtype, reg_strides_host, n_reg, &H_, &R);
     if (rc != PCD_OK) return rc;
     if (workspace_bytes < pcd_com_loss_workspace_bytes(batch, num_max_objs)) return PCD_ERR_WORKSPACE;
-    if ((double)batch * (num_classes > CHL_MAX_DIM ? num_classes : CHL_MAX_DIM) * height * width >= 2147483647.0)
-        return PCD_ERR_UNSUPPORTED;
-    if (num_max_objs > CHL_MAX_OBJS) return PCD_ERR_UNSUPPORTED;
+    rc = chl_check_limits(batch, num_classes, height, width, num_max_objs, 2147483647.0);
+    if (rc != PCD_OK) return rc;
     if (batch > COM_BLOCKS) return PCD_ERR_UNSUPPORTED;   // (the regression sums take one workgroup per frame of a fixed grid)
     ComCur cur = com_cur(cur_host, radius_map_cols == 5);
     if (cur.conf_c * cur.conf_g > 512) return PCD_ERR_UNSUPPORTED;
@@ -679,25 +546,21 @@ extern "C" int pcd_com_loss_backward(const void *hm, void *d_hm, int hm_dtype, c
                                      int num_max_objs, const float *mask_sum, const float *code_weights, float cls_weight,
                                      float loc_weight, const float *out, const float *grad_out, void *stream) {
     PCD_ENTER();
-    if (batch <= 0 || num_classes <= 0 || height <= 0 || width <= 0 || num_max_objs <= 0 || !gt_heatmap || !out ||
-        !grad_out || !d_hm || (n_reg > 0 && !reg_grads_host) || !inds || !box_mask || !target_boxes || !code_weights)
+    if (num_max_objs <= 0 || !grad_out || !d_hm || !inds || !box_mask || !target_boxes || !code_weights)
         return PCD_ERR_INVALID_ARG;
     ChlMap H_;
     ChlRegs R;
-    int rc = chl_pack(hm, d_hm, hm_dtype, hm_strides_host, num_classes, reg_ptrs_host, reg_grads_host,
-                      reg_channels_host, reg_dtype, reg_strides_host, n_reg, &H_, &R);
+    int rc = chl_pack(batch, num_classes, height, width, gt_heatmap, out, hm, d_hm, hm_dtype, hm_strides_host,
+                      reg_ptrs_host, reg_grads_host, reg_channels_host, reg_dtype, reg_strides_host, n_reg, &H_, &R);
     if (rc != PCD_OK) return rc;
-    for (int r = 0; r < n_reg; ++r)
-        if (!reg_grads_host[r]) return PCD_ERR_INVALID_ARG;
-    if ((double)batch * (num_classes > CHL_MAX_DIM ? num_classes : CHL_MAX_DIM) * height * width >= 2147483647.0)
-        return PCD_ERR_UNSUPPORTED;
-    if (num_max_objs > CHL_MAX_OBJS) return PCD_ERR_UNSUPPORTED;
+    rc = chl_check_limits(batch, num_classes, height, width, num_max_objs, 2147483647.0);
+    if (rc != PCD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     com_backward_kernel<<<1024, 256, 0, st>>>(H_, gt_heatmap, mask_sum, batch, num_classes, height, width, R, out,
                                               grad_out, cls_weight);
     if (n_reg > 0)
-        com_scatter_kernel<<<batch, 256, 0, st>>>(R, width, inds, box_mask, target_boxes, num_max_objs, code_weights, out,
-                                                  grad_out, loc_weight);
+        chl_scatter_kernel<float><<<batch, 256, 0, st>>>(R, width, inds, box_mask, target_boxes, num_max_objs,
+                                                         code_weights, out, grad_out, loc_weight);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }

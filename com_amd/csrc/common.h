@@ -71,6 +71,15 @@ __device__ __forceinline__ unsigned short f32_to_bf16_bits(float f) {
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) {
     return __uint_as_float(((u32)b) << 16);
 }
+// element `off` of a PCD_F32 / PCD_BF16 array as float, and back
+__device__ __forceinline__ float load_el(const void *p, int dtype, long long off) {
+    return dtype == PCD_BF16 ? bf16_bits_to_f32(((const unsigned short *)p)[off]) : ((const float *)p)[off];
+}
+__device__ __forceinline__ void store_el(void *p, int dtype, long long off, float v) {
+    if (dtype == PCD_BF16) ((unsigned short *)p)[off] = f32_to_bf16_bits(v);
+    else ((float *)p)[off] = v;
+}
+__device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }   // torch's sigmoid (fp32)
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 

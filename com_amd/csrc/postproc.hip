@@ -62,11 +62,8 @@ struct PpSel {
 
 __device__ __forceinline__ float ld_map(const PpMap &m, int b, int c, int y, int x) {
     const long long off = (long long)b * m.s[0] + (long long)c * m.s[1] + (long long)y * m.s[2] + (long long)x * m.s[3];
-    if (m.bf16) return bf16_bits_to_f32(((const unsigned short *)m.p)[off]);
-    return ((const float *)m.p)[off];
+    return load_el(m.p, m.bf16 ? PCD_BF16 : PCD_F32, off);
 }
-
-__device__ __forceinline__ float sigmoid_f32(float v) { return 1.0f / (1.0f + expf(-v)); }   // torch's sigmoid (fp32)
 
 // one atomic per distinct bin of the wave (all-equal scores -- fresh weights -- would otherwise serialise on one address)
 __device__ __forceinline__ void wave_hist_add(u32 *hist, bool active, u32 bin) {

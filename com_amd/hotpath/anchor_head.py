@@ -17,6 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib as L
+from ._maps import dtype_code as _dt, like as _like
 from .dense2d import _get
 
 KIND_FLOATS = 10      # include/pcd_ops.h: PCD_ANCHOR_KIND_FLOATS
@@ -152,12 +153,6 @@ def _strides3(tensors):
     return (ctypes.c_longlong * 12)(*vals)
 
 
-def _dt(t):
-    if t.dtype not in (torch.float32, torch.bfloat16):
-        raise L.PcdError(f"anchor head: prediction maps must be float32 or bfloat16, got {t.dtype}")
-    return L.PCD_F32 if t.dtype == torch.float32 else L.PCD_BF16
-
-
 class AnchorTables:
     """The three device tables + the static settings the kernels take."""
 
@@ -235,7 +230,7 @@ class _AnchorLoss(torch.autograd.Function):
     def backward(ctx, g_loss, _g_out):
         preds, labels, targets, num_pos, code_weights = ctx.saved_tensors
         tab, has_dir, weights = ctx.meta
-        d_preds = torch.empty_strided(preds.shape, preds.stride(), dtype=preds.dtype, device=preds.device)
+        d_preds = _like(preds)
         cls, box, dr = _split(preds, tab, has_dir)
         d_cls, d_box, d_dr = _split(d_preds, tab, has_dir)
         g = g_loss.detach().to(torch.float32).reshape(1).contiguous()

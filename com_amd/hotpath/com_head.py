@@ -15,14 +15,7 @@ import ctypes
 import torch
 
 from .. import _lib as L
-
-
-
-
-def _like(t):
-    """an uninitialised tensor with EXACTLY t's strides (torch.empty_like densifies a non-dense view, e.g. the 1-3 real
-    channels of a prediction map that was computed with zero-padded channels)."""
-    return torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device)
+from . import _maps
 
 
 def _dev(t, what):
@@ -71,10 +64,7 @@ def assign_targets(gt_boxes, feature_map_size, class_names, class_names_each_hea
            'heatmap_mask': []}
     gate = int(epoch <= epoch_threshold)
     for head_names in class_names_each_head:
-        cmap = [0] * (len(class_names) + 1)
-        for i, name in enumerate(class_names):
-            if name in head_names:
-                cmap[i + 1] = list(head_names).index(name) + 1
+        cmap = _maps.head_class_map(class_names, head_names)
         nc = len(head_names)
         dev = gt.device
         heatmap = torch.empty((B, nc, H, W), dtype=torch.float32, device=dev)
@@ -128,7 +118,7 @@ class _ComHeadLoss(torch.autograd.Function):
         B, C, H, W = hm.shape
         n = int(inds.shape[1])
         dims = sum(int(r.shape[1]) for r in regs)
-        assert dims == target_boxes.shape[2] and all(r.dtype == regs[0].dtype for r in regs)
+        assert dims == target_boxes.shape[2]
         lib = L.lib()
         code_weights = code_weights[:dims].to(device=hm.device, dtype=torch.float32).contiguous()
         out = torch.empty((6 + dims,), dtype=torch.float32, device=hm.device)
@@ -138,20 +128,14 @@ class _ComHeadLoss(torch.autograd.Function):
             assert heatmap_mask is not None and heatmap_mask.is_contiguous() and heatmap_mask.shape == hm.shape
             assert owner is not None and owner.dtype == torch.int32 and owner.numel() >= hm.numel()
             msum = torch.empty((C, H, W), dtype=torch.float32, device=hm.device)
-
-        def dt(t):
-            assert t.dtype in (torch.float32, torch.bfloat16), t.dtype
-            return L.PCD_F32 if t.dtype == torch.float32 else L.PCD_BF16
+        m = _maps.pack_maps(hm, regs)
         L.check(lib.pcd_com_loss_forward(
-            L.ptr(hm), dt(hm), (ctypes.c_longlong * 4)(*hm.stride()), L.ptr(heatmap), B, C, H, W,
-            (ctypes.c_void_p * len(regs))(*[r.data_ptr() for r in regs]),
-            (ctypes.c_int * len(regs))(*[int(r.shape[1]) for r in regs]), dt(regs[0]) if regs else L.PCD_F32,
-            (ctypes.c_longlong * (4 * len(regs)))(*[v for r in regs for v in r.stride()]), len(regs), L.ptr(inds),
-            L.ptr(box_mask), L.ptr(target_boxes), L.ptr(radius_map), int(radius_map.shape[2]), n,
-            L.ptr(heatmap_mask) if cur.ucl else None, L.ptr(owner) if cur.ucl else None, L.ptr(msum),
-            ctypes.cast(ctypes.pointer(cur), ctypes.c_void_p), L.ptr(code_weights), float(cls_weight), float(loc_weight),
-            L.ptr(state), L.ptr(out), L.ptr(conf_all), L.ptr(num_all), L.ptr(conf_epoch), L.ptr(num_epoch), L.ptr(ws),
-            ws.numel(), L.stream_ptr()), "pcd_com_loss_forward")
+            L.ptr(hm), m.hm_dtype, m.hm_strides, L.ptr(heatmap), B, C, H, W, m.reg_ptrs, m.reg_ch, m.reg_dtype,
+            m.reg_strides, m.n, L.ptr(inds), L.ptr(box_mask), L.ptr(target_boxes), L.ptr(radius_map),
+            int(radius_map.shape[2]), n, L.ptr(heatmap_mask) if cur.ucl else None, L.ptr(owner) if cur.ucl else None,
+            L.ptr(msum), ctypes.cast(ctypes.pointer(cur), ctypes.c_void_p), L.ptr(code_weights), float(cls_weight),
+            float(loc_weight), L.ptr(state), L.ptr(out), L.ptr(conf_all), L.ptr(num_all), L.ptr(conf_epoch),
+            L.ptr(num_epoch), L.ptr(ws), ws.numel(), L.stream_ptr()), "pcd_com_loss_forward")
         ctx.save_for_backward(hm, heatmap, inds, box_mask, target_boxes, code_weights, out, *regs)
         ctx.msum = msum
         ctx.weights = (float(cls_weight), float(loc_weight))
@@ -162,21 +146,15 @@ class _ComHeadLoss(torch.autograd.Function):
     def backward(ctx, g_loss, _g_out):
         hm, heatmap, inds, box_mask, target_boxes, code_weights, out, *regs = ctx.saved_tensors
         B, C, H, W = hm.shape
-        d_hm = _like(hm)
-        d_regs = [_like(r) for r in regs]
-        assert d_hm.stride() == hm.stride() and all(d.stride() == r.stride() for d, r in zip(d_regs, regs))
+        d_hm = _maps.like(hm)
+        d_regs = [_maps.like(r) for r in regs]
         g = g_loss.detach().to(torch.float32).reshape(1).contiguous()
-
-        def dt(t):
-            return L.PCD_F32 if t.dtype == torch.float32 else L.PCD_BF16
+        m = _maps.pack_maps(hm, regs, d_regs)
         L.check(L.lib().pcd_com_loss_backward(
-            L.ptr(hm), L.ptr(d_hm), dt(hm), (ctypes.c_longlong * 4)(*hm.stride()), L.ptr(heatmap), B, C, H, W,
-            (ctypes.c_void_p * len(regs))(*[r.data_ptr() for r in regs]),
-            (ctypes.c_void_p * len(regs))(*[d.data_ptr() for d in d_regs]),
-            (ctypes.c_int * len(regs))(*[int(r.shape[1]) for r in regs]), dt(regs[0]) if regs else L.PCD_F32,
-            (ctypes.c_longlong * (4 * len(regs)))(*[v for r in regs for v in r.stride()]), len(regs), L.ptr(inds),
-            L.ptr(box_mask), L.ptr(target_boxes), int(inds.shape[1]), L.ptr(ctx.msum), L.ptr(code_weights),
-            ctx.weights[0], ctx.weights[1], L.ptr(out), L.ptr(g), L.stream_ptr()), "pcd_com_loss_backward")
+            L.ptr(hm), L.ptr(d_hm), m.hm_dtype, m.hm_strides, L.ptr(heatmap), B, C, H, W, m.reg_ptrs, m.reg_grads,
+            m.reg_ch, m.reg_dtype, m.reg_strides, m.n, L.ptr(inds), L.ptr(box_mask), L.ptr(target_boxes),
+            int(inds.shape[1]), L.ptr(ctx.msum), L.ptr(code_weights), ctx.weights[0], ctx.weights[1], L.ptr(out),
+            L.ptr(g), L.stream_ptr()), "pcd_com_loss_backward")
         return (d_hm,) + (None,) * 16 + tuple(d_regs)
 
 

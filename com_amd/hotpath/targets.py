@@ -4,6 +4,7 @@ the device.  Returns the reference's `ret_dict` (lists over heads of [B, ...] te
 import torch
 
 from .. import _lib as L
+from . import _maps
 
 
 def assign_targets(gt_boxes, feature_map_size, class_names, class_names_each_head, point_cloud_range, voxel_size,
@@ -19,10 +20,7 @@ def assign_targets(gt_boxes, feature_map_size, class_names, class_names_each_hea
                      device=gt.device)
     ret = {'heatmaps': [], 'target_boxes': [], 'inds': [], 'masks': [], 'heatmap_masks': []}
     for head_names in class_names_each_head:
-        cmap = [0] * (len(class_names) + 1)
-        for i, name in enumerate(class_names):
-            if name in head_names:
-                cmap[i + 1] = list(head_names).index(name) + 1
+        cmap = _maps.head_class_map(class_names, head_names)
         nc = len(head_names)
         heatmap = torch.empty((B, nc, H, W), dtype=torch.float32, device=gt.device)
         boxes = torch.empty((B, num_max_objs, code), dtype=torch.float32, device=gt.device)
