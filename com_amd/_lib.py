@@ -193,6 +193,15 @@ PROTOTYPES = {
                                       _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp]),
     "pcd_anchor_decode": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, ctypes.c_float,
                                ctypes.c_float, _vp, _vp, _vp]),
+    "pcd_anchor_cur_cluster": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "pcd_anchor_cur_groups": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pcd_anchor_cur_loss_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pcd_anchor_cur_loss_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp,
+                                         ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pcd_anchor_cur_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i,
+                                          _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp,
+                                          _vp, _vp]),
     "pcd_ball_query_stack": (_i, [_i, _i, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcd_group_points_stack": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcd_group_points_stack_grad": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -292,6 +301,18 @@ class PcdComCurriculum(ctypes.Structure):
 
 
 PCD_COM_CLUSTER_X5 = 0
+
+
+class PcdAnchorCurriculum(ctypes.Structure):
+    """include/pcd_ops.h: struct PcdAnchorCurriculum (LOSS_CURRICULUM of the anchor curriculum head)."""
+    _fields_ = [("ucl", ctypes.c_int), ("oto", ctypes.c_int), ("sm", ctypes.c_int), ("sma", ctypes.c_int),
+                ("norm", ctypes.c_int), ("smt", ctypes.c_float), ("pos_norm", ctypes.c_float), ("neg_norm", ctypes.c_float),
+                ("offset", ctypes.c_double), ("ema", ctypes.c_double)]
+
+
+PCD_ANCHOR_CUR_GROUPS = 96
+PCD_ANCHOR_CUR_ACCUM = 3 + 2 * PCD_ANCHOR_CUR_GROUPS
+PCD_ANCHOR_CUR_CLUSTER_BASE, PCD_ANCHOR_CUR_CLUSTER_X1, PCD_ANCHOR_CUR_CLUSTER_CAR, PCD_ANCHOR_CUR_CLUSTER_CAR_X2 = 0, 1, 2, 3
 
 
 class PcdBnReduce(ctypes.Structure):

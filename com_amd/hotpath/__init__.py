@@ -9,3 +9,5 @@ from .dense2d import BaseBEVBackbone, CenterHeadTowers, SeparateHead  # noqa: F4
 from .center_head import CenterHead  # noqa: F401
 from .curriculum_head import CurriculumCenterHead, CurriculumCenterHead_x5  # noqa: F401
 from .anchor_head import AnchorGenerator, AnchorHeadSingle, ResidualCoder  # noqa: F401
+from .anchor_curriculum_head import (CurriculumAnchorHeadSingle, CurriculumAnchorHeadSingle_car,  # noqa: F401
+                                     CurriculumAnchorHeadSingle_car_x2, CurriculumAnchorHeadSingle_x1)

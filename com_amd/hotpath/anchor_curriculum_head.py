@@ -1,0 +1,317 @@
+"""`CurriculumAnchorHeadSingle` and its `head_zoo` variants (`_x1`, `_car`, `_car_x2`) -- the COM curriculum on the
+anchor head of PointPillars, SECOND and the first stage of PV-RCNN, as registry drop-ins
+(pcdet/models/dense_heads/__init__.py; reference classes: curri_anchor_head_single.py:7-139, head_zoo.py:12-140 on
+anchor_head_curriculum.py:12-308, target_assigner/curri_axis_aligned_target_assigner.py and
+`CurriculumSigmoidFocalClassificationLoss`, pcdet/utils/loss_utils.py:79-331).
+
+Same constructor arguments, parameter names (a reference state dict loads with strict=True) and `forward(data_dict)`
+contract (`spatial_features_2d`, `gt_boxes`, `true_object`, `occupancy_ratio`, `facade_type` in), and the attributes the
+training loop touches: `head.epoch` (train_utils.py pushes it every epoch), `head.cls_loss_func.confidence_all`
+(= [sums, counts], device f32 (num_class, 96); what train_utils.py:117-123 reads after every step and feeds to COMAug's
+sampler at the end of the epoch) and `forward_ret_dict['groups']`.  All per-step work is on the device
+(com_amd/csrc/anchorhead_cur.hip; C ABI `pcd_anchor_cur_*`): one launch for `cluster` (the `class_id.max()` of the base
+class and `_x1` is reduced inside it), one gather for the anchors' `groups`, and get_loss = statistics pass + one-block
+state update + the fused anchor loss with the curriculum weight + ordered finish.  Nothing is read back, no
+[B, N, C, 97] tensor exists, and forward + get_loss + backward can sit in a captured graph.
+
+Epoch: everything that depends on `head.epoch` (the heights with START / END / INV / FIXED / CUT folded in, the SME
+gate) lives in a small device table that `head.epoch = e` refreshes with a host-to-device copy, outside any graph: a
+captured step survives an epoch change without re-capture.  The state (mean / std per class as device doubles, the
+(num_class, 96) tensors and their running epoch sums) is created by `cls_loss_func.init_state(device)` or by the first
+eager step, never during capture.
+
+Scope: what `AnchorHeadSingle` supports, and in `get_loss` num_class == 1 (the reference's own get_box_reg_layer_loss
+multiplies a (B, N) by a (B, N, C) tensor there) and `LOSS_CURRICULUM.DIST` False (it needs a collective in the middle
+of the loss).  Targets and groups work for any class count.  Everything else raises a PcdError naming the key.
+
+Deviations from the reference, on purpose:
+  * On a first UCL step without a grouped positive the reference raises (`None + ...`, loss_utils.py:240); here its
+    evident fallback applies: threshold 0.5, variance 0.2 (:243-246).
+  * A zero standard deviation under NORM is not special-cased (the weight is then inf / nan, as in the reference).
+  * The reference's quirk is kept: the EMA factor of the mean / std is the focal `alpha` (0.25, :196-197), not
+    LOSS_CURRICULUM.ALPHA.
+  * Box groups above 96 (reachable in `_x1`, whose car loop counts to 160) index outside the reference's scatter tensor
+    and fail there; here they count in the statistics and are left out of `confidence_all`."""
+import ctypes
+import math
+
+import torch
+import torch.nn as nn
+
+from .. import _lib as L
+from ._maps import dtype_code as _dt, like as _like
+from .anchor_head import AnchorHeadSingle, _split, _strides3
+from .dense2d import _get
+
+NUM_GROUPS = L.PCD_ANCHOR_CUR_GROUPS
+SAVED_FLOATS = 8          # com_amd/csrc/anchorhead_common.h: SV_FLOATS
+TABLE_FLOATS = 4          # include/pcd_ops.h: epoch_table row
+
+
+def _dev(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise L.PcdError(f"{what} needs a HIP device tensor (there is no CPU fallback)")
+    return t
+
+
+def cluster(gt_boxes, true_object, occupancy_ratio, facade_type, variant=L.PCD_ANCHOR_CUR_CLUSTER_BASE):
+    """[B, M] int64 difficulty groups of one of the four `cluster` methods.  true_object=None (the reference would fail
+    on `None == 1`) is rejected."""
+    if true_object is None:
+        raise L.PcdError("cluster needs data_dict['true_object'] (COMAug's marker of real vs pasted objects)")
+    gt = _dev(gt_boxes, "cluster").contiguous().float()
+    B, M, code = gt.shape
+    to, occ, fac = (_dev(t, "cluster").contiguous().float() for t in (true_object, occupancy_ratio, facade_type))
+    assert to.shape == (B, M) and occ.shape == (B, M) and fac.shape == (B, M)
+    group = torch.empty((B, M), dtype=torch.int64, device=gt.device)
+    L.check(L.lib().pcd_anchor_cur_cluster(L.ptr(gt), B, M, code, L.ptr(to), L.ptr(occ), L.ptr(fac), int(variant),
+                                           L.ptr(group), L.stream_ptr()), "pcd_anchor_cur_cluster")
+    return group
+
+
+def anchor_groups(targets, group):
+    """`groups` int32 [B, N] of curri_axis_aligned_target_assigner.py:246-311: the box's group at the positives, 0 at the
+    background anchors, -1 at the ignored ones."""
+    labels, gt_index = targets['box_cls_labels'], targets['box_gt_index']
+    group = _dev(group, "assign_targets").contiguous().to(torch.int64)
+    B, N = labels.shape
+    if group.dim() != 2 or group.shape[0] != B:
+        raise L.PcdError(f"assign_targets: group {tuple(group.shape)}, want [{B}, M] (one value per gt box)")
+    groups = torch.empty((B, N), dtype=torch.int32, device=labels.device)
+    L.check(L.lib().pcd_anchor_cur_groups(L.ptr(labels), L.ptr(gt_index), L.ptr(group) if group.shape[1] else None, B, N,
+                                          int(group.shape[1]), L.ptr(groups), L.stream_ptr()), "pcd_anchor_cur_groups")
+    return groups
+
+
+def normalisers(offset, pos_weight=1):
+    """(pos_norm, neg_norm) of loss_utils.py:117-119 with the normal cdf from math.erf."""
+    cdf = 0.5 * (1.0 + math.erf(float(offset) / math.sqrt(2.0)))
+    return 0.5 / (1.0 - cdf) * pos_weight, 0.5 / cdf
+
+
+def _per_class(value, idx):
+    return value[idx] if type(value) is list else value
+
+
+def epoch_table(curriculum, epoch, num_class):
+    """[num_class][4] host rows {height, elongation, SME gate, 0} at `epoch` (loss_utils.py:249-274, :283, :288)."""
+    g = dict(curriculum or {}).get
+    start, cut = g('START', 0), g('CUT', 10000)
+    rows = []
+    for c in range(num_class):
+        base_height, end = _per_class(g('HEIGHT', 1), c), _per_class(g('END', 30), c)
+        if g('INV', False):
+            height = base_height * (end - epoch) / (end - start)
+        else:
+            height = base_height * max(end - epoch, 0) / (end - start)
+        if g('FIXED', False):
+            height = base_height
+        if epoch > cut:
+            height = 0
+        rows.append([float(height), float(_per_class(g('ELONGATION', -10), c)), float(epoch >= g('SME', 20)), 0.0])
+    return rows
+
+
+def curriculum_struct(curriculum, alpha=0.25):
+    """LOSS_CURRICULUM -> PcdAnchorCurriculum with CurriculumSigmoidFocalClassificationLoss.__init__'s defaults (:97-125)."""
+    g = dict(curriculum or {}).get
+    c = L.PcdAnchorCurriculum()
+    c.ucl, c.oto, c.sm, c.sma = int(bool(g('UCL', True))), int(bool(g('OTO', False))), int(bool(g('SM', False))), int(bool(g('SMA', False)))
+    c.norm = int(g('NORM', False) is not False)          # (`if self.use_norm is False: var = 1`, :247)
+    c.smt = float(g('SMT', 0.15))
+    c.pos_norm, c.neg_norm = normalisers(g('OFFSET', 0), g('POSW', 1))
+    c.offset, c.ema = float(g('OFFSET', 0)), float(alpha)
+    return c
+
+
+class CurriculumSigmoidFocalClassificationLoss(nn.Module):
+    """What the reference's loss object keeps between steps (loss_utils.py:93, :121, :183-197, :312), on the device:
+    `state` double [num_class, 4] = {mean, std, stored flag, 0}; `confidence_all` = [sums, counts] of the last step; the
+    running epoch sums of both (`start_epoch()` clears them); the epoch table.  It holds no parameters or buffers."""
+
+    def __init__(self, gamma=2.0, alpha=0.25, model_config=None, num_class=1):
+        super().__init__()
+        self.alpha, self.gamma, self.num_class = float(alpha), float(gamma), int(num_class)
+        curriculum = _get(model_config, 'LOSS_CURRICULUM', None)
+        if curriculum is None:
+            raise L.PcdError("CurriculumAnchorHeadSingle: LOSS_CURRICULUM is missing from the head's configuration")
+        self.curriculum = dict(curriculum)
+        if self.curriculum.get('DIST', False):
+            raise L.PcdError("CurriculumAnchorHeadSingle: LOSS_CURRICULUM.DIST = True is not supported by the HIP anchor "
+                             "head (it needs a collective in the middle of the loss)")
+        self.use_curriculum_loss = bool(self.curriculum.get('UCL', True))
+        self.pos_norm, self.neg_norm = normalisers(self.curriculum.get('OFFSET', 0), self.curriculum.get('POSW', 1))
+        self.struct = curriculum_struct(self.curriculum, self.alpha)
+        self.epoch = 0
+        self.state = None
+        self.confidence_all = 0                      # (the reference's initial value, :93)
+        self.epoch_confidence = self.epoch_num = None
+        self._accum = self._table = None
+        self._table_epoch = None
+
+    def init_state(self, device):
+        """Create the device-side state.  Done by the first get_loss; call it yourself before capturing the first step
+        into a graph (state allocated during a capture would live in the graph's private pool and die with it)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise L.PcdError("CurriculumAnchorHeadSingle: run one eager step (or cls_loss_func.init_state(device)) before "
+                             "graph capture")
+        shape = (self.num_class, NUM_GROUPS)
+        self.state = torch.zeros((self.num_class, 4), dtype=torch.float64, device=device)
+        self.confidence_all = [torch.zeros(shape, dtype=torch.float32, device=device) for _ in range(2)]
+        self.epoch_confidence = torch.zeros(shape, dtype=torch.float32, device=device)
+        self.epoch_num = torch.zeros(shape, dtype=torch.float32, device=device)
+        self._accum = torch.zeros((L.PCD_ANCHOR_CUR_ACCUM,), dtype=torch.int64, device=device)
+        self._table = torch.zeros((self.num_class, TABLE_FLOATS), dtype=torch.float32, device=device)
+        self._table_epoch = None
+        self.set_epoch(self.epoch)
+        return self
+
+    def set_epoch(self, epoch):
+        """Refresh the device table for `epoch` (a host-to-device copy; never inside a capture)."""
+        self.epoch = epoch
+        if self._table is None or self._table_epoch == epoch:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise L.PcdError("CurriculumAnchorHeadSingle: set head.epoch outside the graph capture (the epoch table is "
+                             "refreshed by a host-to-device copy)")
+        self._table.copy_(torch.tensor(epoch_table(self.curriculum, epoch, self.num_class), dtype=torch.float32))
+        self._table_epoch = epoch
+
+    def start_epoch(self):
+        """the per-epoch sums start empty (train_utils.py:57-58)."""
+        if self.epoch_confidence is not None:
+            self.epoch_confidence.zero_()
+            self.epoch_num.zero_()
+
+    @property
+    def means(self):
+        """self.means of the reference as a host list (a read-back: for logging and tests only)."""
+        return self._host(0)
+
+    @property
+    def stds(self):
+        return self._host(1)
+
+    def _host(self, col):
+        if self.state is None:
+            return None
+        s = self.state.cpu()
+        return [float(s[c, col]) if float(s[c, 2]) != 0 else None for c in range(self.num_class)]
+
+
+class _AnchorCurLoss(torch.autograd.Function):
+    """get_loss through pcd_anchor_cur_loss_forward / _backward: 4 + 1 launches."""
+
+    @staticmethod
+    def forward(ctx, preds, labels, targets, num_pos, groups, code_weights, tab, has_dir, weights, lf):
+        if not preds.is_cuda:
+            raise L.PcdError("CurriculumAnchorHeadSingle.get_loss needs HIP device tensors (there is no CPU fallback)")
+        cls, box, dr = _split(preds, tab, has_dir)
+        B = int(preds.shape[0])
+        lib = L.lib()
+        out = torch.empty((4,), dtype=torch.float32, device=preds.device)
+        saved = torch.empty((SAVED_FLOATS,), dtype=torch.float32, device=preds.device)
+        ws = torch.empty((max(int(lib.pcd_anchor_cur_loss_workspace_bytes(B, tab.H, tab.W, tab.A)), 256),), dtype=torch.uint8,
+                         device=preds.device)
+        cur = ctypes.cast(ctypes.pointer(lf.struct), ctypes.c_void_p)
+        L.check(lib.pcd_anchor_cur_loss_forward(
+            L.ptr(cls), L.ptr(box), L.ptr(dr), _dt(preds), _strides3([cls, box, dr]), L.ptr(labels), L.ptr(targets),
+            L.ptr(num_pos), L.ptr(groups), B, tab.H, tab.W, tab.A, tab.num_class, tab.num_dir_bins, L.ptr(tab.kinds),
+            L.ptr(code_weights), weights[0], weights[1], weights[2], tab.dir_offset, cur, L.ptr(lf._table), L.ptr(lf.state),
+            L.ptr(lf._accum), L.ptr(lf.confidence_all[0]), L.ptr(lf.confidence_all[1]), L.ptr(lf.epoch_confidence),
+            L.ptr(lf.epoch_num), L.ptr(saved), L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr()),
+            "pcd_anchor_cur_loss_forward")
+        ctx.save_for_backward(preds, labels, targets, num_pos, groups, code_weights, saved)
+        ctx.meta = (tab, has_dir, weights, lf.struct)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_out):
+        preds, labels, targets, num_pos, groups, code_weights, saved = ctx.saved_tensors
+        tab, has_dir, weights, struct = ctx.meta
+        d_preds = _like(preds)
+        cls, box, dr = _split(preds, tab, has_dir)
+        d_cls, d_box, d_dr = _split(d_preds, tab, has_dir)
+        g = g_loss.detach().to(torch.float32).reshape(1).contiguous()
+        L.check(L.lib().pcd_anchor_cur_loss_backward(
+            L.ptr(cls), L.ptr(box), L.ptr(dr), L.ptr(d_cls), L.ptr(d_box), L.ptr(d_dr), _dt(preds),
+            _strides3([cls, box, dr]), L.ptr(labels), L.ptr(targets), L.ptr(num_pos), L.ptr(groups), int(preds.shape[0]),
+            tab.H, tab.W, tab.A, tab.num_class, tab.num_dir_bins, L.ptr(tab.kinds), L.ptr(code_weights), weights[0],
+            weights[1], weights[2], tab.dir_offset, ctypes.cast(ctypes.pointer(struct), ctypes.c_void_p), L.ptr(saved),
+            L.ptr(g), L.stream_ptr()), "pcd_anchor_cur_loss_backward")
+        return (d_preds,) + (None,) * 9
+
+
+def anchor_curriculum_loss(preds, targets_dict, tab, code_weights, cls_weight, loc_weight, dir_weight, loss_func, has_dir=True):
+    """(rpn_loss, out) as anchor_head.anchor_loss, with the curriculum of `loss_func` (its state is updated)."""
+    if tab.num_class != 1:
+        raise L.PcdError(f"CurriculumAnchorHeadSingle.get_loss: num_class = {tab.num_class} is not supported (the "
+                         "reference's get_box_reg_layer_loss cannot broadcast its curriculum weight for more than one class)")
+    if loss_func.state is None or loss_func.state.device != preds.device:
+        loss_func.init_state(preds.device)
+    loss_func.set_epoch(loss_func.epoch)
+    return _AnchorCurLoss.apply(preds, targets_dict['box_cls_labels'], targets_dict['box_reg_targets'],
+                                targets_dict['num_pos'], targets_dict['groups'], code_weights, tab, bool(has_dir),
+                                (float(cls_weight), float(loc_weight), float(dir_weight)), loss_func)
+
+
+class CurriculumAnchorHeadSingle(AnchorHeadSingle):
+    """curri_anchor_head_single.py:7-139 on anchor_head_curriculum.py (module docstring)."""
+    cluster_variant = L.PCD_ANCHOR_CUR_CLUSTER_BASE
+
+    def __init__(self, model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range,
+                 predict_boxes_when_training=True, **kwargs):
+        super().__init__(model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range,
+                         predict_boxes_when_training=predict_boxes_when_training)
+        self.cls_loss_func = CurriculumSigmoidFocalClassificationLoss(alpha=0.25, gamma=2.0, model_config=model_cfg,
+                                                                      num_class=self.num_class)
+        self.epoch = 0
+
+    @property
+    def epoch(self):
+        return self.cls_loss_func.epoch
+
+    @epoch.setter
+    def epoch(self, value):
+        self.cls_loss_func.set_epoch(value)
+
+    def cluster(self, gt_boxes, true_object, occupancy_ratio, facade_type):
+        return cluster(gt_boxes, true_object, occupancy_ratio, facade_type, self.cluster_variant)
+
+    def assign_targets(self, gt_boxes, group=None):
+        """anchor_head_curriculum.py:90-101: the plain targets + `groups` (int32 [B, N]) when `group` is given."""
+        targets = super().assign_targets(gt_boxes)
+        if group is not None:
+            targets['groups'] = anchor_groups(targets, group)
+        return targets
+
+    def _targets(self, data_dict):
+        group = self.cluster(gt_boxes=data_dict['gt_boxes'], true_object=data_dict.get('true_object', None),
+                             occupancy_ratio=data_dict['occupancy_ratio'], facade_type=data_dict['facade_type'])
+        return self.assign_targets(gt_boxes=data_dict['gt_boxes'], group=group)
+
+    def get_loss(self):
+        """anchor_head_curriculum.py:249-256"""
+        f = self.forward_ret_dict
+        loss, out = anchor_curriculum_loss(f['preds'], f, self.tables(f['preds'].device), self.code_weights,
+                                           *self.loss_weights, loss_func=self.cls_loss_func, has_dir=self.use_dir)
+        tb_dict = {'rpn_loss_cls': out[1], 'rpn_loss_loc': out[2], 'rpn_loss': out[0]}
+        if self.use_dir:
+            tb_dict['rpn_loss_dir'] = out[3]
+        return loss, tb_dict
+
+
+class CurriculumAnchorHeadSingle_x1(CurriculumAnchorHeadSingle):
+    """head_zoo.py:12-65: five distance bins; the car, pedestrian and cyclist loops in that order."""
+    cluster_variant = L.PCD_ANCHOR_CUR_CLUSTER_X1
+
+
+class CurriculumAnchorHeadSingle_car(CurriculumAnchorHeadSingle):
+    """head_zoo.py:68-104: the 96 car groups."""
+    cluster_variant = L.PCD_ANCHOR_CUR_CLUSTER_CAR
+
+
+class CurriculumAnchorHeadSingle_car_x2(CurriculumAnchorHeadSingle):
+    """head_zoo.py:107-140: 15 car groups over distance and the unscaled occupancy bins."""
+    cluster_variant = L.PCD_ANCHOR_CUR_CLUSTER_CAR_X2

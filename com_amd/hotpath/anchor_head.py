@@ -374,6 +374,10 @@ class AnchorHeadSingle(nn.Module):
         """anchor_head_template.py:89-100 -> axis_aligned_target_assigner.py:36-210, three launches for the batch."""
         return assign_targets(self.tables(gt_boxes.device), gt_boxes)
 
+    def _targets(self, data_dict):
+        """the training targets of forward() (the curriculum heads add their groups here)"""
+        return self.assign_targets(gt_boxes=data_dict['gt_boxes'])
+
     def get_loss(self):
         """anchor_head_template.py:220-227"""
         f = self.forward_ret_dict
@@ -403,7 +407,7 @@ class AnchorHeadSingle(nn.Module):
         if self.use_dir:
             self.forward_ret_dict['dir_cls_preds'] = dir_cls_preds
         if self.training:
-            self.forward_ret_dict.update(self.assign_targets(gt_boxes=data_dict['gt_boxes']))
+            self.forward_ret_dict.update(self._targets(data_dict))
         if not self.training or self.predict_boxes_when_training:
             with torch.no_grad():
                 batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(

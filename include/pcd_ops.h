@@ -780,6 +780,68 @@ int pcd_anchor_decode(const void *cls_preds, const void *box_preds, const void *
                       float dir_limit_offset, float *batch_box_preds, float *batch_cls_preds, void *stream);
 
 /* ============================================================================================
+ * (f3b) The COM curriculum on the anchor head: CurriculumAnchorHeadSingle and its head_zoo variants (_x1, _car, _car_x2)
+ *       over AnchorHeadCurriculum / CurriculumAxisAlignedTargetAssigner / CurriculumSigmoidFocalClassificationLoss --
+ *       com_amd/csrc/anchorhead_cur.hip.  Tables, maps and labels as in (f3); every entry point takes a stream, allocates
+ *       nothing and reads nothing back.
+ *
+ *   pcd_anchor_cur_cluster   pcdet/models/dense_heads/curri_anchor_head_single.py:43-96 (PCD_ANCHOR_CUR_CLUSTER_BASE) and
+ *     head_zoo.py:12-65 (_X1), :68-104 (_CAR), :107-140 (_CAR_X2): group int64 [B][M], the value each box holds after all of
+ *     the reference's overwriting assignments.  BASE and X1 branch on `class_id.max() == 1` over the whole batch
+ *     (:81, head_zoo.py:50,59): the maximum is reduced on the device in the same (single-block) launch.
+ *   pcd_anchor_cur_groups    target_assigner/curri_axis_aligned_target_assigner.py:246-311 (POS_FRACTION < 0): groups int32
+ *     [B][N] = group[b][gt_index] at the positives, 0 where box_cls_labels == 0, -1 at ignored anchors.
+ *   pcd_anchor_cur_loss_forward   anchor_head_curriculum.py:103-256 (get_cls_layer_loss, get_box_reg_layer_loss, get_loss)
+ *     with pcdet/utils/loss_utils.py:79-331.  num_class must be 1 (PCD_ERR_UNSUPPORTED otherwise: the reference's
+ *     get_box_reg_layer_loss multiplies (B, N) by (B, N, C)).  Four launches:
+ *       statistics (:150-181, :200-214)  over the grouped positives: sigmoid sum, sum of squares, count; the 96 group
+ *         sums and counts -- 64-bit fixed-point integer atomics into accum (order independent, bit-identical runs)
+ *       state (:183-197, :240-247)  one block: state double[4] = {mean, std, stored flag, 0} (first update stores, later
+ *         ones are an EMA with factor cur->ema; untouched without a grouped positive or with ucl == 0); conf_sum /
+ *         conf_num f32 [96] of this step (confidence_all), added to epoch_conf / epoch_num; saved f32 [8] = threshold,
+ *         variance, then the epoch_table row; accum cleared for the next step (accum: 195 x u64, zero before the first)
+ *       loss (:236-300 weight, times the focal term, the smooth-L1 weights and the direction weights) + ordered finish:
+ *         out as pcd_anchor_loss_forward.  ucl == 0: weight 1, bit-identical to pcd_anchor_loss_forward.
+ *     epoch_table device f32 [4] = {height, elongation, SME gate (epoch >= SME), 0} of class 0 at the current epoch:
+ *     everything that depends on the epoch (START / END / INV / FIXED / CUT are folded into the height by the host).
+ *   pcd_anchor_cur_loss_backward  weight x the plain anchor gradient (the weight is detached, :298); reads the `saved`
+ *     of its forward, never the live state.
+ * ============================================================================================ */
+#define PCD_ANCHOR_CUR_GROUPS 96
+#define PCD_ANCHOR_CUR_ACCUM (3 + 2 * PCD_ANCHOR_CUR_GROUPS)
+#define PCD_ANCHOR_CUR_CLUSTER_BASE 0
+#define PCD_ANCHOR_CUR_CLUSTER_X1 1
+#define PCD_ANCHOR_CUR_CLUSTER_CAR 2
+#define PCD_ANCHOR_CUR_CLUSTER_CAR_X2 3
+typedef struct PcdAnchorCurriculum {        /* LOSS_CURRICULUM as CurriculumSigmoidFocalClassificationLoss.__init__ reads it */
+    int ucl, oto, sm, sma, norm;
+    float smt, pos_norm, neg_norm;          /* SMT; 0.5 / (1 - cdf(OFFSET)) * POSW; 0.5 / cdf(OFFSET) */
+    double offset, ema;                     /* OFFSET; the EMA factor (the reference uses the focal alpha, 0.25) */
+} PcdAnchorCurriculum;
+int pcd_anchor_cur_cluster(const float *gt_boxes, int batch, int n_boxes, int code_size, const float *true_object,
+                           const float *occupancy_ratio, const float *facade_type, int variant, long long *group,
+                           void *stream);
+int pcd_anchor_cur_groups(const int *box_cls_labels, const int *gt_index, const long long *group, int batch, int n_anchors,
+                          int n_boxes, int *groups, void *stream);
+size_t pcd_anchor_cur_loss_workspace_bytes(int batch, int height, int width, int n_kinds);
+int pcd_anchor_cur_loss_forward(const void *cls_preds, const void *box_preds, const void *dir_preds, int dtype,
+                                const long long *strides_host /*[3][4]*/, const int *box_cls_labels,
+                                const float *box_reg_targets, const int *num_pos, const int *groups, int batch, int height,
+                                int width, int n_kinds, int num_class, int num_dir_bins, const float *kinds,
+                                const float *code_weights, float cls_weight, float loc_weight, float dir_weight,
+                                float dir_offset, const PcdAnchorCurriculum *cur, const float *epoch_table, double *state,
+                                unsigned long long *accum, float *conf_sum, float *conf_num, float *epoch_conf,
+                                float *epoch_num, float *saved /*device [8]*/, float *out /*device [4]*/, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int pcd_anchor_cur_loss_backward(const void *cls_preds, const void *box_preds, const void *dir_preds, void *d_cls, void *d_box,
+                                 void *d_dir, int dtype, const long long *strides_host, const int *box_cls_labels,
+                                 const float *box_reg_targets, const int *num_pos, const int *groups, int batch, int height,
+                                 int width, int n_kinds, int num_class, int num_dir_bins, const float *kinds,
+                                 const float *code_weights, float cls_weight, float loc_weight, float dir_weight,
+                                 float dir_offset, const PcdAnchorCurriculum *cur, const float *saved, const float *grad_out,
+                                 void *stream);
+
+/* ============================================================================================
  * (f2, BASELINE config 3) The COM curriculum head on the device.  Replaces, for one head and the whole batch:
  *   pcd_com_cluster_groups   CurriculumCenterHead.cluster         pcdet/models/dense_heads/curriculum_center_head.py:414-459
  *   pcd_com_assign_targets   assign_targets / assign_target_of_single_head  same file :108-307 (+ centernet_utils.py:46-106)
