@@ -225,6 +225,15 @@ PROTOTYPES = {
     "pcd_pfn_relu_pool_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "pcd_boxes_overlap_bev": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp]),
     "pcd_boxes_iou_bev_host": (_i, [_vp, _i, _vp, _i, _vp]),
+    "pcd_points_in_boxes_host": (_i, [_vp, _i, _vp, _i, _vp]),
+    "pcd_points_in_boxes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pcd_point_head_assign_targets": (_i, [_vp, _i, _vp, _i, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i, _vp, _vp,
+                                           _vp]),
+    "pcd_point_head_loss_workspace_bytes": (_sz, [_i]),
+    "pcd_point_head_loss_forward": (_i, [_vp, _i, ctypes.c_longlong, _vp, _vp, _i, _i, ctypes.c_float, _vp, _vp, _sz, _vp]),
+    "pcd_point_head_loss_backward": (_i, [_vp, _vp, _i, ctypes.c_longlong, _vp, _vp, _i, _i, ctypes.c_float, _vp, _vp]),
+    "pcd_roiaware_pool3d_forward": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "pcd_roiaware_pool3d_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "pcd_nms_workspace_bytes": (_sz, [_i]),
     "pcd_nms_bev": (_i, [_vp, _i, ctypes.c_float, _i, _vp, _vp, _vp, _sz, _vp]),
     "pcd_centerhead_postproc_workspace_bytes": (_sz, [_vp, _vp]),

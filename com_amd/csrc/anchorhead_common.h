@@ -1,6 +1,7 @@
 // What the anchor-head loss kernels share (anchorhead.hip: AnchorHeadSingle; anchorhead_cur.hip: the COM curriculum
 // form): table layout, the prediction-map descriptor, ONE loss core with a compile-time curriculum variant, the ordered
-// second pass and the host-side argument checks.  Include inside the translation unit (everything is file-local).
+// second pass and the host-side argument checks; the focal element and the ordered pass also serve the point head
+// (roiaware.hip).  Include inside the translation unit (everything is file-local).
 #pragma once
 #include "common.h"
 
@@ -81,6 +82,20 @@ __device__ __forceinline__ float anc_cur_weight(const AncCur &q, const float *sv
     return wgt * (p > thr ? q.pos_norm : q.neg_norm);
 }
 
+// One element of SigmoidFocalClassificationLoss (loss_utils.py:41-74), alpha 0.25, gamma 2, for a logit xv and a target t
+// in {0, 1}: the unweighted loss (GRAD == false) or its derivative with respect to the logit (GRAD == true).  The anchor
+// heads (below) and the point head (roiaware.hip) weight it per anchor / per point.
+template <bool GRAD>
+__device__ __forceinline__ float focal_el(float xv, float t) {
+    const float p = 1.f / (1.f + expf(-xv));
+    const float aw = t * 0.25f + (1.f - t) * 0.75f;
+    const float pt = t * (1.f - p) + (1.f - t) * p;
+    const float bce = fmaxf(xv, 0.f) - xv * t + log1pf(expf(-fabsf(xv)));
+    if (!GRAD) return aw * (pt * pt) * bce;
+    const float dpt = (1.f - 2.f * t) * p * (1.f - p);
+    return aw * (2.f * pt * dpt * bce + pt * pt * (p - t));
+}
+
 struct AncNoCur {                   // the plain loss: no extra kernel arguments
     static constexpr bool on = false;
 };
@@ -136,17 +151,8 @@ __global__ __launch_bounds__(256) void anc_loss_kernel(AncMaps m, AncLossCfg c, 
             }
             const float xv = load_el(m.p[0], m.dtype, off);
             const float t = (j == tcls) ? 1.f : 0.f;
-            const float p = 1.f / (1.f + expf(-xv));
-            const float aw = t * 0.25f + (1.f - t) * 0.75f;
-            const float pt = t * (1.f - p) + (1.f - t) * p;
-            const float bce = fmaxf(xv, 0.f) - xv * t + log1pf(expf(-fabsf(xv)));
-            if (!GRAD) {
-                l_cls += aw * (pt * pt) * bce * w;
-            } else {
-                const float dpt = (1.f - 2.f * t) * p * (1.f - p);
-                const float g = aw * (2.f * pt * dpt * bce + pt * pt * (p - t));
-                store_el(m.g[0], m.dtype, off, g * up * c.cls_w);
-            }
+            if (!GRAD) l_cls += focal_el<false>(xv, t) * w;
+            else store_el(m.g[0], m.dtype, off, focal_el<true>(xv, t) * up * c.cls_w);
         }
         // ---- regression: smooth-L1, beta 1/9, with the sin-difference substitution on the heading (:141-148, :192-193)
         const float *tg = reg_targets + ((size_t)b * N + n) * 7;

@@ -1,0 +1,469 @@
+// The reference's roiaware_pool3d package and the PointHeadSimple targets / loss on the device (gfx950).  C ABI:
+// include/pcd_ops.h (f5).
+//
+//   pcd_points_in_boxes_host     pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:121-168 (points_in_boxes_cpu): HOST
+//                                pointers, no GPU call -- what box_utils.remove_points_in_boxes3d (box_utils.py:117-131)
+//                                calls per frame inside the DataLoader workers of COMAug's database samplers
+//   pcd_points_in_boxes          roiaware_pool3d_kernel.cu:16-36, :313-359 (points_in_boxes_gpu)
+//   pcd_point_head_assign_targets   pcdet/models/dense_heads/point_head_simple.py:21-48 + point_head_template.py:49-129
+//                                (assign_stack_targets with set_ignore_flag) + box_utils.py:187-200 (enlarge_box3d), for
+//                                the whole stacked batch
+//   pcd_point_head_loss_forward / _backward   point_head_template.py:131-155 (get_cls_layer_loss) with loss_utils.py:10-74
+//   pcd_roiaware_pool3d_forward / _backward   roiaware_pool3d_kernel.cu:39-310
+//
+// Point-in-box: one thread per point; the frame's boxes are staged once per workgroup in LDS as centre, half height,
+// cos / sin and the two double thresholds (roiaware_geom.h), in chunks of 128 (no cap on the number of boxes).  Every lane
+// reads the same box (an LDS broadcast), the sincos is paid per box and workgroup instead of per (point, box) pair, and a
+// lane stops at its first hit.  The target assignment stages the plain and the enlarged box of a GT row together (one
+// sincos for both) and walks the frames a workgroup's points belong to (one, when the stacked points are sorted by frame).
+//
+// RoI-aware pooling: the contract is the ORDER of a voxel's point list (ascending point index, cut after
+// max_pts_each_voxel - 1 entries: what the reference's serial one-thread-per-box loop produces).  One workgroup per RoI
+// walks the points 1024 at a time: all four waves test their points and leave a voxel id (or -1) per point in LDS, then
+// wave 0 walks those ids in order and appends them, the rank of a point among the lanes with the same voxel coming from
+// ballots, the voxel counters living in LDS.  The (N, P) int mask of the reference is never materialised.  Pooling and
+// its backward run with the CHANNEL as the fastest thread index: a wave reads / adds into contiguous runs of one point's
+// row (the lesson of pcd_group_points_stack_grad) instead of 64 different rows.
+#include "anchorhead_common.h"
+#include "roiaware_geom.h"
+
+#include <limits.h>
+
+#define RA_CHUNK 128            // boxes staged per pass
+#define RA_COLLECT_PTS 1024     // points per pass of the collect kernel (4 per thread)
+#define RA_MAX_VOXELS 8192      // voxel counters of one RoI in LDS (32 KiB)
+
+namespace {
+
+__global__ __launch_bounds__(256) void ra_points_in_boxes_kernel(const float *__restrict__ boxes, const float *__restrict__ pts,
+                                                                 int nb, int np, int *__restrict__ out) {
+    __shared__ RaBox s_box[RA_CHUNK];
+    const int b = blockIdx.y;
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const bool valid = n < np;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (valid) {
+        const float *p = pts + ((size_t)b * np + n) * 3;
+        x = p[0];
+        y = p[1];
+        z = p[2];
+    }
+    int found = -1;
+    for (int m0 = 0; m0 < nb; m0 += RA_CHUNK) {
+        const int cnt = min(RA_CHUNK, nb - m0);
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) s_box[threadIdx.x] = ra_prepare(boxes + ((size_t)b * nb + m0 + threadIdx.x) * 7, RA_MARGIN_DEVICE);
+        __syncthreads();
+        if (!valid || found >= 0) continue;
+        for (int j = 0; j < cnt; ++j) {
+            float lx, ly;
+            if (ra_point_in_box(s_box[j], x, y, z, lx, ly)) {
+                found = m0 + j;
+                break;
+            }
+        }
+    }
+    if (valid) out[(size_t)b * np + n] = found;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// PointHeadSimple targets
+struct PhBox {
+    RaBox in;                   // the GT box
+    double tx_e, ty_e;          // the enlarged box: same centre and heading
+    float hz_e;
+    int cls;
+};
+
+__global__ __launch_bounds__(256) void ph_assign_kernel(const float *__restrict__ pc, int N, const float *__restrict__ gt, int B, int M,
+                                                        float ex, float ey, float ez, int num_class,
+                                                        long long *__restrict__ labels, int *__restrict__ num_pos) {
+    __shared__ PhBox s_box[RA_CHUNK];
+    __shared__ int s_lo, s_hi;
+    __shared__ int s_cnt[4];
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const bool valid = n < N;
+    if (threadIdx.x == 0) {
+        s_lo = INT_MAX;
+        s_hi = -1;
+    }
+    __syncthreads();
+    int bs = -1;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (valid) {
+        const float *p = pc + (size_t)n * 4;
+        const float fb = p[0];
+        if (fb >= 0.f && fb < (float)B && fb == (float)(int)fb) bs = (int)fb;   // (bs_idx == k): other rows match no frame
+        x = p[1];
+        y = p[2];
+        z = p[3];
+        if (bs >= 0) {
+            atomicMin(&s_lo, bs);
+            atomicMax(&s_hi, bs);
+        }
+    }
+    __syncthreads();
+    const int lo = s_lo, hi = s_hi;
+    bool fg = false, ext = false;
+    int cls = 0;
+    for (int f = lo; f <= hi; ++f) {
+        for (int m0 = 0; m0 < M; m0 += RA_CHUNK) {
+            const int cnt = min(RA_CHUNK, M - m0);
+            __syncthreads();
+            if ((int)threadIdx.x < cnt) {
+                const float *g = gt + ((size_t)f * M + m0 + threadIdx.x) * 8;
+                PhBox q;
+                q.in = ra_prepare(g, RA_MARGIN_DEVICE);
+                RaBox e = q.in;                                          // enlarge_box3d: widths added to every row,
+                ra_extents(e, g[3] + ex, g[4] + ey, g[5] + ez, RA_MARGIN_DEVICE);   // zero padding rows included
+                q.tx_e = e.tx;
+                q.ty_e = e.ty;
+                q.hz_e = e.hz;
+                q.cls = (int)g[7];
+                s_box[threadIdx.x] = q;
+            }
+            __syncthreads();
+            if (bs != f || (fg && ext)) continue;
+            for (int j = 0; j < cnt; ++j) {
+                const PhBox &q = s_box[j];
+                const bool zi = !fg && ra_z_inside(z, q.in.cz, q.in.hz);
+                const bool ze = !ext && ra_z_inside(z, q.in.cz, q.hz_e);
+                if (!zi && !ze) continue;
+                float lx, ly;
+                ra_local(q.in, x, y, lx, ly);
+                if (zi && ra_xy_inside(lx, ly, q.in.tx, q.in.ty)) {        // the FIRST containing box gives the class
+                    fg = true;
+                    cls = q.cls;
+                }
+                if (ze && ra_xy_inside(lx, ly, q.tx_e, q.ty_e)) ext = true;
+                if (fg && ext) break;
+            }
+        }
+    }
+    // point_head_template.py:91-92, :101-102: ignored where fg XOR inside an enlarged box, then the foreground's class
+    int label = 0;
+    if (fg != ext) label = -1;
+    if (fg) label = num_class == 1 ? 1 : cls;
+    if (valid) labels[n] = (long long)label;
+    const int wave_cnt = __popcll(__ballot(valid && label > 0));
+    if (lane_id() == 0) s_cnt[threadIdx.x >> 6] = wave_cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (c) atomicAdd(num_pos, c);                                    // integer: order independent
+    }
+}
+
+__global__ void ph_clear_kernel(int *num_pos) { num_pos[0] = 0; }
+
+// get_cls_layer_loss: one thread per point over its num_class logits; the focal element is the anchor heads' (focal_el).
+// GRAD == false: per-block partial sums (slot 0 of the three block_sum3 carries).  GRAD == true: d loss / d logits, every
+// element written.
+template <bool GRAD>
+__global__ __launch_bounds__(256) void ph_loss_kernel(const void *__restrict__ logits, void *__restrict__ d_logits, int dtype,
+                                                      long long row_stride, const long long *__restrict__ labels,
+                                                      const int *__restrict__ num_pos, int N, int num_class, float cls_w,
+                                                      const float *__restrict__ grad_out, float *__restrict__ partials) {
+    __shared__ float s_red[12];
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    float l = 0.f;
+    if (n < N) {
+        const long long label = labels[n];
+        // cls_weights = ((label == 0) + (label > 0)) / clamp(pos, 1)          (:135-139)
+        const float w = label >= 0 ? 1.f / fmaxf((float)num_pos[0], 1.f) : 0.f;
+        const long long tcls = label > 0 ? label - 1 : -1;                     // the one-hot without its column 0 (:141-143)
+        float up = 0.f;
+        if (GRAD) up = grad_out[0] * w;
+        for (int j = 0; j < num_class; ++j) {
+            const long long off = (long long)n * row_stride + j;
+            if (label < 0) {
+                if (GRAD) store_el(d_logits, dtype, off, 0.f);
+                continue;
+            }
+            const float xv = load_el(logits, dtype, off);
+            const float t = ((long long)j == tcls) ? 1.f : 0.f;
+            if (!GRAD) l += focal_el<false>(xv, t) * w;
+            else store_el(d_logits, dtype, off, focal_el<true>(xv, t) * up * cls_w);
+        }
+    }
+    if (!GRAD) block_sum3(l, 0.f, 0.f, s_red, partials + (size_t)blockIdx.x * 3);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// RoI-aware pooling
+__device__ __forceinline__ int ra_voxel_index(float local, float d, float res, int out) {
+    // int((local + d / 2) / res) clamped to [0, out - 1]   (roiaware_pool3d_kernel.cu:60-70).  nan and every negative
+    // quotient give 0: the reference's unsigned compare would send a quotient <= -1 to out - 1, which local + d / 2 >=
+    // -MARGIN makes unreachable for a box wider than 1e-5 m per voxel
+    const float q = __fdiv_rn(local + d / 2.f, res);
+    if (!(q >= 1.f)) return 0;
+    return q < (float)out ? (int)q : out - 1;
+}
+
+__global__ __launch_bounds__(256) void ra_collect_kernel(const float *__restrict__ rois, const float *__restrict__ pts, int np, int ox,
+                                                         int oy, int oz, int mpv, int *__restrict__ lists) {
+    extern __shared__ int s_cnt[];                    // [ox * oy * oz]
+    __shared__ int s_vox[RA_COLLECT_PTS];
+    const int roi = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int nvox = ox * oy * oz;
+    const float *r = rois + (size_t)roi * 7;
+    const RaBox box = ra_prepare(r, RA_MARGIN_DEVICE);
+    const float dx = r[3], dy = r[4], dz = r[5];
+    const float x_res = __fdiv_rn(dx, (float)ox), y_res = __fdiv_rn(dy, (float)oy), z_res = __fdiv_rn(dz, (float)oz);
+    int *L = lists + (size_t)roi * nvox * mpv;
+    for (int v = tid; v < nvox; v += 256) s_cnt[v] = 0;
+    const u64 lower = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    for (int base = 0; base < np; base += RA_COLLECT_PTS) {
+#pragma unroll
+        for (int j = 0; j < RA_COLLECT_PTS / 256; ++j) {
+            const int k = base + j * 256 + tid;
+            int v = -1;
+            if (k < np) {
+                const float x = pts[(size_t)k * 3], y = pts[(size_t)k * 3 + 1], z = pts[(size_t)k * 3 + 2];
+                float lx, ly;
+                if (ra_point_in_box(box, x, y, z, lx, ly)) {
+                    const float lz = z - box.cz;
+                    v = (ra_voxel_index(lx, dx, x_res, ox) * oy + ra_voxel_index(ly, dy, y_res, oy)) * oz +
+                        ra_voxel_index(lz, dz, z_res, oz);
+                }
+            }
+            s_vox[j * 256 + tid] = v;
+        }
+        __syncthreads();
+        if (tid < 64) {
+            // wave 0 appends in point order: within a 64-point piece the lanes of one voxel are ranked by ballots
+            for (int k0 = 0; k0 < RA_COLLECT_PTS; k0 += 64) {
+                const int v = s_vox[k0 + lane];
+                u64 act = __ballot(v >= 0);
+                while (act) {
+                    const int leader = __ffsll((long long)act) - 1;
+                    const int lv = __shfl(v, leader, 64);
+                    const u64 same = __ballot(v == lv);
+                    const int have = s_cnt[lv];
+                    if (v == lv) {
+                        const int pos = have + __popcll(same & lower);
+                        if (pos < mpv - 1) L[(size_t)lv * mpv + pos + 1] = base + k0 + lane;
+                    }
+                    if (lane == leader) s_cnt[lv] = min(have + __popcll(same), mpv - 1);
+                    act &= ~same;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    for (int v = tid; v < nvox; v += 256) L[(size_t)v * mpv] = s_cnt[v];
+}
+
+// one thread per (voxel, channel), channel fastest
+template <bool AVG>
+__global__ __launch_bounds__(256) void ra_pool_kernel(const float *__restrict__ feat, const int *__restrict__ lists, int nvox, int C,
+                                                      int mpv, int np, float *__restrict__ pooled, int *__restrict__ argmax) {
+    const int roi = blockIdx.y;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)nvox * C) return;
+    const int v = (int)(i / C), c = (int)(i - (size_t)v * C);
+    const int *L = lists + ((size_t)roi * nvox + v) * mpv;
+    const int total = min(L[0], mpv - 1);
+    const size_t o = (size_t)roi * nvox * C + i;
+    if (AVG) {
+        float sum = 0.f;
+        for (int k = 1; k <= total; ++k) {
+            const int idx = L[k];
+            if ((unsigned)idx < (unsigned)np) sum += feat[(size_t)idx * C + c];
+        }
+        pooled[o] = total > 0 ? __fdiv_rn(sum, (float)total) : 0.f;
+    } else {
+        int arg = -1;
+        float mx = -INFINITY;                                            // (float)-1e50
+        for (int k = 1; k <= total; ++k) {
+            const int idx = L[k];
+            if ((unsigned)idx >= (unsigned)np) continue;
+            const float f = feat[(size_t)idx * C + c];
+            if (f > mx) {                                                // the first strict maximum in list order
+                mx = f;
+                arg = idx;
+            }
+        }
+        pooled[o] = arg != -1 ? mx : 0.f;
+        argmax[o] = arg;
+    }
+}
+
+// Backward, same thread layout: the lanes of a wave are consecutive channels of one voxel (C >= 64), so one atomic
+// instruction adds into contiguous runs of at most as many point rows as the voxel holds (avg: exactly one row).
+template <bool AVG>
+__global__ __launch_bounds__(256) void ra_pool_grad_kernel(const int *__restrict__ lists, const int *__restrict__ argmax,
+                                                           const float *__restrict__ grad_out, int nvox, int C, int mpv, int np,
+                                                           float *__restrict__ grad_in) {
+    const int roi = blockIdx.y;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)nvox * C) return;
+    const int v = (int)(i / C), c = (int)(i - (size_t)v * C);
+    const size_t o = (size_t)roi * nvox * C + i;
+    if (AVG) {
+        const int *L = lists + ((size_t)roi * nvox + v) * mpv;
+        const int total = min(L[0], mpv - 1);
+        if (total <= 0) return;
+        const float g = grad_out[o] * __fdiv_rn(1.f, fmaxf((float)total, 1.f));
+        for (int k = 1; k <= total; ++k) {
+            const int idx = L[k];
+            if ((unsigned)idx < (unsigned)np) atomicAdd(grad_in + (size_t)idx * C + c, g);
+        }
+    } else {
+        const int a = argmax[o];
+        if ((unsigned)a < (unsigned)np) atomicAdd(grad_in + (size_t)a * C + c, grad_out[o]);
+    }
+}
+
+bool pool_shape_ok(int num_rois, int ox, int oy, int oz, int channels, int mpv) {
+    if (num_rois < 0 || ox < 1 || oy < 1 || oz < 1 || channels < 1 || mpv < 2) return false;
+    if (ox > 255 || oy > 255 || oz > 255 || num_rois > 65535) return false;                   // (the reference: < 256)
+    const long long nvox = (long long)ox * oy * oz;
+    return nvox <= RA_MAX_VOXELS && nvox * channels < (1ll << 31) && nvox * mpv < (1ll << 31);
+}
+
+}  // namespace
+
+extern "C" int pcd_points_in_boxes_host(const float *boxes_host, int num_boxes, const float *pts_host, int num_pts,
+                                        int *out_host) {
+    if (num_boxes < 0 || num_pts < 0) return PCD_ERR_INVALID_ARG;
+    if (num_boxes == 0 || num_pts == 0) return PCD_OK;
+    if (!boxes_host || !pts_host || !out_host) return PCD_ERR_INVALID_ARG;
+    for (int i = 0; i < num_boxes; ++i) {
+        const RaBox b = ra_prepare(boxes_host + (size_t)i * 7, RA_MARGIN_HOST);
+        for (int j = 0; j < num_pts; ++j) {
+            const float *p = pts_host + (size_t)j * 3;
+            float lx, ly;
+            out_host[(size_t)i * num_pts + j] = ra_point_in_box(b, p[0], p[1], p[2], lx, ly) ? 1 : 0;
+        }
+    }
+    return PCD_OK;
+}
+
+extern "C" int pcd_points_in_boxes(const float *boxes, const float *pts, int batch, int num_boxes, int num_pts,
+                                   int *box_idx_of_pts, void *stream) {
+    PCD_ENTER();
+    if (batch < 0 || num_boxes < 0 || num_pts < 0) return PCD_ERR_INVALID_ARG;
+    if (batch == 0 || num_pts == 0) return PCD_OK;
+    if (!pts || !box_idx_of_pts || (num_boxes > 0 && !boxes)) return PCD_ERR_INVALID_ARG;
+    if (batch > 65535 || (long long)batch * num_pts * 3 >= (1ll << 31) || (long long)batch * num_boxes * 7 >= (1ll << 31))
+        return PCD_ERR_UNSUPPORTED;
+    dim3 grid((unsigned)pcd_div_up(num_pts, 256), (unsigned)batch);
+    ra_points_in_boxes_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(boxes, pts, num_boxes, num_pts, box_idx_of_pts);
+    PCD_RETURN_IF_LAUNCH_FAILED();
+    return PCD_OK;
+}
+
+extern "C" int pcd_point_head_assign_targets(const float *point_coords, int num_points, const float *gt_boxes, int batch,
+                                             int n_boxes, float extra_x, float extra_y, float extra_z, int num_class,
+                                             long long *point_cls_labels, int *num_pos, void *stream) {
+    PCD_ENTER();
+    if (num_points < 0 || batch < 1 || n_boxes < 0 || num_class < 1 || !num_pos) return PCD_ERR_INVALID_ARG;
+    if (num_points > 0 && (!point_coords || !point_cls_labels)) return PCD_ERR_INVALID_ARG;
+    if (n_boxes > 0 && !gt_boxes) return PCD_ERR_INVALID_ARG;
+    if ((long long)num_points * 4 >= (1ll << 31) || (long long)batch * n_boxes * 8 >= (1ll << 31)) return PCD_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    ph_clear_kernel<<<1, 1, 0, st>>>(num_pos);
+    if (num_points > 0)
+        ph_assign_kernel<<<pcd_div_up(num_points, 256), 256, 0, st>>>(point_coords, num_points, gt_boxes, batch, n_boxes, extra_x,
+                                                                      extra_y, extra_z, num_class, point_cls_labels, num_pos);
+    PCD_RETURN_IF_LAUNCH_FAILED();
+    return PCD_OK;
+}
+
+extern "C" size_t pcd_point_head_loss_workspace_bytes(int num_points) {
+    if (num_points < 0) return 0;
+    return ws_piece((size_t)(pcd_div_up(num_points, 256) + 1) * 3, sizeof(float));
+}
+
+static bool ph_loss_args_ok(const void *logits, int dtype, long long row_stride, const long long *labels, const int *num_pos,
+                            int num_points, int num_class) {
+    return logits && labels && num_pos && (dtype == PCD_F32 || dtype == PCD_BF16) && num_points >= 1 && num_class >= 1 &&
+           row_stride >= num_class;
+}
+
+extern "C" int pcd_point_head_loss_forward(const void *logits, int dtype, long long row_stride, const long long *point_cls_labels,
+                                           const int *num_pos, int num_points, int num_class, float cls_weight, float *out,
+                                           void *workspace, size_t workspace_bytes, void *stream) {
+    PCD_ENTER();
+    if (!ph_loss_args_ok(logits, dtype, row_stride, point_cls_labels, num_pos, num_points, num_class) || !out)
+        return PCD_ERR_INVALID_ARG;
+    WsCarver ws(workspace, workspace_bytes);
+    const int blocks = pcd_div_up(num_points, 256);
+    float *partials = ws.take<float>((size_t)(blocks + 1) * 3);
+    if (!ws.ok) return PCD_ERR_WORKSPACE;
+    AncLossCfg c = {};                                 // the anchor heads' ordered finish: sum * 1 * cls_w, no other terms
+    c.inv_batch = 1.f;
+    c.cls_w = cls_weight;
+    hipStream_t st = (hipStream_t)stream;
+    ph_loss_kernel<false><<<blocks, 256, 0, st>>>(logits, nullptr, dtype, row_stride, point_cls_labels, num_pos, num_points,
+                                                  num_class, cls_weight, nullptr, partials);
+    anc_loss_finish_kernel<<<1, 256, 0, st>>>(partials, blocks, c, out);
+    PCD_RETURN_IF_LAUNCH_FAILED();
+    return PCD_OK;
+}
+
+extern "C" int pcd_point_head_loss_backward(const void *logits, void *d_logits, int dtype, long long row_stride,
+                                            const long long *point_cls_labels, const int *num_pos, int num_points, int num_class,
+                                            float cls_weight, const float *grad_out, void *stream) {
+    PCD_ENTER();
+    if (!ph_loss_args_ok(logits, dtype, row_stride, point_cls_labels, num_pos, num_points, num_class) || !d_logits || !grad_out)
+        return PCD_ERR_INVALID_ARG;
+    ph_loss_kernel<true><<<pcd_div_up(num_points, 256), 256, 0, (hipStream_t)stream>>>(
+        logits, d_logits, dtype, row_stride, point_cls_labels, num_pos, num_points, num_class, cls_weight, grad_out, nullptr);
+    PCD_RETURN_IF_LAUNCH_FAILED();
+    return PCD_OK;
+}
+
+extern "C" int pcd_roiaware_pool3d_forward(const float *rois, int num_rois, const float *pts, int num_pts,
+                                           const float *pts_feature, int channels, int out_x, int out_y, int out_z,
+                                           int max_pts_each_voxel, int pool_method, int *pts_idx_of_voxels, int *argmax,
+                                           float *pooled_features, void *stream) {
+    PCD_ENTER();
+    if (num_pts < 0 || (pool_method != 0 && pool_method != 1)) return PCD_ERR_INVALID_ARG;
+    if (!pool_shape_ok(num_rois, out_x, out_y, out_z, channels, max_pts_each_voxel) || (long long)num_pts * channels >= (1ll << 31))
+        return PCD_ERR_UNSUPPORTED;
+    if (num_rois == 0) return PCD_OK;
+    if (!rois || !pts_idx_of_voxels || !pooled_features || (pool_method == 0 && !argmax) || (num_pts > 0 && (!pts || !pts_feature)))
+        return PCD_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int nvox = out_x * out_y * out_z;
+    pcd_fill(pts_idx_of_voxels, 0, (size_t)num_rois * nvox * max_pts_each_voxel * sizeof(int), st);
+    ra_collect_kernel<<<num_rois, 256, (size_t)nvox * sizeof(int), st>>>(rois, pts, num_pts, out_x, out_y, out_z, max_pts_each_voxel,
+                                                                         pts_idx_of_voxels);
+    dim3 grid((unsigned)(((size_t)nvox * channels + 255) / 256), (unsigned)num_rois);
+    if (pool_method == 0)
+        ra_pool_kernel<false><<<grid, 256, 0, st>>>(pts_feature, pts_idx_of_voxels, nvox, channels, max_pts_each_voxel, num_pts,
+                                                    pooled_features, argmax);
+    else
+        ra_pool_kernel<true><<<grid, 256, 0, st>>>(pts_feature, pts_idx_of_voxels, nvox, channels, max_pts_each_voxel, num_pts,
+                                                   pooled_features, nullptr);
+    PCD_RETURN_IF_LAUNCH_FAILED();
+    return PCD_OK;
+}
+
+extern "C" int pcd_roiaware_pool3d_backward(const int *pts_idx_of_voxels, const int *argmax, const float *grad_out, int num_rois,
+                                            int out_x, int out_y, int out_z, int channels, int max_pts_each_voxel,
+                                            int pool_method, int num_pts, float *grad_in, void *stream) {
+    PCD_ENTER();
+    if (num_pts < 0 || (pool_method != 0 && pool_method != 1)) return PCD_ERR_INVALID_ARG;
+    if (!pool_shape_ok(num_rois, out_x, out_y, out_z, channels, max_pts_each_voxel) || (long long)num_pts * channels >= (1ll << 31))
+        return PCD_ERR_UNSUPPORTED;
+    if (num_pts == 0) return PCD_OK;
+    if (!grad_in) return PCD_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    pcd_fill(grad_in, 0, (size_t)num_pts * channels * sizeof(float), st);
+    if (num_rois > 0) {
+        if (!grad_out || (pool_method == 0 ? !argmax : !pts_idx_of_voxels)) return PCD_ERR_INVALID_ARG;
+        const int nvox = out_x * out_y * out_z;
+        dim3 grid((unsigned)(((size_t)nvox * channels + 255) / 256), (unsigned)num_rois);
+        if (pool_method == 0)
+            ra_pool_grad_kernel<false><<<grid, 256, 0, st>>>(pts_idx_of_voxels, argmax, grad_out, nvox, channels, max_pts_each_voxel,
+                                                             num_pts, grad_in);
+        else
+            ra_pool_grad_kernel<true><<<grid, 256, 0, st>>>(pts_idx_of_voxels, argmax, grad_out, nvox, channels, max_pts_each_voxel,
+                                                            num_pts, grad_in);
+    }
+    PCD_RETURN_IF_LAUNCH_FAILED();
+    return PCD_OK;
+}

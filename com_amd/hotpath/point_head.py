@@ -1,0 +1,183 @@
+"""`PointHeadSimple` -- the keypoint segmentation head of PV-RCNN (pcdet/models/dense_heads/point_head_simple.py,
+point_head_template.py; `POINT_HEAD.NAME: PointHeadSimple` in tools/cfgs/waymo_models/pv_rcnn.yaml) as a registry
+drop-in: same constructor arguments, `cls_layers` built by `make_fc_layers` (a reference state dict loads with
+strict=True), `forward(batch_dict)` writes `point_cls_scores`, `assign_targets` and `get_loss(tb_dict)` keep their names
+and returns.  Target assignment and the loss run on the device (com_amd/csrc/roiaware.hip; C ABI `pcd_point_head_*`): one
+launch for the whole stacked batch instead of a host loop over frames with two points_in_boxes_gpu calls, boolean-mask
+indexing and `bs_mask.sum()` syncs each; no `.item()` -- `tb_dict` holds DEVICE scalars, and forward + get_loss + backward
+can sit in a captured graph with a fixed number of points.
+
+Scope: PointHeadSimple with set_ignore_flag targets.  PointHeadBox, PointIntraPartOffsetHead and targets with
+ret_box_labels / ret_part_labels / use_ball_constraint are refused at construction with a PcdError that names the key."""
+import torch
+import torch.nn as nn
+
+from .. import _lib as L
+from ._maps import dtype_code as _dt
+from .dense2d import _get
+
+
+def assign_targets(point_coords, gt_boxes, extra_width, num_class):
+    """pcd_point_head_assign_targets: (point_cls_labels int64 [N], num_pos int32 [1]) for point_coords [N, 4] rows of
+    (bs_idx, x, y, z) and gt_boxes [B, M, 8]; point_head_simple.py:21-48."""
+    if not point_coords.is_cuda or not gt_boxes.is_cuda:
+        raise L.PcdError("PointHeadSimple.assign_targets needs HIP device tensors (there is no CPU fallback)")
+    assert gt_boxes.shape.__len__() == 3, 'gt_boxes.shape=%s' % str(gt_boxes.shape)
+    assert point_coords.shape.__len__() in [2], 'points.shape=%s' % str(point_coords.shape)
+    if point_coords.shape[1] != 4 or gt_boxes.shape[2] != 8:
+        raise L.PcdError(f"PointHeadSimple.assign_targets: point_coords {tuple(point_coords.shape)}, gt_boxes "
+                         f"{tuple(gt_boxes.shape)}; want [N, 4] and [B, M, 8]")
+    pc, gt = point_coords.contiguous().float(), gt_boxes.contiguous().float()
+    n, b, m = int(pc.shape[0]), int(gt.shape[0]), int(gt.shape[1])
+    labels = torch.empty((n,), dtype=torch.int64, device=pc.device)
+    num_pos = torch.empty((1,), dtype=torch.int32, device=pc.device)
+    ex, ey, ez = (float(v) for v in extra_width)
+    L.check(L.lib().pcd_point_head_assign_targets(L.ptr(pc) if n else None, n, L.ptr(gt) if m else None, b, m, ex, ey, ez,
+                                                  int(num_class), L.ptr(labels) if n else None, L.ptr(num_pos), L.stream_ptr()),
+            "pcd_point_head_assign_targets")
+    return labels, num_pos
+
+
+class _PointClsLoss(torch.autograd.Function):
+    """get_cls_layer_loss through pcd_point_head_loss_forward / _backward: 2 + 1 launches."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, num_pos, num_class, cls_weight):
+        if not logits.is_cuda:
+            raise L.PcdError("PointHeadSimple.get_loss needs HIP device tensors (there is no CPU fallback)")
+        if logits.dim() != 2 or logits.shape[1] != num_class or logits.stride(1) != 1 or labels.shape[0] != logits.shape[0]:
+            raise L.PcdError(f"point head: logits {tuple(logits.shape)} / labels {tuple(labels.shape)}, want [N, {num_class}] rows")
+        n = int(logits.shape[0])
+        lib = L.lib()
+        out = torch.empty((4,), dtype=torch.float32, device=logits.device)
+        ws = torch.empty((max(int(lib.pcd_point_head_loss_workspace_bytes(n)), 256),), dtype=torch.uint8, device=logits.device)
+        L.check(lib.pcd_point_head_loss_forward(L.ptr(logits), _dt(logits), int(logits.stride(0)), L.ptr(labels), L.ptr(num_pos),
+                                                n, num_class, cls_weight, L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr()),
+                "pcd_point_head_loss_forward")
+        ctx.save_for_backward(logits, labels, num_pos)
+        ctx.meta = (num_class, cls_weight)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        logits, labels, num_pos = ctx.saved_tensors
+        num_class, cls_weight = ctx.meta
+        d = torch.empty_strided(logits.shape, logits.stride(), dtype=logits.dtype, device=logits.device)
+        g = g_loss.detach().to(torch.float32).reshape(1).contiguous()
+        L.check(L.lib().pcd_point_head_loss_backward(L.ptr(logits), L.ptr(d), _dt(logits), int(logits.stride(0)), L.ptr(labels),
+                                                     L.ptr(num_pos), int(logits.shape[0]), num_class, cls_weight, L.ptr(g),
+                                                     L.stream_ptr()), "pcd_point_head_loss_backward")
+        return d, None, None, None, None
+
+
+def point_cls_loss(point_cls_preds, point_cls_labels, num_pos, num_class, cls_weight):
+    """point_loss_cls (device scalar, differentiable in point_cls_preds [N, num_class], f32 or bf16)."""
+    if point_cls_preds.shape[0] == 0:
+        return point_cls_preds.float().sum() * float(cls_weight)
+    return _PointClsLoss.apply(point_cls_preds, point_cls_labels, num_pos, int(num_class), float(cls_weight))
+
+
+class PointHeadSimple(nn.Module):
+    """point_head_simple.py:7-91 + point_head_template.py (module docstring)."""
+
+    def __init__(self, num_class, input_channels, model_cfg, **kwargs):
+        super().__init__()
+        self.model_cfg = model_cfg
+        self.num_class = int(num_class)
+        self._refuse(model_cfg)
+        self.extra_width = tuple(float(v) for v in _get(_get(model_cfg, 'TARGET_CONFIG'), 'GT_EXTRA_WIDTH'))
+        if len(self.extra_width) != 3:
+            raise L.PcdError(f"PointHeadSimple: TARGET_CONFIG.GT_EXTRA_WIDTH needs 3 values, got {len(self.extra_width)}")
+        self.point_cls_weight = float(_get(_get(model_cfg, 'LOSS_CONFIG'), 'LOSS_WEIGHTS')['point_cls_weight'])
+        self.use_before_fusion = bool(_get(model_cfg, 'USE_POINT_FEATURES_BEFORE_FUSION', False))
+        self.forward_ret_dict = None
+        self.cls_layers = self.make_fc_layers(fc_cfg=_get(model_cfg, 'CLS_FC'), input_channels=input_channels,
+                                              output_channels=self.num_class)
+
+    @staticmethod
+    def _refuse(model_cfg):
+        """the configurations outside the scope of the kernels: a PcdError that names the key"""
+        def no(key, why):
+            raise L.PcdError(f"PointHeadSimple: {key} {why} is not supported by the HIP point head")
+        name = _get(model_cfg, 'NAME', 'PointHeadSimple')
+        if name != 'PointHeadSimple':
+            no('NAME', f"= {name!r}")
+        for key in ('PART_FC', 'REG_FC'):
+            if _get(model_cfg, key, None) is not None:
+                no(key, '(a box / part-offset branch)')
+        ta = _get(model_cfg, 'TARGET_CONFIG')
+        if ta is None or _get(ta, 'GT_EXTRA_WIDTH', None) is None:
+            no('TARGET_CONFIG.GT_EXTRA_WIDTH', 'missing')
+        if _get(ta, 'BOX_CODER', None) is not None:
+            no('TARGET_CONFIG.BOX_CODER', f"= {_get(ta, 'BOX_CODER')!r}")
+        for key in ('ret_box_labels', 'ret_part_labels', 'use_ball_constraint'):
+            for k in (key, key.upper()):
+                if _get(ta, k, False):
+                    no(f'TARGET_CONFIG.{k}', '= True')
+        lc = _get(model_cfg, 'LOSS_CONFIG')
+        lw = _get(lc, 'LOSS_WEIGHTS', None) if lc is not None else None
+        if lw is None or 'point_cls_weight' not in lw:
+            no('LOSS_CONFIG.LOSS_WEIGHTS.point_cls_weight', 'missing')
+        for key in ('point_box_weight', 'point_part_weight'):
+            if key in lw:
+                no(f'LOSS_CONFIG.LOSS_WEIGHTS.{key}', '(a box / part-offset loss)')
+
+    @staticmethod
+    def make_fc_layers(fc_cfg, input_channels, output_channels):
+        """point_head_template.py:35-47"""
+        fc_layers = []
+        c_in = input_channels
+        for k in range(0, fc_cfg.__len__()):
+            fc_layers.extend([
+                nn.Linear(c_in, fc_cfg[k], bias=False),
+                nn.BatchNorm1d(fc_cfg[k]),
+                nn.ReLU(),
+            ])
+            c_in = fc_cfg[k]
+        fc_layers.append(nn.Linear(c_in, output_channels, bias=True))
+        return nn.Sequential(*fc_layers)
+
+    def assign_targets(self, input_dict):
+        """point_head_simple.py:21-48: {'point_cls_labels': int64 [N], 'point_box_labels': None, 'point_part_labels':
+        None} + 'point_pos_num' (device int32 [1], what the loss normalises with)."""
+        labels, num_pos = assign_targets(input_dict['point_coords'], input_dict['gt_boxes'], self.extra_width, self.num_class)
+        return {'point_cls_labels': labels, 'point_box_labels': None, 'point_part_labels': None, 'point_pos_num': num_pos}
+
+    def get_cls_layer_loss(self, tb_dict=None):
+        """point_head_template.py:131-155; the tb_dict values are device scalars"""
+        f = self.forward_ret_dict
+        labels = f['point_cls_labels'].view(-1)
+        preds = f['point_cls_preds'].view(-1, self.num_class)
+        num_pos = f.get('point_pos_num')
+        if num_pos is None:                       # labels that did not come from assign_targets
+            num_pos = (labels > 0).sum().to(torch.int32).reshape(1)
+        point_loss_cls = point_cls_loss(preds, labels, num_pos, self.num_class, self.point_cls_weight)
+        if tb_dict is None:
+            tb_dict = {}
+        tb_dict.update({'point_loss_cls': point_loss_cls.detach(), 'point_pos_num': num_pos[0].float()})
+        return point_loss_cls, tb_dict
+
+    def get_loss(self, tb_dict=None):
+        """point_head_simple.py:50-56"""
+        tb_dict = {} if tb_dict is None else tb_dict
+        point_loss_cls, tb_dict_1 = self.get_cls_layer_loss()
+        point_loss = point_loss_cls
+        tb_dict.update(tb_dict_1)
+        return point_loss, tb_dict
+
+    def forward(self, batch_dict):
+        """point_head_simple.py:58-91"""
+        if self.use_before_fusion:
+            point_features = batch_dict['point_features_before_fusion']
+        else:
+            point_features = batch_dict['point_features']
+        point_cls_preds = self.cls_layers(point_features)  # (total_points, num_class)
+        ret_dict = {'point_cls_preds': point_cls_preds}
+        point_cls_scores = torch.sigmoid(point_cls_preds)
+        batch_dict['point_cls_scores'], _ = point_cls_scores.max(dim=-1)
+        if self.training:
+            targets_dict = self.assign_targets(batch_dict)
+            ret_dict['point_cls_labels'] = targets_dict['point_cls_labels']
+            ret_dict['point_pos_num'] = targets_dict['point_pos_num']
+        self.forward_ret_dict = ret_dict
+        return batch_dict

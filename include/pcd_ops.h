@@ -1245,6 +1245,66 @@ int pcd_sparse_conv_subm_window_f32(const void *x, int n_rows, int c_in, const v
                                     const int32_t *nbr, int nbr_stride, const int32_t *n_rows_dev, const void *plan,
                                     int c_out, void *y, float *y_f32, const void *addend, void *stream);
 
+/* ============================================================================================
+ * (f5) Point-in-box tests, RoI-aware pooling and the PointHeadSimple targets / loss -- replaces pcdet/ops/roiaware_pool3d
+ *      (binder src/roiaware_pool3d.cpp:172-177; kernels src/roiaware_pool3d_kernel.cu; Python callers
+ *      roiaware_pool3d_utils.py:9-107) and the host loops of pcdet/models/dense_heads/point_head_template.py.
+ *      Boxes are rows of 7 float32 (x, y, z, dx, dy, dz, heading); the arithmetic of the test is the reference's, step by
+ *      step (com_amd/csrc/roiaware_geom.h): z test first, cos / sin of -heading in float, the xy comparison in double.
+ *   pcd_points_in_boxes_host: points_in_boxes_cpu (roiaware_pool3d.cpp:121-168), which box_utils.remove_points_in_boxes3d
+ *                (box_utils.py:117-131) calls per frame inside the DataLoader workers of COMAug's database samplers
+ *                (datasets/augmentor/database_sampler_v2.py:538, database_sampler.py:458).  HOST pointers, synchronous,
+ *                touches no GPU state (safe in forked workers).  out_host = [num_boxes][num_pts] int32 0 / 1, every box
+ *                tested on its own (no first-match rule); MARGIN 1e-2.
+ *   pcd_points_in_boxes: points_in_boxes_gpu (roiaware_pool3d.cpp:98-118, roiaware_pool3d_kernel.cu:313-359).  boxes
+ *                [batch][num_boxes][7], pts [batch][num_pts][3]; box_idx_of_pts [batch][num_pts] int32 receives the LOWEST
+ *                index of a box that contains the point, -1 for a point in no box (every element written); MARGIN 1e-5.
+ *   pcd_point_head_assign_targets: PointHeadSimple.assign_targets (point_head_simple.py:21-48) = enlarge_box3d
+ *                (box_utils.py:187-200) + assign_stack_targets with set_ignore_flag (point_head_template.py:49-129) for the
+ *                whole stacked batch.  point_coords [num_points][4] rows of (bs_idx, x, y, z); gt_boxes [batch][n_boxes][8]
+ *                (7 box floats + class, zero rows = padding); extra_x / _y / _z = TARGET_CONFIG.GT_EXTRA_WIDTH, added to
+ *                dx, dy, dz of EVERY row (padding rows included, as the reference does).  point_cls_labels int64
+ *                [num_points]: the class of the first box that contains the point (1 when num_class == 1), -1 where
+ *                foreground XOR inside-any-enlarged-box, 0 otherwise.  *num_pos (device int32) = number of labels > 0
+ *                (integer atomics: deterministic).  No read-back: capturable.
+ *   pcd_point_head_loss_forward / _backward: get_cls_layer_loss (point_head_template.py:131-155):
+ *                SigmoidFocalClassificationLoss(alpha 0.25, gamma 2) over logits [num_points][num_class] (f32 or bf16, rows
+ *                row_stride elements apart) with weights ((label == 0) + (label > 0)) / max(*num_pos, 1), summed in a fixed
+ *                order (bit-reproducible) and multiplied by cls_weight.  out = 4 device floats: out[0] = out[1] = the loss,
+ *                out[2] = out[3] = 0 (the ordered finish pass of the anchor heads is reused).  backward: d_logits (layout
+ *                and dtype of logits, every element written) = *grad_out (device f32) x d loss / d logits.
+ *   pcd_roiaware_pool3d_forward: roiaware_pool3d_gpu (roiaware_pool3d.cpp:29-66).  rois [num_rois][7], pts [num_pts][3],
+ *                pts_feature [num_pts][channels] f32.  pts_idx_of_voxels int32 [num_rois][out_x][out_y][out_z]
+ *                [max_pts_each_voxel]: slot 0 = count, then the ASCENDING indices of the voxel's points, cut after
+ *                max_pts_each_voxel - 1 entries, unused slots 0 (every element written).  pool_method 0 = max: pooled_features
+ *                f32 [num_rois][out_x][out_y][out_z][channels] and argmax int32 (same shape) = first strict maximum in list
+ *                order, -1 / 0.0 for an empty voxel; 1 = avg: the sum in list order / count (argmax may be NULL).  No
+ *                [num_rois][num_pts] mask is allocated.  PCD_ERR_UNSUPPORTED: an out size above 255, more than 8192 voxels
+ *                per RoI, more than 65535 RoIs.
+ *   pcd_roiaware_pool3d_backward: roiaware_pool3d_gpu_backward (:68-96).  grad_in f32 [num_pts][channels] is cleared and
+ *                receives grad_out through argmax (max) or grad_out / max(count, 1) over the lists (avg).  Float atomics:
+ *                the order of the additions into one point's row is not fixed.
+ * ============================================================================================ */
+int pcd_points_in_boxes_host(const float *boxes_host, int num_boxes, const float *pts_host, int num_pts, int *out_host);
+int pcd_points_in_boxes(const float *boxes, const float *pts, int batch, int num_boxes, int num_pts, int *box_idx_of_pts,
+                        void *stream);
+int pcd_point_head_assign_targets(const float *point_coords, int num_points, const float *gt_boxes, int batch, int n_boxes,
+                                  float extra_x, float extra_y, float extra_z, int num_class, long long *point_cls_labels,
+                                  int *num_pos, void *stream);
+size_t pcd_point_head_loss_workspace_bytes(int num_points);
+int pcd_point_head_loss_forward(const void *logits, int dtype, long long row_stride, const long long *point_cls_labels,
+                                const int *num_pos, int num_points, int num_class, float cls_weight, float *out,
+                                void *workspace, size_t workspace_bytes, void *stream);
+int pcd_point_head_loss_backward(const void *logits, void *d_logits, int dtype, long long row_stride,
+                                 const long long *point_cls_labels, const int *num_pos, int num_points, int num_class,
+                                 float cls_weight, const float *grad_out, void *stream);
+int pcd_roiaware_pool3d_forward(const float *rois, int num_rois, const float *pts, int num_pts, const float *pts_feature,
+                                int channels, int out_x, int out_y, int out_z, int max_pts_each_voxel, int pool_method,
+                                int *pts_idx_of_voxels, int *argmax, float *pooled_features, void *stream);
+int pcd_roiaware_pool3d_backward(const int *pts_idx_of_voxels, const int *argmax, const float *grad_out, int num_rois, int out_x,
+                                 int out_y, int out_z, int channels, int max_pts_each_voxel, int pool_method, int num_pts,
+                                 float *grad_in, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
