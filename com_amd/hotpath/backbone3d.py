@@ -92,7 +92,7 @@ class _RulebookPrefetcher:
                     t.indice_dict["__subm_hint__"] = self._subm_hint(conv, unit, t)
                 rb, out_idx, out_shape = conv._rulebook(t)
                 t.indice_dict.pop("__subm_hint__", None)
-                if getattr(rb, "ready_event", None) is None:
+                if rb.ready_event is None:
                     built.append(rb)
                     self._window_plan(conv, rb)
                 if not conv.subm:
@@ -155,7 +155,7 @@ class _RulebookPrefetcher:
         """The window kernel's tile plan of a freshly built SubM rulebook (ops.subm_window_plan caches it on the rulebook),
         here on the rulebook stream: built by the first conv that uses it, it sat on the main chain (~30 us per level)."""
         from .. import ops, _lib as L
-        if not (conv.subm and tuple(conv.kernel_size) == (3, 3, 3) and getattr(rb, "order", None) == ops.ROWS_YXZ):
+        if not (conv.subm and tuple(conv.kernel_size) == (3, 3, 3) and rb.order == ops.ROWS_YXZ):
             return
         c = conv.out_channels
         bit = {64: 1, 32: 2, 16: 4, 128: 8}.get(c, 0)

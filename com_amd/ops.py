@@ -3,6 +3,7 @@
 Every function here calls the HIP library; nothing is computed in Python/torch except buffer
 allocation, the one host read-back of a data-dependent row count, and trivial views.
 """
+import collections
 import ctypes
 import math
 
@@ -128,14 +129,12 @@ class StaticPlan:
 
     def prepare(self, device):
         """Allocate the sticky flag (call BEFORE capturing: it must not live in a graph's private pool)."""
-        import torch
         if self.flag is None:
             self.flag = torch.zeros((2,), dtype=torch.int32, device=device)
             torch.cuda.current_stream().synchronize()
 
     def arm(self):
         """Enqueue the overflow check of every recorded count on the current stream (capturable)."""
-        import torch
         if not self.recorded:
             return
         if self.flag is None:
@@ -149,14 +148,12 @@ class StaticPlan:
                 last = n_dev.reshape(-1)[-1:]
                 tab.count[j] = last.data_ptr()
                 tab.cap[j] = int(cap)
-            import ctypes
             L.check(L.lib().pcd_static_overflow_check(ctypes.cast(ctypes.pointer(tab), ctypes.c_void_p), len(chunk),
                                                       L.ptr(self.flag), L.stream_ptr()), "pcd_static_overflow_check")
 
     def poll(self, wait=False):
         """Non-blocking overflow poll: returns True (overflow seen), False (clean) or None (no result yet).  The
         first call starts an async copy of the flag to pinned host memory; later calls read it once it landed."""
-        import torch
         if self.flag is None:
             return False
         if self._poll_event is None:
@@ -466,26 +463,32 @@ class Rulebook:
     pairs [K, 2, n_in], pair_num [K]: spconv's indice_pairs / indice_pair_num, canonical order.
     """
 
-    def __init__(self, subm, kvol, n_in, n_out, nbr_out, nbr_in, pairs, pair_num, out_indices, out_shape,
-                 ksize, stride, padding, dilation, n_in_dev=None, n_out_dev=None):
+    def __init__(self, *, subm, kvol, n_in, n_out, ksize, stride, padding, dilation, nbr_out=None, nbr_in=None, pairs=None,
+                 pair_num=None, out_indices=None, out_shape=None, n_in_dev=None, n_out_dev=None, rank=None, order=None,
+                 classes=None, implicit_pairs=False, nbr_out_packed=None, nbr_cls=None):
         self.subm, self.kvol, self.n_in, self.n_out = subm, kvol, n_in, n_out
         # device-side row counts (static-shape mode): n_in / n_out are then capacities
         self.n_in_dev, self.n_out_dev = n_in_dev, n_out_dev
-        self._nbr_out, self._finish_tables = nbr_out, None
-        self._nbr_in, self._pairs, self._pair_num = nbr_in, pairs, pair_num
+        self._nbr_out, self._nbr_in, self._pairs, self._pair_num = nbr_out, nbr_in, pairs, pair_num
+        self._finish_tables = None    # callable that completes `_nbr_out` (one launch): run by the first reader of `nbr_out`
         # compact tables of a strided rulebook (rulebook_conv(compact=True): pcd_rulebook_conv_cm_build_compact): what the training
         # step's kernels read; `nbr_out` / `nbr_in` are then expanded from them on first access (same values)
-        self.nbr_out_packed = None    # uint32 [kh * kw, n_out]: {first row : 29, kz presence : 3} per (ky, kx)
-        self.nbr_cls = None           # int32 [8, vcap]: entry (j-th usable offset of the class, permutation slot)
+        self.nbr_out_packed = nbr_out_packed    # uint32 [kh * kw, n_out]: {first row : 29, kz presence : 3} per (ky, kx)
+        self.nbr_cls = nbr_cls                  # int32 [8, vcap]: entry (j-th usable offset of the class, permutation slot)
         self.out_indices = out_indices
         self.out_shape = list(out_shape) if out_shape is not None else None
         self.ksize, self.stride, self.padding, self.dilation = ksize, stride, padding, dilation
-        self.rank = None          # RankMap of the output level (strided builds only)
-        self.order = None         # ROWS_* of the output rows when they are key-numbered (strided / rank-map builds)
-        self.classes = None       # (perm, vstart, vcap): input rows grouped by stride-parity class (strided, training)
+        self.rank = rank          # RankMap / ColumnMap of the output level (strided and rank-map builds)
+        self.order = order        # ROWS_* of the output rows when they are key-numbered (strided / rank-map builds)
+        self.classes = classes    # (perm, vstart, vcap): input rows grouped by stride-parity class (strided, training)
         # strided, training: built WITHOUT pair lists -- the weight gradient reads the pairs of offset k off the parity class
         # that can use k and nbr_in (pcd_sparse_conv_wgrad_classes); `pairs` / `pair_num` are derived on first access
-        self.implicit_pairs = False
+        self.implicit_pairs = implicit_pairs
+        self._win_plans = {}      # window-kernel tile plans of a SubM 3x3x3 rulebook by _plan_key() (subm_window_plan)
+        # a rulebook built ahead on another stream (the backbones' prefetcher): the event its consumers wait on, and the
+        # stream that has already done so
+        self.ready_event = None
+        self.joined_stream = None
 
     # nbr_out is the COMPLETE neighbour table.  A SubM rulebook of a level whose convs all run on window tiles is built without it
     # (rulebook_subm(..., window=, nbr_tables=False): the plan comes straight from the column map and only the columns of
@@ -568,9 +571,9 @@ class Rulebook:
             key = torch.where(valid, sw[:, 0, :], torch.full_like(sw[:, 0, :], 2 ** 31 - 1))
             order = torch.argsort(key, dim=1, stable=True)
             pairs = torch.gather(sw, 2, order.unsqueeze(1).expand(-1, 2, -1)).contiguous()
-        return Rulebook(False, self.kvol, self.n_out, self.n_in, self.nbr_in, self.nbr_out, pairs,
-                        self.pair_num, None, None, self.ksize, self.stride, self.padding, self.dilation,
-                        n_in_dev=self.n_out_dev, n_out_dev=self.n_in_dev)
+        return Rulebook(subm=False, kvol=self.kvol, n_in=self.n_out, n_out=self.n_in, nbr_out=self.nbr_in, nbr_in=self.nbr_out,
+                        pairs=pairs, pair_num=self.pair_num, ksize=self.ksize, stride=self.stride, padding=self.padding,
+                        dilation=self.dilation, n_in_dev=self.n_out_dev, n_out_dev=self.n_in_dev)
 
 
 def conv_out_shape(spatial_shape, ksize, stride, padding, dilation):
@@ -701,15 +704,33 @@ def rulebook_subm(indices, batch_size, spatial_shape, ksize=3, dilation=1, want_
             L.check(lib.pcd_rulebook_subm(L.ptr(indices), n, batch_size, L.host_i32(shp), L.host_i32(ks),
                                           L.host_i32(dl), L.ptr(nbr), L.ptr(pairs), L.ptr(pair_num), int(pad_pairs),
                                           L.ptr(n_dev), L.ptr(ws), ws.numel(), L.stream_ptr()), "pcd_rulebook_subm")
-    rb = Rulebook(True, K, n, n, nbr, None, pairs, pair_num, indices, shp, ks, [1, 1, 1],
-                  [k // 2 for k in ks], dl, n_in_dev=n_dev, n_out_dev=n_dev)
-    if rank is not None and rank.matches(indices, shp, ks):
-        rb.order = rank.order
-        rb.rank = rank
+    ranked = rank is not None and rank.matches(indices, shp, ks)
+    rb = Rulebook(subm=True, kvol=K, n_in=n, n_out=n, nbr_out=nbr, pairs=pairs, pair_num=pair_num, out_indices=indices,
+                  out_shape=shp, ksize=ks, stride=[1, 1, 1], padding=[k // 2 for k in ks], dilation=dl, n_in_dev=n_dev,
+                  n_out_dev=n_dev, rank=rank if ranked else None, order=rank.order if ranked else None)
     if win_plan is not None:
-        rb.__dict__.setdefault("_win_plans", {})[win_plan[0]] = win_plan[1]
+        rb._win_plans[win_plan[0]] = win_plan[1]
     rb._finish_tables = finish
     return rb
+
+
+CLS_TILE = 256
+IMPLICIT_STRIDED_PAIRS = True     # spconv layers build strided rulebooks without indice_pairs (rulebook_conv(pair_lists=False))
+COMPACT_STRIDED_TABLES = True     # ... and, under a static plan, with compact neighbour tables only (rulebook_conv(compact=True))
+
+# The two back ends of the strided build (C entry points): the flat one ranks the output rows over a bitmap of the output key
+# space; the column-map one derives the output level's ColumnMap from the input level's -- its calls carry the input map
+# behind the geometry and the output map behind out_indices, and no dilation / row order (1 / ROWS_YXZ by construction).
+_StridedEntries = collections.namedtuple("_StridedEntries", "count fill build")
+_FLAT_BUILD = _StridedEntries("pcd_rulebook_conv_count", "pcd_rulebook_conv_fill", "pcd_rulebook_conv_build")
+_COLMAP_BUILD = _StridedEntries("pcd_rulebook_conv_cm_count", "pcd_rulebook_conv_cm_fill", "pcd_rulebook_conv_cm_build")
+
+
+def _parity_classes(n, ncls, dev):
+    """(perm, vstart, vcap): buffers for the input rows of a strided conv grouped by stride-parity class, every class padded to
+    whole tiles of CLS_TILE rows."""
+    vcap = (n + CLS_TILE - 1) // CLS_TILE * CLS_TILE + ncls * CLS_TILE
+    return (torch.empty((vcap,), dtype=torch.int32, device=dev), torch.empty((ncls + 1,), dtype=torch.int32, device=dev), vcap)
 
 
 def rulebook_conv(indices, batch_size, spatial_shape, ksize, stride, padding, dilation=1, want_pairs=True,
@@ -733,27 +754,42 @@ def rulebook_conv(indices, batch_size, spatial_shape, ksize, stride, padding, di
                            _triple(spatial_shape))
     K = ks[0] * ks[1] * ks[2]
     lib = L.lib()
-    args = (L.host_i32(shp), L.host_i32(ks), L.host_i32(st), L.host_i32(pd), L.host_i32(dl))
+    geo = (L.host_i32(shp), L.host_i32(ks), L.host_i32(st), L.host_i32(pd))
     out_shape = conv_out_shape(shp, ks, st, pd, dl)
+    be = None
     if isinstance(in_rank, ColumnMap) and order == ROWS_YXZ and n > 0 and dl == [1, 1, 1] \
             and in_rank.serves(indices, shp, batch_size):
-        rb = _rulebook_conv_cm(indices, batch_size, shp, ks, st, pd, dl, want_pairs, pad_pairs, n_dev, plan_key, in_rank,
-                               out_shape, pair_lists, compact)
-        if rb is not None:
-            return rb
-    wsb = lib.pcd_rulebook_conv_workspace_bytes(n, batch_size, *args)
-    if wsb == 0:
-        raise L.PcdError("pcd_rulebook_conv: bad geometry or key space too large")
+        wsb = lib.pcd_rulebook_conv_cm_workspace_bytes(n, batch_size, *geo)
+        if wsb:                                  # (0: geometry outside what pcd_rulebook_conv_cm_* covers -> the flat build)
+            be = _COLMAP_BUILD
+            geo += (L.ptr(in_rank.buf), in_rank.buf.numel(), in_rank.cap)
+    if be is None:
+        be = _FLAT_BUILD
+        geo += (L.host_i32(dl),)
+        wsb = lib.pcd_rulebook_conv_workspace_bytes(n, batch_size, *geo)
+        if wsb == 0:
+            raise L.PcdError("pcd_rulebook_conv: bad geometry or key space too large")
+    cm = be is _COLMAP_BUILD
     ws = _ws(wsb, dev)
     n_out_dev = torch.empty((1,), dtype=torch.int32, device=dev)      # always written by the scan launch
     static = PLAN is not None and PLAN.active
     ncls = st[0] * st[1] * st[2]
-    classes = None
     lists = want_pairs and (pair_lists or ncls > 8 or K > 27)
+    want_classes = want_pairs and ncls <= 8      # training: input rows grouped by stride-parity class (dgrad_classes, wgrad)
+    head = (L.ptr(indices), n, batch_size, *geo)
+    tail = (L.ptr(ws), ws.numel(), L.stream_ptr()) + (() if cm else (int(order),))
 
-    def outputs(n_out):
-        return (torch.empty((n_out, 4), dtype=torch.int32, device=dev),
-                torch.empty((K, n), dtype=torch.int32, device=dev),
+    def level(n_out):
+        """out_indices and the C arguments of the output level's column map (column-map build)"""
+        out_indices = torch.empty((n_out, 4), dtype=torch.int32, device=dev)
+        if not cm:
+            return out_indices, None, ()
+        cmap = torch.empty((lib.pcd_colmap_bytes(batch_size, L.host_i32(out_shape), max(n_out, 1)),), dtype=torch.uint8,
+                           device=dev)
+        return out_indices, cmap, (L.ptr(cmap), cmap.numel())
+
+    def tables(n_out):
+        return (torch.empty((K, n), dtype=torch.int32, device=dev),
                 torch.empty((K, n_out), dtype=torch.int32, device=dev),
                 torch.empty((K, 2, n), dtype=torch.int32, device=dev) if lists else None,
                 torch.empty((K,), dtype=torch.int32, device=dev) if lists else None)
@@ -762,30 +798,43 @@ def rulebook_conv(indices, batch_size, spatial_shape, ksize, stride, padding, di
         p_ = int((nbr_in >= 0).sum().item())
         return dict(bytes=16 * n + 8 * p_ + 16 * n_out, flops=0, rows=n_out, pairs=p_)
 
+    classes = packed = cls_tab = None
     if static and n > 0:
         # capacity known on the host: both phases and the parity classes in one call, nothing read back
         n_out = PLAN.cap(plan_key)
         PLAN.record(plan_key, n_out_dev, n_out)
-        out_indices, nbr_in, nbr_out, pairs, pair_num = outputs(n_out)
-        perm = vstart = None
-        vcap = 0
-        if want_pairs and ncls <= 8:
-            vcap = (n + CLS_TILE - 1) // CLS_TILE * CLS_TILE + ncls * CLS_TILE
-            perm = torch.empty((vcap,), dtype=torch.int32, device=dev)
-            vstart = torch.empty((ncls + 1,), dtype=torch.int32, device=dev)
-            classes = (perm, vstart, vcap)
-        with _Timed("rulebook_conv_build", meta):
-            L.check(lib.pcd_rulebook_conv_build(L.ptr(indices), n, batch_size, *args, n_out, L.ptr(n_out_dev),
-                                                L.ptr(out_indices), L.ptr(nbr_in), L.ptr(nbr_out), L.ptr(pairs),
-                                                L.ptr(pair_num), int(pad_pairs), CLS_TILE, L.ptr(perm), vcap,
-                                                L.ptr(vstart), L.ptr(n_dev), L.ptr(ws), ws.numel(), L.stream_ptr(),
-                                                int(order)),
-                    "pcd_rulebook_conv_build")
+        out_indices, cmap, omap = level(n_out)
+        if want_classes:
+            classes = _parity_classes(n, ncls, dev)
+        perm, vstart, vcap = classes or (None, None, 0)
+        # (compact: 8 table rows -- every parity class must get by with at most 8 usable offsets)
+        if cm and compact and want_classes and not lists and ks[0] == 3 \
+                and math.prod(-(-ks[d] // st[d]) for d in range(3)) <= 8:
+            nbr_in = nbr_out = pairs = pair_num = None
+            packed = torch.empty((ks[1] * ks[2], n_out), dtype=torch.int32, device=dev)
+            cls_tab = torch.empty((8, vcap), dtype=torch.int32, device=dev)
+
+            def meta_c():                          # pairs = presence bits of the packed table (rows beyond the count hold 0)
+                m_ = (packed >> 29) & 7
+                p_ = int(((m_ & 1) + ((m_ >> 1) & 1) + ((m_ >> 2) & 1)).sum().item())
+                return dict(bytes=16 * n + 8 * p_ + 16 * n_out, flops=0, rows=n_out, pairs=p_)
+
+            with _Timed("rulebook_conv_build", meta_c):
+                L.check(lib.pcd_rulebook_conv_cm_build_compact(*head, n_out, L.ptr(n_out_dev), L.ptr(out_indices), *omap,
+                                                               L.ptr(packed), L.ptr(cls_tab), CLS_TILE, L.ptr(perm), vcap,
+                                                               L.ptr(vstart), L.ptr(n_dev), *tail),
+                        "pcd_rulebook_conv_cm_build_compact")
+        else:
+            nbr_in, nbr_out, pairs, pair_num = tables(n_out)
+            with _Timed("rulebook_conv_build", meta):
+                L.check(getattr(lib, be.build)(*head, n_out, L.ptr(n_out_dev), L.ptr(out_indices), *omap, L.ptr(nbr_in),
+                                               L.ptr(nbr_out), L.ptr(pairs), L.ptr(pair_num), int(pad_pairs), CLS_TILE,
+                                               L.ptr(perm), vcap, L.ptr(vstart), L.ptr(n_dev), *tail), be.build)
     else:
         with _Timed("rulebook_conv_count", lambda: dict(bytes=0, flops=0, rows=n, pairs=0)):
-            L.check(lib.pcd_rulebook_conv_count(L.ptr(indices), n, batch_size, *args, L.ptr(n_out_dev), L.ptr(n_dev),
-                                                L.ptr(ws), ws.numel(), L.stream_ptr(), int(order)),
-                    "pcd_rulebook_conv_count")
+            # (the column-map count reads the input level's map, not its rows)
+            counted = (n, batch_size, *geo, L.ptr(n_out_dev)) if cm else (*head, L.ptr(n_out_dev), L.ptr(n_dev))
+            L.check(getattr(lib, be.count)(*counted, *tail), be.count)
         if static:
             n_out = PLAN.cap(plan_key)         # capacity; the real count stays in n_out_dev (no host sync)
             PLAN.record(plan_key, n_out_dev, n_out)
@@ -793,182 +842,57 @@ def rulebook_conv(indices, batch_size, spatial_shape, ksize, stride, padding, di
             n_out = int(n_out_dev.item())      # host sync: data-dependent number of output rows
             if PLAN is not None and plan_key is not None:
                 PLAN.observe(plan_key, n_out)
-        out_indices, nbr_in, nbr_out, pairs, pair_num = outputs(n_out)
-        with _Timed("rulebook_conv_fill", meta):
-            L.check(lib.pcd_rulebook_conv_fill(L.ptr(indices), n, batch_size, *args, n_out, L.ptr(out_indices),
-                                               L.ptr(nbr_in), L.ptr(nbr_out), L.ptr(pairs), L.ptr(pair_num),
-                                               int(pad_pairs), L.ptr(n_dev), L.ptr(ws), ws.numel(), L.stream_ptr(),
-                                               int(order)),
-                    "pcd_rulebook_conv_fill")
-    rb = Rulebook(False, K, n, n_out, nbr_out, nbr_in, pairs, pair_num, out_indices, out_shape, ks, st,
-                  pd, dl, n_in_dev=n_dev, n_out_dev=n_out_dev if static else None)
-    # the build's bitmap + prefix stay valid as long as `ws` lives: a SubM conv on out_indices can rank with them
-    import ctypes
-    boff, poff, nwords = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
-    L.check(lib.pcd_rulebook_conv_rank_layout(n, batch_size, *args, ctypes.byref(boff), ctypes.byref(poff),
-                                              ctypes.byref(nwords)), "pcd_rulebook_conv_rank_layout")
-    nw = int(nwords.value)
-    rb.rank = RankMap(ws, ws[boff.value:boff.value + 4 * nw].view(torch.int32),
-                      ws[poff.value:poff.value + 4 * nw].view(torch.int32), out_indices, out_shape, 1, order)
-    rb.order = order
-    rb.implicit_pairs = want_pairs and not lists
-    if classes is not None:
-        rb.classes = classes
-    elif want_pairs and ncls <= 8:
-        # training: input rows grouped by stride-parity class for the data gradient (dgrad_classes)
-        vcap = (n + CLS_TILE - 1) // CLS_TILE * CLS_TILE + ncls * CLS_TILE
-        perm = torch.empty((vcap,), dtype=torch.int32, device=dev)
-        vstart = torch.empty((ncls + 1,), dtype=torch.int32, device=dev)
-        cws = _ws(lib.pcd_rulebook_conv_classes_workspace_bytes(n), dev)
-        with _Timed("rulebook_conv_classes", lambda: dict(bytes=0, flops=0, rows=n, pairs=0)):
-            L.check(lib.pcd_rulebook_conv_classes(L.ptr(indices), n, L.host_i32(st), L.host_i32(pd), CLS_TILE,
-                                                  L.ptr(perm), vcap, L.ptr(vstart), L.ptr(n_dev), L.ptr(cws),
-                                                  cws.numel(), L.stream_ptr()), "pcd_rulebook_conv_classes")
-        rb.classes = (perm, vstart, vcap)
-    return rb
-
-
-CLS_TILE = 256
-IMPLICIT_STRIDED_PAIRS = True     # spconv layers build strided rulebooks without indice_pairs (rulebook_conv(pair_lists=False))
-COMPACT_STRIDED_TABLES = True     # ... and, under a static plan, with compact neighbour tables only (rulebook_conv(compact=True))
-
-
-def _rulebook_conv_cm(indices, batch_size, shp, ks, st, pd, dl, want_pairs, pad_pairs, n_dev, plan_key, in_rank, out_shape,
-                      pair_lists=True, compact=False):
-    """rulebook_conv through the column maps (None: geometry outside what pcd_rulebook_conv_cm_* covers)."""
-    PLAN = current_plan()
-    lib = L.lib()
-    dev = indices.device
-    n = indices.shape[0]
-    K = ks[0] * ks[1] * ks[2]
-    geo = (L.host_i32(shp), L.host_i32(ks), L.host_i32(st), L.host_i32(pd))
-    wsb = lib.pcd_rulebook_conv_cm_workspace_bytes(n, batch_size, *geo)
-    if wsb == 0:
-        return None
-    ws = _ws(wsb, dev)
-    n_out_dev = torch.empty((1,), dtype=torch.int32, device=dev)
-    static = PLAN is not None and PLAN.active
-    ncls = st[0] * st[1] * st[2]
-    inmap = (L.ptr(in_rank.buf), in_rank.buf.numel(), in_rank.cap)
-    lists = want_pairs and (pair_lists or ncls > 8 or K > 27)
-
-    def outputs(n_out):
-        cmb = lib.pcd_colmap_bytes(batch_size, L.host_i32(out_shape), max(n_out, 1))
-        return (torch.empty((n_out, 4), dtype=torch.int32, device=dev),
-                torch.empty((K, n), dtype=torch.int32, device=dev),
-                torch.empty((K, n_out), dtype=torch.int32, device=dev),
-                torch.empty((K, 2, n), dtype=torch.int32, device=dev) if lists else None,
-                torch.empty((K,), dtype=torch.int32, device=dev) if lists else None,
-                torch.empty((cmb,), dtype=torch.uint8, device=dev))
-
-    def meta():                                  # SURVEY 8d: read 16 N_in, write 8 P + 16 N_out
-        p_ = int((nbr_in >= 0).sum().item())
-        return dict(bytes=16 * n + 8 * p_ + 16 * n_out, flops=0, rows=n_out, pairs=p_)
-
-    classes = None
-    packed = cls_tab = None
-    # (compact: 8 table rows -- every parity class must get by with at most 8 usable offsets)
-    if static and compact and want_pairs and not lists and ks[0] == 3 and ncls <= 8 \
-            and math.prod(-(-ks[d] // st[d]) for d in range(3)) <= 8:
-        n_out = PLAN.cap(plan_key)
-        PLAN.record(plan_key, n_out_dev, n_out)
-        cmb = lib.pcd_colmap_bytes(batch_size, L.host_i32(out_shape), max(n_out, 1))
-        out_indices = torch.empty((n_out, 4), dtype=torch.int32, device=dev)
-        cmap = torch.empty((cmb,), dtype=torch.uint8, device=dev)
-        nbr_in = nbr_out = pairs = pair_num = None
-        vcap = (n + CLS_TILE - 1) // CLS_TILE * CLS_TILE + ncls * CLS_TILE
-        perm = torch.empty((vcap,), dtype=torch.int32, device=dev)
-        vstart = torch.empty((ncls + 1,), dtype=torch.int32, device=dev)
-        classes = (perm, vstart, vcap)
-        packed = torch.empty((ks[1] * ks[2], n_out), dtype=torch.int32, device=dev)
-        cls_tab = torch.empty((8, vcap), dtype=torch.int32, device=dev)
-
-        def meta_c():                              # pairs = presence bits of the packed table (rows beyond the count hold 0)
-            m_ = (packed >> 29) & 7
-            p_ = int(((m_ & 1) + ((m_ >> 1) & 1) + ((m_ >> 2) & 1)).sum().item())
-            return dict(bytes=16 * n + 8 * p_ + 16 * n_out, flops=0, rows=n_out, pairs=p_)
-
-        with _Timed("rulebook_conv_build", meta_c):
-            L.check(lib.pcd_rulebook_conv_cm_build_compact(L.ptr(indices), n, batch_size, *geo, *inmap, n_out, L.ptr(n_out_dev),
-                                                           L.ptr(out_indices), L.ptr(cmap), cmap.numel(), L.ptr(packed),
-                                                           L.ptr(cls_tab), CLS_TILE, L.ptr(perm), vcap, L.ptr(vstart), L.ptr(n_dev),
-                                                           L.ptr(ws), ws.numel(), L.stream_ptr()),
-                    "pcd_rulebook_conv_cm_build_compact")
-    elif static:
-        n_out = PLAN.cap(plan_key)
-        PLAN.record(plan_key, n_out_dev, n_out)
-        out_indices, nbr_in, nbr_out, pairs, pair_num, cmap = outputs(n_out)
-        perm = vstart = None
-        vcap = 0
-        if want_pairs and ncls <= 8:
-            vcap = (n + CLS_TILE - 1) // CLS_TILE * CLS_TILE + ncls * CLS_TILE
-            perm = torch.empty((vcap,), dtype=torch.int32, device=dev)
-            vstart = torch.empty((ncls + 1,), dtype=torch.int32, device=dev)
-            classes = (perm, vstart, vcap)
-        with _Timed("rulebook_conv_build", meta):
-            L.check(lib.pcd_rulebook_conv_cm_build(L.ptr(indices), n, batch_size, *geo, *inmap, n_out, L.ptr(n_out_dev),
-                                                   L.ptr(out_indices), L.ptr(cmap), cmap.numel(), L.ptr(nbr_in),
-                                                   L.ptr(nbr_out), L.ptr(pairs), L.ptr(pair_num), int(pad_pairs), CLS_TILE,
-                                                   L.ptr(perm), vcap, L.ptr(vstart), L.ptr(n_dev), L.ptr(ws), ws.numel(),
-                                                   L.stream_ptr()), "pcd_rulebook_conv_cm_build")
-    else:
-        with _Timed("rulebook_conv_count", lambda: dict(bytes=0, flops=0, rows=n, pairs=0)):
-            L.check(lib.pcd_rulebook_conv_cm_count(n, batch_size, *geo, *inmap, L.ptr(n_out_dev), L.ptr(ws), ws.numel(),
-                                                   L.stream_ptr()), "pcd_rulebook_conv_cm_count")
-        n_out = int(n_out_dev.item())          # host sync: data-dependent number of output rows
-        if PLAN is not None and plan_key is not None:
-            PLAN.observe(plan_key, n_out)
-        out_indices, nbr_in, nbr_out, pairs, pair_num, cmap = outputs(n_out)
-        if n_out > 0:
-            with _Timed("rulebook_conv_fill", meta):
-                L.check(lib.pcd_rulebook_conv_cm_fill(L.ptr(indices), n, batch_size, *geo, *inmap, n_out, L.ptr(out_indices),
-                                                      L.ptr(cmap), cmap.numel(), L.ptr(nbr_in), L.ptr(nbr_out), L.ptr(pairs),
-                                                      L.ptr(pair_num), int(pad_pairs), L.ptr(n_dev), L.ptr(ws), ws.numel(),
-                                                      L.stream_ptr()), "pcd_rulebook_conv_cm_fill")
-        else:
+        out_indices, cmap, omap = level(n_out)
+        nbr_in, nbr_out, pairs, pair_num = tables(n_out)
+        if cm and n_out == 0:                  # (no output level to map: nothing to launch)
             nbr_in.fill_(-1)
             if pair_num is not None:
                 pair_num.zero_()
-    rb = Rulebook(False, K, n, n_out, nbr_out, nbr_in, pairs, pair_num, out_indices, out_shape, ks, st, pd, dl,
-                  n_in_dev=n_dev, n_out_dev=n_out_dev if static else None)
-    rb.rank = ColumnMap(cmap, max(n_out, 1), out_indices, out_shape, batch_size) if n_out > 0 else None
-    rb.order = ROWS_YXZ
-    rb.implicit_pairs = want_pairs and not lists
+        else:
+            with _Timed("rulebook_conv_fill", meta):
+                L.check(getattr(lib, be.fill)(*head, n_out, L.ptr(out_indices), *omap, L.ptr(nbr_in), L.ptr(nbr_out),
+                                              L.ptr(pairs), L.ptr(pair_num), int(pad_pairs), L.ptr(n_dev), *tail), be.fill)
+    if cm:
+        rank = ColumnMap(cmap, max(n_out, 1), out_indices, out_shape, batch_size) if n_out > 0 else None
+    else:
+        # the build's bitmap + prefix stay valid as long as `ws` lives: a SubM conv on out_indices can rank with them
+        boff, poff, nwords = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        L.check(lib.pcd_rulebook_conv_rank_layout(n, batch_size, *geo, ctypes.byref(boff), ctypes.byref(poff),
+                                                  ctypes.byref(nwords)), "pcd_rulebook_conv_rank_layout")
+        nw = int(nwords.value)
+        rank = RankMap(ws, ws[boff.value:boff.value + 4 * nw].view(torch.int32),
+                       ws[poff.value:poff.value + 4 * nw].view(torch.int32), out_indices, out_shape, 1, order)
+    rb = Rulebook(subm=False, kvol=K, n_in=n, n_out=n_out, nbr_out=nbr_out, nbr_in=nbr_in, pairs=pairs, pair_num=pair_num,
+                  out_indices=out_indices, out_shape=out_shape, ksize=ks, stride=st, padding=pd, dilation=dl, n_in_dev=n_dev,
+                  n_out_dev=n_out_dev if static else None, rank=rank, order=order, classes=classes,
+                  implicit_pairs=want_pairs and not lists, nbr_out_packed=packed, nbr_cls=cls_tab)
     if packed is not None:
-        rb.nbr_out_packed, rb.nbr_cls = packed, cls_tab
-        kq = ks[1] * ks[2]
-
         def finish():
             rb._nbr_out = torch.empty((K, n_out), dtype=torch.int32, device=dev)
-            L.check(lib.pcd_rulebook_conv_expand_nbr_out(L.ptr(packed), kq, n_out, L.ptr(n_out_dev), L.ptr(rb._nbr_out),
-                                                         L.stream_ptr()), "pcd_rulebook_conv_expand_nbr_out")
+            L.check(lib.pcd_rulebook_conv_expand_nbr_out(L.ptr(packed), ks[1] * ks[2], n_out, L.ptr(n_out_dev),
+                                                         L.ptr(rb._nbr_out), L.stream_ptr()), "pcd_rulebook_conv_expand_nbr_out")
         rb._finish_tables = finish
-    if rb.rank is not None:
+    if cm and rank is not None:
         # columns <= the map's column capacity?  (a geometry whose output z range does not cover every input z -- pad_z 0, k 3, s 2
         # on an even depth -- numbers output columns that have no rows: more columns than rows are then possible, and the capacity is
         # sized by rows; columns beyond it would be lost silently)
-        cnts, ncol_cap = rb.rank.counts()
+        cnts, ncol_cap = rank.counts()
         if static:
             PLAN.record(("columns",) + tuple(plan_key if isinstance(plan_key, tuple) else (plan_key,)), cnts[0:1], ncol_cap)
         elif int(cnts[0].item()) > ncol_cap:
             raise L.PcdError(f"column map of the output level: {int(cnts[0].item())} columns > capacity {ncol_cap} "
                              "(output z range does not cover the input: use the flat build, order=ROWS_ZYX, for this geometry)")
-    if classes is not None:
-        rb.classes = classes
-    elif want_pairs and ncls <= 8:
-        vcap = (n + CLS_TILE - 1) // CLS_TILE * CLS_TILE + ncls * CLS_TILE
-        perm = torch.empty((vcap,), dtype=torch.int32, device=dev)
-        vstart = torch.empty((ncls + 1,), dtype=torch.int32, device=dev)
+    if want_classes and classes is None:
+        # (two-phase build: the parity classes in a pass of their own)
+        rb.classes = perm, vstart, vcap = _parity_classes(n, ncls, dev)
         cws = _ws(lib.pcd_rulebook_conv_classes_workspace_bytes(n), dev)
         with _Timed("rulebook_conv_classes", lambda: dict(bytes=0, flops=0, rows=n, pairs=0)):
             L.check(lib.pcd_rulebook_conv_classes(L.ptr(indices), n, L.host_i32(st), L.host_i32(pd), CLS_TILE,
                                                   L.ptr(perm), vcap, L.ptr(vstart), L.ptr(n_dev), L.ptr(cws),
                                                   cws.numel(), L.stream_ptr()), "pcd_rulebook_conv_classes")
-        rb.classes = (perm, vstart, vcap)
     return rb
 
 
-import os as _os
 BN_FUSED_MID = True       # fold the BatchNorm "mid" reduction into the conv launches
 _BN_COUNTER_POOL = {}     # device -> [int32 zeros [slots * 16], next slot]     (eager launches)
 _BN_CAPTURE_BLOCK = {}    # (device, stream) -> [capture id, int32 zeros, next slot]   (launches recorded into a hipGraph)
@@ -977,7 +901,6 @@ _BN_CAPTURE_SLOTS = 128    # slots per captured block (a training step takes ~45
 
 
 def _capture_id():
-    import ctypes
     cid = ctypes.c_ulonglong(0)
     L.check(L.lib().pcd_stream_capture_id(L.stream_ptr(), ctypes.byref(cid)), "pcd_stream_capture_id")
     return int(cid.value)
@@ -1025,6 +948,8 @@ class BnReduce:
         self.mode, self.relu = mode, bool(relu)
         self.x, self.y, self.mean, self.invstd = x, y, mean, invstd
         self.partial, self.rows = None, 0
+        # BN_FUSED_MID: the conv's own partial rows (their count, the tensor), `partial` / `rows` being the folded mid rows
+        self.partial_rows, self.partial_keep = 0, None
 
     def usable(self, c_out, out_dtype):
         if out_dtype != torch.bfloat16:
@@ -1055,19 +980,19 @@ class BnReduce:
         return True
 
     def _struct(self, tiles, c_out, device):
-        self.partial = torch.empty((max(tiles, 1), 2, c_out), dtype=torch.float32, device=device)
+        self.partial = own = torch.empty((max(tiles, 1), 2, c_out), dtype=torch.float32, device=device)
         self.rows = tiles
+        self.partial_rows, self.partial_keep = 0, None
         mid = counters = None
         if BN_FUSED_MID and tiles > 0:
             # the conv launch also folds its partial rows into the 16 rows the BatchNorm apply pass starts from
             # (no bn_mid launch between the conv and the apply pass): hand `mid` on as the "partials"
             mid = torch.empty((L.BN_MID_ROWS, 2, c_out), dtype=torch.float64, device=device)
             counters = _bn_counters(device)
-            self.partial_rows, self.partial_keep = tiles, self.partial
+            self.partial_rows, self.partial_keep = tiles, own
             self.partial, self.rows = mid, L.BN_EXT_MID
         return L.PcdBnReduce(self.mode, int(self.relu), L.ptr(self.x), L.ptr(self.y), L.ptr(self.mean),
-                             L.ptr(self.invstd), L.ptr(self.partial_keep if mid is not None else self.partial), tiles,
-                             L.ptr(mid), L.ptr(counters))
+                             L.ptr(self.invstd), L.ptr(own), tiles, L.ptr(mid), L.ptr(counters))
 
 
 def _tiles(v, what):
@@ -1077,7 +1002,6 @@ def _tiles(v, what):
 
 
 def _byref(struct):
-    import ctypes
     return ctypes.cast(ctypes.pointer(struct), ctypes.c_void_p) if struct is not None else None
 
 
@@ -1245,7 +1169,7 @@ def subm_window_plan(rb, c_in, c_out):
     size: every conv of the indice_key, forward and backward, shares it."""
     T = _plan_key(c_in, c_out)
     assert T[0] > 0 and rb.subm and rb.kvol == 27
-    cache = rb.__dict__.setdefault("_win_plans", {})
+    cache = rb._win_plans
     if T not in cache:
         lib = L.lib()
         n = rb.nbr_out.shape[1]                  # (a plan of another tile size than the one the build made: from the table)
@@ -1341,17 +1265,38 @@ def subm_window_wgrad(x, dy, rb, out=None, defer=None, cin=None):
         L.check(lib.pcd_sparse_conv_subm_window_wgrad(L.ptr(x), L.ptr(dy), n, c, L.ptr(rb.nbr_buffer), rb.nbr_buffer.shape[1],
                                                       L.ptr(rb.n_out_dev), L.ptr(plan), L.ptr(slab), slab.numel(),
                                                       L.stream_ptr()), "pcd_sparse_conv_subm_window_wgrad")
-    job = (slab, dw, 27, c, c, 0, splits, 0, 0, cin if cin < c else 0)
-    if defer is not None:
-        defer.append(job)
-    else:
-        wgrad_reduce_batched([job])
-    return dw
+    return _reduce_or_defer(WgradJob(slab, dw, kvol=27, cin=c, cout=c, pmax=0, splits=splits,
+                                     cin_write=cin if cin < c else 0), defer)
 
 
 def _usable_out(out, numel):
     return (out is not None and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == numel
             and out.is_cuda)
+
+
+# One slab reduction of a weight gradient (C ABI: PcdWgradReduceJob, same fields): `workspace` holds the partial sums the MFMA
+# kernel left -- `splits` > 0: that many whole dW slabs; 0: the per-tile partials of the pair kernels over `pmax` pairs.
+WgradJob = collections.namedtuple("WgradJob", "workspace dweight kvol cin cout pmax splits layout cout_write cin_write",
+                                  defaults=(0, 0, 0, 0))
+
+
+def _wgrad_job_struct(job):
+    if not isinstance(job, WgradJob):
+        job = WgradJob(*job)
+    return L.PcdWgradReduceJob(L.ptr(job.workspace), L.ptr(job.dweight), *job[2:])
+
+
+def _reduce_or_defer(job, defer):
+    """The common end of the weight-gradient launches: the reduction of `job` joins the list `defer`, or runs now (whole slabs
+    through the batched entry, the pair kernels' partials through pcd_sparse_conv_wgrad_reduce).  Returns dW."""
+    if defer is not None:
+        defer.append(job)
+    elif job.splits:
+        wgrad_reduce_batched([job])
+    else:
+        L.check(L.lib().pcd_sparse_conv_wgrad_reduce(job.kvol, job.cin, job.cout, job.pmax, L.ptr(job.dweight),
+                                                     L.ptr(job.workspace), L.stream_ptr()), "pcd_sparse_conv_wgrad_reduce")
+    return job.dweight
 
 
 WGRAD_OS = True      # 16-output-channel layers: output-stationary kernel over nbr_out (pcd_sparse_conv_wgrad_os)
@@ -1392,89 +1337,68 @@ def wgrad(x, cin, dy, pairs, pair_num, kvol, out=None, defer=None, nbr_out=None,
     assert cout_write == 0 or (defer is not None and _usable_out(out, cout_write * kvol * cin) and nbr_out is None)
     dw = out if _usable_out(out, (cout_write or cout) * kvol * cin) else \
         torch.empty((cout, kvol, cin), dtype=torch.float32, device=x.device)
-    os_splits = 0
-    if WGRAD_OS and nbr_out is not None and nbr_out.is_contiguous() and nbr_out.shape[1] >= dy.shape[0]:
-        os_splits = lib.pcd_sparse_conv_wgrad_os_splits(dy.shape[0], kvol, x.shape[1], cout)
-    if os_splits > 0:
-        slab = torch.empty((os_splits * cout * kvol * cin * 4,), dtype=torch.uint8, device=x.device)
+    x_w = x.shape[1]
 
-        def meta_os():
-            npairs = int((nbr_out >= 0).sum().item())
-            return dict(bytes=(x.shape[0] * x.shape[1] + dy.shape[0] * cout) * 2 + 8 * npairs + kvol * cin * cout * 4,
-                        flops=2 * npairs * x.shape[1] * cout, rows=dy.shape[0], pairs=npairs)
-
-        with _Timed(f"wgrad_os16_kernel {x.shape[1]}x{cout} K={kvol}", meta_os):
-            L.check(lib.pcd_sparse_conv_wgrad_os(L.ptr(x), x.shape[0], x.shape[1], cin, L.ptr(dy), dy.shape[0],
-                                                 L.ptr(n_out_dev), cout, L.ptr(nbr_out), nbr_out.shape[1], kvol,
-                                                 L.ptr(slab), slab.numel(), L.stream_ptr()), "pcd_sparse_conv_wgrad_os")
-        job = (slab, dw, kvol, cin, cout, 0, os_splits)
-        if defer is not None:
-            defer.append(job)
-        else:
-            wgrad_reduce_batched([job])
-        return dw
-    if rb is not None and not rb.subm and rb.implicit_pairs and rb._pairs is None and rb.classes is not None \
-            and not (cin == 128 and cout == 128 and x.shape[1] == 128) and not x_block:
-        # strided rulebook without pair lists: the pairs of offset k are its parity class's rows and their nbr_in entries
-        n_x = x.shape[0]
-        wsb = lib.pcd_sparse_conv_wgrad_workspace_bytes(kvol, cin, cout, n_x)
-        ws = _ws(wsb, x.device) if defer is None else torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
-
-        def meta_c():
-            npairs = int((rb.nbr_in >= 0).sum().item())
-            return dict(bytes=(n_x * x.shape[1] + dy.shape[0] * cout) * 2 + 8 * npairs + kvol * cin * cout * 4,
-                        flops=2 * npairs * x.shape[1] * cout, rows=dy.shape[0], pairs=npairs)
-
-        b = lambda c: 4 if (c + 15) // 16 >= 4 else (2 if (c + 15) // 16 >= 2 else 1)
-        with _Timed(f"wgrad_kernel<{b(cin)}, {b(cout)}> {x.shape[1]}x{cout} K={kvol} classes", meta_c):
-            tab, compact = (rb.nbr_cls, 1) if rb.nbr_cls is not None else (rb.nbr_in, 0)
-            L.check(lib.pcd_sparse_conv_wgrad_classes(L.ptr(x), n_x, L.ptr(n_in_dev), x.shape[1], cin, L.ptr(dy), dy.shape[0],
-                                                      cout, L.ptr(tab), tab.shape[1], L.host_i32(rb.ksize),
-                                                      L.host_i32(rb.stride), L.host_i32(rb.dilation), L.ptr(rb.classes[0]),
-                                                      L.ptr(rb.classes[1]), L.ptr(dw), L.ptr(ws), ws.numel(), L.stream_ptr(),
-                                                      compact),
-                    "pcd_sparse_conv_wgrad_classes")
-        if defer is not None:
-            defer.append((ws, dw, kvol, cin, cout, n_x, 0, 1 if conv2d_layout else 0, cout_write))
-            return dw
-        L.check(lib.pcd_sparse_conv_wgrad_reduce(kvol, cin, cout, n_x, L.ptr(dw), L.ptr(ws), L.stream_ptr()),
-                "pcd_sparse_conv_wgrad_reduce")
-        return dw
-    if rb is not None:
-        pairs, pair_num = rb.pairs, rb.pair_num
-    if pairs is None or pair_num is None:
-        raise L.PcdError("weight gradient needs the rulebook's pair lists, but this rulebook was built without them "
-                         "(want_pairs=False: the layer saw no tensor requiring grad when it built the rulebook, e.g. "
-                         "under torch.no_grad()); rebuild it with gradients enabled")
-    _require_cuda(pairs, pair_num)
-    assert pairs.is_contiguous()
-    pmax = pairs.shape[2]
-    wsb = lib.pcd_sparse_conv_wgrad_workspace_bytes(kvol, cin, cout, pmax)
-    ws = _ws(wsb, x.device) if defer is None else torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
-
-    def meta():
-        npairs = int(pair_num.sum().item())
-        e = 2
-        return dict(bytes=(x.shape[0] * x.shape[1] + dy.shape[0] * cout) * e + 8 * npairs
-                    + kvol * cin * cout * 4, flops=2 * npairs * x.shape[1] * cout, rows=dy.shape[0],
-                    pairs=npairs)
+    def meta_of(count_pairs):                    # SURVEY 8d, by the table the kernel reads its pairs off
+        def meta():
+            npairs = count_pairs()
+            return dict(bytes=(x.shape[0] * x_w + dy.shape[0] * cout) * 2 + 8 * npairs + kvol * cin * cout * 4,
+                        flops=2 * npairs * x_w * cout, rows=dy.shape[0], pairs=npairs)
+        return meta
 
     def blocks(c):
         b = (c + 15) // 16
         return 4 if b >= 4 else (2 if b >= 2 else 1)
 
-    kname = "wgrad128_kernel" if (cin == 128 and cout == 128 and x.shape[1] == 128) else \
-        f"wgrad_kernel<{blocks(cin)}, {blocks(cout)}>"
-    with _Timed(f"{kname} {x.shape[1]}x{cout} K={kvol}", meta):
-        L.check(lib.pcd_sparse_conv_wgrad_v2(L.ptr(x), x.shape[0], L.ptr(n_in_dev), x_ld, cin, L.ptr(dy),
-                                             dy.shape[0], cout, L.ptr(pairs), L.ptr(pair_num), kvol, pmax, L.ptr(dw),
-                                             L.ptr(ws), ws.numel(), L.stream_ptr()), "pcd_sparse_conv_wgrad_v2")
-    if defer is not None:
-        defer.append((ws, dw, kvol, cin, cout, pmax, 0, 1 if conv2d_layout else 0, cout_write))
-        return dw
-    L.check(lib.pcd_sparse_conv_wgrad_reduce(kvol, cin, cout, pmax, L.ptr(dw), L.ptr(ws), L.stream_ptr()),
-            "pcd_sparse_conv_wgrad_reduce")
-    return dw
+    def tile_job(pmax):
+        """the reduction of the pair kernels' per-tile partials over `pmax` pairs, with a workspace of its own when deferred"""
+        wsb = lib.pcd_sparse_conv_wgrad_workspace_bytes(kvol, cin, cout, pmax)
+        ws = _ws(wsb, x.device) if defer is None else torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
+        return WgradJob(ws, dw, kvol, cin, cout, pmax, layout=1 if conv2d_layout else 0, cout_write=cout_write)
+
+    wide = cin == 128 and cout == 128 and x_w == 128     # (wgrad128_kernel: cuts the concatenated pair lists into equal chunks)
+    os_splits = 0
+    if WGRAD_OS and nbr_out is not None and nbr_out.is_contiguous() and nbr_out.shape[1] >= dy.shape[0]:
+        os_splits = lib.pcd_sparse_conv_wgrad_os_splits(dy.shape[0], kvol, x_w, cout)
+    if os_splits > 0:
+        job = WgradJob(torch.empty((os_splits * cout * kvol * cin * 4,), dtype=torch.uint8, device=x.device), dw, kvol, cin,
+                       cout, pmax=0, splits=os_splits)
+        slab = job.workspace
+        with _Timed(f"wgrad_os16_kernel {x_w}x{cout} K={kvol}", meta_of(lambda: int((nbr_out >= 0).sum().item()))):
+            L.check(lib.pcd_sparse_conv_wgrad_os(L.ptr(x), x.shape[0], x_w, cin, L.ptr(dy), dy.shape[0],
+                                                 L.ptr(n_out_dev), cout, L.ptr(nbr_out), nbr_out.shape[1], kvol,
+                                                 L.ptr(slab), slab.numel(), L.stream_ptr()), "pcd_sparse_conv_wgrad_os")
+    elif rb is not None and not rb.subm and rb.implicit_pairs and rb._pairs is None and rb.classes is not None \
+            and not wide and not x_block:
+        # strided rulebook without pair lists: the pairs of offset k are its parity class's rows and their nbr_in entries
+        job = tile_job(x.shape[0])
+        ws = job.workspace
+        with _Timed(f"wgrad_kernel<{blocks(cin)}, {blocks(cout)}> {x_w}x{cout} K={kvol} classes",
+                    meta_of(lambda: int((rb.nbr_in >= 0).sum().item()))):
+            tab, compact = (rb.nbr_cls, 1) if rb.nbr_cls is not None else (rb.nbr_in, 0)
+            L.check(lib.pcd_sparse_conv_wgrad_classes(L.ptr(x), x.shape[0], L.ptr(n_in_dev), x_w, cin, L.ptr(dy), dy.shape[0],
+                                                      cout, L.ptr(tab), tab.shape[1], L.host_i32(rb.ksize),
+                                                      L.host_i32(rb.stride), L.host_i32(rb.dilation), L.ptr(rb.classes[0]),
+                                                      L.ptr(rb.classes[1]), L.ptr(dw), L.ptr(ws), ws.numel(), L.stream_ptr(),
+                                                      compact),
+                    "pcd_sparse_conv_wgrad_classes")
+    else:
+        if rb is not None:
+            pairs, pair_num = rb.pairs, rb.pair_num
+        if pairs is None or pair_num is None:
+            raise L.PcdError("weight gradient needs the rulebook's pair lists, but this rulebook was built without them "
+                             "(want_pairs=False: the layer saw no tensor requiring grad when it built the rulebook, e.g. "
+                             "under torch.no_grad()); rebuild it with gradients enabled")
+        _require_cuda(pairs, pair_num)
+        assert pairs.is_contiguous()
+        job = tile_job(pairs.shape[2])
+        ws = job.workspace
+        kname = "wgrad128_kernel" if wide else f"wgrad_kernel<{blocks(cin)}, {blocks(cout)}>"
+        with _Timed(f"{kname} {x_w}x{cout} K={kvol}", meta_of(lambda: int(pair_num.sum().item()))):
+            L.check(lib.pcd_sparse_conv_wgrad_v2(L.ptr(x), x.shape[0], L.ptr(n_in_dev), x_ld, cin, L.ptr(dy),
+                                                 dy.shape[0], cout, L.ptr(pairs), L.ptr(pair_num), kvol, job.pmax, L.ptr(dw),
+                                                 L.ptr(ws), ws.numel(), L.stream_ptr()), "pcd_sparse_conv_wgrad_v2")
+    return _reduce_or_defer(job, defer)
 
 
 class LinearFunctionalLoss(torch.autograd.Function):
@@ -1601,12 +1525,8 @@ def conv2d_wgrad(x, dy, cout=None, out=None, defer=None):
                              rows=B * H * W, pairs=0)):
         L.check(lib.pcd_conv2d_wgrad_3x3_nhwc(L.ptr(x), x_cs, L.ptr(dy), B, H, W, cin, cp, L.ptr(slab), slab.numel() * 4,
                                               L.stream_ptr()), "pcd_conv2d_wgrad_3x3_nhwc")
-    job = (slab, dw, 9, cin, cp, 1, splits, 1, cout if cout != cp else 0)
-    if defer is not None:
-        defer.append(job)
-    else:
-        wgrad_reduce_batched([job])
-    return dw
+    return _reduce_or_defer(WgradJob(slab, dw, kvol=9, cin=cin, cout=cp, pmax=1, splits=splits, layout=1,
+                                     cout_write=cout if cout != cp else 0), defer)
 
 
 def conv2d_planes_nhwc(mode, x, packed_w, cout, out_hw, bias=None):
@@ -1659,17 +1579,11 @@ def wgrad_f32(x, dy, pairs, pair_num, kvol):
 
 
 def wgrad_reduce_batched(jobs):
-    """jobs = [(slab workspace, dw, kvol, cin, cout, pmax[, splits[, layout[, cout_write[, cin_write]]]])] collected by
-    wgrad(defer=...) / subm_window_wgrad(defer=...)."""
-    import ctypes
+    """jobs = [WgradJob] collected by wgrad(defer=...) / subm_window_wgrad(defer=...) / conv2d_wgrad(defer=...); a plain tuple
+    (slab workspace, dw, kvol, cin, cout, pmax[, splits[, layout[, cout_write[, cin_write]]]]) is read as one."""
     for i in range(0, len(jobs), L.WGRAD_MAX_JOBS):
         chunk = jobs[i:i + L.WGRAD_MAX_JOBS]
-        arr = (L.PcdWgradReduceJob * len(chunk))()
-        for j, job in enumerate(chunk):
-            ws, dw, kvol, cin, cout, pmax = job[:6]
-            arr[j] = L.PcdWgradReduceJob(L.ptr(ws), L.ptr(dw), kvol, cin, cout, pmax, job[6] if len(job) > 6 else 0,
-                                         job[7] if len(job) > 7 else 0, job[8] if len(job) > 8 else 0,
-                                         job[9] if len(job) > 9 else 0)
+        arr = (L.PcdWgradReduceJob * len(chunk))(*[_wgrad_job_struct(job) for job in chunk])
         L.check(L.lib().pcd_sparse_conv_wgrad_reduce_batched(ctypes.cast(arr, ctypes.c_void_p), len(chunk),
                                                              L.stream_ptr()), "pcd_sparse_conv_wgrad_reduce_batched")
 
@@ -1814,7 +1728,6 @@ def col_sum_finalize(partial, rows, out=None):
 
 def col_sum_finalize_batched(jobs):
     """jobs = [(partial [rows, c], rows, out [c] f32)]: all of them in ceil(len / 32) launches."""
-    import ctypes
     for i in range(0, len(jobs), L.COLSUM_MAX_JOBS):
         chunk = jobs[i:i + L.COLSUM_MAX_JOBS]
         arr = (L.PcdColsumJob * len(chunk))()

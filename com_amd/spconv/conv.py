@@ -239,9 +239,9 @@ class SparseConvolution(SparseModule):
         assert isinstance(input, SparseConvTensor)
         rb, out_idx, out_shape = self._rulebook(input)
         cur = torch.cuda.current_stream()
-        ev = getattr(rb, "ready_event", None)
+        ev = rb.ready_event
         first_use = False
-        if ev is not None and getattr(rb, "joined_stream", None) != cur.cuda_stream:
+        if ev is not None and rb.joined_stream != cur.cuda_stream:
             cur.wait_event(ev)                      # built on the prefetch stream: order this stream after it ONCE
             rb.joined_stream = cur.cuda_stream
             first_use = True
@@ -254,7 +254,7 @@ class SparseConvolution(SparseModule):
             fp8 = None                                  # (the fp8-forward training form; inference has Fp8Backbone)
         # window kernel: SubM rulebook over z-fastest rows, bf16 features (decided here -- the packs follow the decision)
         padded = self.in_channels < self.out_channels        # (conv_input: 5 -> 16 on rows zero-padded to 16 channels)
-        win = (fp8 is None and rb.subm and getattr(rb, "order", None) == ops.ROWS_YXZ and input.features.is_cuda
+        win = (fp8 is None and rb.subm and rb.order == ops.ROWS_YXZ and input.features.is_cuda
                and input.features.dtype == torch.bfloat16
                and (input.features.shape[1] == self.in_channels or
                     (padded and input.features.shape[1] in (ops.pow2_ge8(self.in_channels), self.out_channels)))

@@ -30,7 +30,7 @@ _PENDING = []   # [(event, tensors kept alive)] of weight-gradient launches not 
 
 
 _COLSUM_JOBS = []   # [(partial, rows, bias.grad)] of deferred bias gradients: one launch at the join
-_WGRAD_JOBS = []    # [(slab, dW, kvol, cin, cout, pmax)] of deferred slab reductions: one launch at the join
+_WGRAD_JOBS = []    # [ops.WgradJob] of deferred slab reductions: one launch at the join
 WGRAD_FLUSH_BYTES = 32 << 20     # deferred slab reductions are flushed whenever this many slab bytes have piled up (0: once, at the join)
 _WGRAD_KEEP = []
 _SP_SEQ = [0]       # diagnostics (ops.STAMPS["sparse"]): running index of the sparse conv layers in backward order
@@ -154,7 +154,7 @@ class SparseConvFunction(Function):
             assert out_dtype == torch.bfloat16 and rb.subm
             y = ops.subm_window(x, packed_fwd, b, rb, cout, bn_reduce=stats)
         else:
-            packed = getattr(rb, "nbr_out_packed", None) is not None and out_dtype == torch.bfloat16 \
+            packed = rb.nbr_out_packed is not None and out_dtype == torch.bfloat16 \
                 and not ops.gather_gemm_is_wide(x.shape[0], cin_pad, rb.kvol, rb.n_out, cout)
             y = ops.gather_gemm(x, packed_fwd, b, rb.nbr_out_packed if packed else rb.nbr_out, rb.kvol, False, rb.n_out, cout,
                                 out_dtype, n_dev=rb.n_out_dev, bn_reduce=stats, nbr_packed=packed)
@@ -233,7 +233,7 @@ class SparseConvFunction(Function):
                 assert not ctx.window, "window packs cannot feed the generic kernel"
                 dxp = ops.gather_gemm(dy16, packed_d, None, rb.nbr_out, rb.kvol, True, rb.n_in, ctx.cin_pad,
                                       ctx.in_dtype, n_dev=rb.n_in_dev, addend=add, bn_reduce=red)
-            elif USE_DGRAD_CLASSES and getattr(rb, "classes", None) is not None and ctx.cout >= 32 \
+            elif USE_DGRAD_CLASSES and rb.classes is not None and ctx.cout >= 32 \
                     and (ctx.cout & (ctx.cout - 1)) == 0 and ctx.cin_pad % 16 == 0:
                 # strided conv: rows grouped by parity class run only the 1..8 offsets they can use
                 dxp = ops.dgrad_classes(dy16, packed_d, rb, ctx.cin_pad, ctx.in_dtype, addend=add, bn_reduce=red)
@@ -293,7 +293,7 @@ class SparseConvFunction(Function):
                     ctx.colsum_link.result = None
                 if direct_b:
                     db = None
-            if deferred and WGRAD_FLUSH_BYTES > 0 and sum(j[0].numel() for j in _WGRAD_JOBS) >= WGRAD_FLUSH_BYTES:
+            if deferred and WGRAD_FLUSH_BYTES > 0 and sum(j.workspace.numel() for j in _WGRAD_JOBS) >= WGRAD_FLUSH_BYTES:
                 # the slabs collected so far are summed NOW, on this (side) stream, in the middle of the backward pass: one
                 # reduction of every layer at the very end read ~170 MB of 128-channel tiles on the step's critical tail
                 ops.wgrad_reduce_batched(_WGRAD_JOBS)
