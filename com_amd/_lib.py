@@ -234,6 +234,13 @@ PROTOTYPES = {
     "pcd_point_head_loss_backward": (_i, [_vp, _vp, _i, ctypes.c_longlong, _vp, _vp, _i, _i, ctypes.c_float, _vp, _vp]),
     "pcd_roiaware_pool3d_forward": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "pcd_roiaware_pool3d_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "pcd_roi_head_max_overlaps": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "pcd_roi_head_sample_targets": (_i, [_vp] * 20),
+    "pcd_roi_head_loss_forward": (_i, [_vp, _i, ctypes.c_longlong, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                       ctypes.c_float, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp]),
+    "pcd_roi_head_loss_backward": (_i, [_vp, _i, ctypes.c_longlong, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                        ctypes.c_float, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pcd_roi_head_decode": (_i, [_vp, _vp, _i, ctypes.c_longlong, _i, _vp, _vp]),
     "pcd_nms_workspace_bytes": (_sz, [_i]),
     "pcd_nms_bev": (_i, [_vp, _i, ctypes.c_float, _i, _vp, _vp, _vp, _sz, _vp]),
     "pcd_centerhead_postproc_workspace_bytes": (_sz, [_vp, _vp]),
@@ -322,6 +329,17 @@ class PcdAnchorCurriculum(ctypes.Structure):
 PCD_ANCHOR_CUR_GROUPS = 96
 PCD_ANCHOR_CUR_ACCUM = 3 + 2 * PCD_ANCHOR_CUR_GROUPS
 PCD_ANCHOR_CUR_CLUSTER_BASE, PCD_ANCHOR_CUR_CLUSTER_X1, PCD_ANCHOR_CUR_CLUSTER_CAR, PCD_ANCHOR_CUR_CLUSTER_CAR_X2 = 0, 1, 2, 3
+
+
+PCD_ROI_SCORE_ROI_IOU, PCD_ROI_SCORE_CLS = 0, 1
+
+
+class PcdRoiSampler(ctypes.Structure):
+    """include/pcd_ops.h: struct PcdRoiSampler (TARGET_CONFIG of a RoI head as pcd_roi_head_sample_targets takes it)."""
+    _fields_ = [("batch", ctypes.c_int), ("num_rois", ctypes.c_int), ("num_gt", ctypes.c_int), ("rois_per_image", ctypes.c_int),
+                ("fg_rois_per_image", ctypes.c_int), ("score_type", ctypes.c_int), ("given_inds", ctypes.c_int),
+                ("reg_fg_thresh", ctypes.c_float), ("cls_fg_thresh", ctypes.c_float), ("cls_bg_thresh", ctypes.c_float),
+                ("cls_bg_thresh_lo", ctypes.c_float), ("cls_span", ctypes.c_float)]
 
 
 class PcdBnReduce(ctypes.Structure):

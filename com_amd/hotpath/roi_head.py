@@ -1,0 +1,500 @@
+"""`PVRCNNHead` -- the RoI head of PV-RCNN (pcdet/models/roi_heads/pvrcnn_head.py, roi_head_template.py,
+target_assigner/proposal_target_layer.py; `ROI_HEAD.NAME: PVRCNNHead` in tools/cfgs/waymo_models/pv_rcnn.yaml:134-192) as a
+registry drop-in: same constructor arguments, the modules `roi_grid_pool_layer`, `shared_fc_layer`, `cls_layers`,
+`reg_layers`, `reg_loss_func` built as the reference builds them (a reference state dict loads with strict=True),
+`proposal_layer`, `assign_targets`, `get_loss(tb_dict)`, `generate_predicted_boxes` and `forward(batch_dict)` with the
+reference's names, arguments and returns.
+
+Proposal targets, the loss and the box decoding run on the device (com_amd/csrc/roihead.hip; C ABI `pcd_roi_head_*`): two
+launches for the targets of the whole batch instead of a host loop over frames and classes with a dozen nonzero() calls and
+a sync per padded GT row, one launch for the loss and one for its backward instead of boolean-mask indexing and five
+`.item()`.  Nothing reads back: `tb_dict` holds DEVICE scalars, and assign_targets + get_loss + backward can sit in a
+captured graph.
+
+Randomness is an input (`uniforms` f32 [B, N + ROI_PER_IMAGE] in [0, 1)): the stream of random
+numbers differs from the reference's (np.random.permutation / torch.randint on the host), the distribution of the sampled
+RoIs does not.
+
+Scope: code_size 7, ResidualCoder, BinaryCrossEntropy, smooth-l1, class-agnostic NMS.  Everything else is refused at
+construction with a PcdError that names the key."""
+import ctypes
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import _lib as L
+from .. import iou3d_nms
+from ._maps import dtype_code as _dt
+from ._maps import like as _like
+from .dense2d import _get
+from .pvrcnn_stage2 import StackSAModuleMSG, roi_grid_pool
+
+SCORE_TYPES = {'roi_iou': L.PCD_ROI_SCORE_ROI_IOU, 'cls': L.PCD_ROI_SCORE_CLS}
+
+
+def _dev(name, *tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise L.PcdError(f"{name} needs HIP device tensors (there is no CPU fallback)")
+
+
+def _shapes(name, rois, gt_boxes):
+    if rois.dim() != 3 or rois.shape[2] != 7 or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 8 or gt_boxes.shape[0] != rois.shape[0]:
+        raise L.PcdError(f"{name}: rois {tuple(rois.shape)}, gt_boxes {tuple(gt_boxes.shape)}; want [B, N, 7] and [B, M, 8] "
+                         "(code_size 7)")
+
+
+def max_overlaps(rois, roi_labels, gt_boxes, same_class=False):
+    """pcd_roi_head_max_overlaps: (max_overlaps f32 [B, N], gt_assignment int32 [B, N]); proposal_target_layer.py:89-105,
+    :195-228."""
+    _dev("roi head max_overlaps", rois, gt_boxes, roi_labels)
+    _shapes("roi head max_overlaps", rois, gt_boxes)
+    r, g, lab = rois.contiguous().float(), gt_boxes.contiguous().float(), roi_labels.contiguous().long()
+    B, N, M = int(r.shape[0]), int(r.shape[1]), int(g.shape[1])
+    if tuple(lab.shape) != (B, N):
+        raise L.PcdError(f"roi head max_overlaps: roi_labels {tuple(lab.shape)}, want {(B, N)}")
+    ov = torch.empty((B, N), dtype=torch.float32, device=r.device)
+    ga = torch.empty((B, N), dtype=torch.int32, device=r.device)
+    L.check(L.lib().pcd_roi_head_max_overlaps(L.ptr(r), L.ptr(lab), L.ptr(g) if M else None, B, N, M, int(bool(same_class)),
+                                              L.ptr(ov), L.ptr(ga), L.stream_ptr()), "pcd_roi_head_max_overlaps")
+    return ov, ga
+
+
+class ProposalTargetLayer(nn.Module):
+    """proposal_target_layer.py:8-228 plus the canonical transformation of RoIHeadTemplate.assign_targets, on the device."""
+
+    def __init__(self, roi_sampler_cfg):
+        super().__init__()
+        self.roi_sampler_cfg = c = roi_sampler_cfg
+        for key in ('ROI_PER_IMAGE', 'FG_RATIO', 'CLS_SCORE_TYPE', 'CLS_FG_THRESH', 'CLS_BG_THRESH', 'CLS_BG_THRESH_LO',
+                    'HARD_BG_RATIO', 'REG_FG_THRESH'):
+            if _get(c, key, None) is None:
+                raise L.PcdError(f"ProposalTargetLayer: TARGET_CONFIG.{key} missing")
+        self.score_type = _get(c, 'CLS_SCORE_TYPE')
+        if self.score_type not in SCORE_TYPES:
+            raise L.PcdError(f"ProposalTargetLayer: TARGET_CONFIG.CLS_SCORE_TYPE = {self.score_type!r} is not supported "
+                             f"(supported: {sorted(SCORE_TYPES)})")
+        self.rois_per_image = int(_get(c, 'ROI_PER_IMAGE'))
+        self.fg_rois_per_image = int(np.round(_get(c, 'FG_RATIO') * self.rois_per_image))        # :119
+        ratio = _get(c, 'HARD_BG_RATIO')
+        self.hard_bg_counts = [int(bg * ratio) for bg in range(self.rois_per_image + 1)]           # :167, per bg count
+        self.same_class = bool(_get(c, 'SAMPLE_ROI_BY_EACH_CLASS', False))
+        self.generator = None           # a device generator, made on first use; seed it with .manual_seed()
+        self._table = None
+        self.status = None              # device int32 [1]: frames that had neither fg nor bg (the reference raises)
+
+    def manual_seed(self, seed, device="cuda"):
+        """seed the generator the uniforms are drawn from (philox: usable under graph capture)"""
+        if self.generator is None:
+            self.generator = torch.Generator(device=device)
+        self.generator.manual_seed(int(seed))
+        return self
+
+    def draw_uniforms(self, batch, num_rois, device):
+        """f32 [B, N + ROI_PER_IMAGE] in [0, 1): one key per RoI, one draw per output slot"""
+        if self.generator is None:
+            self.generator = torch.Generator(device=device)
+        return torch.rand((batch, num_rois + self.rois_per_image), dtype=torch.float32, device=device, generator=self.generator)
+
+    def check_status(self):
+        """frames whose RoIs were neither foreground nor background since the last check (one read-back: call it outside
+        capture).  The reference raises NotImplementedError for such a frame."""
+        if self.status is None or torch.cuda.is_current_stream_capturing():
+            return 0
+        n = int(self.status.item())
+        if n:
+            self.status.zero_()
+            raise L.PcdError(f"ProposalTargetLayer: {n} frame(s) with neither foreground nor background RoIs (NaN IoUs?)")
+        return n
+
+    def forward(self, batch_dict, uniforms=None, sampled_inds=None):
+        """The reference's seven keys (+ 'gt_of_rois_src', 'gt_of_rois_canonical' = what RoIHeadTemplate.assign_targets makes
+        of them, and 'sampled_inds' int32 [B, R]).  `sampled_inds` given: only the gather runs."""
+        c = self.roi_sampler_cfg
+        rois, gt = batch_dict['rois'], batch_dict['gt_boxes']
+        scores, labels = batch_dict['roi_scores'], batch_dict['roi_labels']
+        _dev("ProposalTargetLayer", rois, gt, scores, labels)
+        _shapes("ProposalTargetLayer", rois, gt)
+        B, N, M, R = int(rois.shape[0]), int(rois.shape[1]), int(gt.shape[1]), self.rois_per_image
+        if 'batch_size' in batch_dict and int(batch_dict['batch_size']) != B:
+            raise L.PcdError(f"ProposalTargetLayer: batch_size {batch_dict['batch_size']}, rois {tuple(rois.shape)}")
+        rois, gt = rois.contiguous().float(), gt.contiguous().float()
+        scores, labels = scores.contiguous().float(), labels.contiguous().long()
+        dev = rois.device
+        ov, ga = max_overlaps(rois, labels, gt, self.same_class)
+        cfg = L.PcdRoiSampler()
+        cfg.batch, cfg.num_rois, cfg.num_gt, cfg.rois_per_image = B, N, M, R
+        cfg.fg_rois_per_image, cfg.score_type = self.fg_rois_per_image, SCORE_TYPES[self.score_type]
+        cfg.given_inds = int(sampled_inds is not None)
+        cfg.reg_fg_thresh, cfg.cls_fg_thresh = float(_get(c, 'REG_FG_THRESH')), float(_get(c, 'CLS_FG_THRESH'))
+        cfg.cls_bg_thresh, cfg.cls_bg_thresh_lo = float(_get(c, 'CLS_BG_THRESH')), float(_get(c, 'CLS_BG_THRESH_LO'))
+        cfg.cls_span = float(_get(c, 'CLS_FG_THRESH') - _get(c, 'CLS_BG_THRESH'))
+        if sampled_inds is not None:
+            if tuple(sampled_inds.shape) != (B, R):
+                raise L.PcdError(f"ProposalTargetLayer: sampled_inds {tuple(sampled_inds.shape)}, want {(B, R)}")
+            inds = sampled_inds.to(device=dev, dtype=torch.int32).contiguous().clone()
+            uniforms = None
+        else:
+            if uniforms is None:
+                uniforms = self.draw_uniforms(B, N, dev)
+            if tuple(uniforms.shape) != (B, N + R) or uniforms.dtype != torch.float32 or not uniforms.is_cuda:
+                raise L.PcdError(f"ProposalTargetLayer: uniforms {tuple(uniforms.shape)} {uniforms.dtype}, want f32 {(B, N + R)} "
+                                 "on the device")
+            uniforms = uniforms.contiguous()
+            inds = torch.empty((B, R), dtype=torch.int32, device=dev)
+        if self._table is None or self._table.device != dev:
+            self._table = torch.tensor(self.hard_bg_counts, dtype=torch.int32, device=dev)
+            self.status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {'rois': torch.empty((B, R, 7), **f32), 'gt_of_rois': torch.empty((B, R, 8), **f32),
+               'gt_iou_of_rois': torch.empty((B, R), **f32), 'roi_scores': torch.empty((B, R), **f32),
+               'roi_labels': torch.empty((B, R), dtype=torch.int64, device=dev),
+               'reg_valid_mask': torch.empty((B, R), dtype=torch.int64, device=dev),
+               'rcnn_cls_labels': torch.empty((B, R), dtype=torch.float32 if self.score_type == 'roi_iou' else torch.int64,
+                                              device=dev)}
+        canonical = torch.empty((B, R, 8), **f32)
+        L.check(L.lib().pcd_roi_head_sample_targets(
+            ctypes.cast(ctypes.pointer(cfg), ctypes.c_void_p), L.ptr(rois), L.ptr(scores), L.ptr(labels), L.ptr(gt) if M else None,
+            L.ptr(ov), L.ptr(ga), L.ptr(uniforms), L.ptr(self._table), L.ptr(inds), L.ptr(out['rois']), L.ptr(out['roi_scores']),
+            L.ptr(out['roi_labels']), L.ptr(out['gt_iou_of_rois']), L.ptr(out['gt_of_rois']), L.ptr(canonical),
+            L.ptr(out['reg_valid_mask']), L.ptr(out['rcnn_cls_labels']), L.ptr(self.status), L.stream_ptr()),
+            "pcd_roi_head_sample_targets")
+        out['gt_of_rois_src'] = out['gt_of_rois']
+        out['gt_of_rois_canonical'] = canonical
+        out['sampled_inds'] = inds
+        out['max_overlaps'], out['gt_assignment'] = ov, ga
+        return out
+
+
+class _RoiLoss(torch.autograd.Function):
+    """get_loss through pcd_roi_head_loss_forward / _backward: 1 + 1 launches.  Returns out f32 [5] (rcnn_loss, rcnn_loss_cls,
+    rcnn_loss_reg with the corner term, rcnn_loss_corner, fg_sum) and aux f32 [4]; only out[0] carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, rcnn_cls, rcnn_reg, cls_labels, reg_valid, rois, gt_ct, gt_src, code_weights, weights, corner):
+        _dev("PVRCNNHead.get_loss", rcnn_cls, rcnn_reg, cls_labels, reg_valid, rois, gt_ct, gt_src)
+        n = int(rcnn_reg.shape[0])
+        cls2 = rcnn_cls.reshape(n, -1) if rcnn_cls.dim() != 2 else rcnn_cls
+        if rcnn_reg.dim() != 2 or rcnn_reg.shape[1] != 7 or rcnn_reg.stride(1) != 1 or cls2.shape[1] != 1 or n < 1:
+            raise L.PcdError(f"roi head loss: rcnn_cls {tuple(rcnn_cls.shape)}, rcnn_reg {tuple(rcnn_reg.shape)}; want "
+                             "[B*R] or [B*R, 1] and [B*R, 7] rows")
+        for name, t, width in (('rcnn_cls_labels', cls_labels, 1), ('reg_valid_mask', reg_valid, 1), ('rois', rois, 7),
+                               ('gt_of_rois', gt_ct, 8), ('gt_of_rois_src', gt_src, 8)):
+            if t.numel() != n * width or not t.is_contiguous():
+                raise L.PcdError(f"roi head loss: {name} {tuple(t.shape)}, want {n} dense rows of {width}")
+        out = torch.empty((5,), dtype=torch.float32, device=rcnn_reg.device)
+        aux = torch.empty((4,), dtype=torch.float32, device=rcnn_reg.device)
+        cw = L.host_f32(code_weights)
+        L.check(L.lib().pcd_roi_head_loss_forward(
+            L.ptr(cls2), _dt(cls2), int(cls2.stride(0)), L.ptr(rcnn_reg), _dt(rcnn_reg), int(rcnn_reg.stride(0)), L.ptr(cls_labels),
+            L.ptr(reg_valid), L.ptr(rois), L.ptr(gt_ct), L.ptr(gt_src), n, cw, weights[0], weights[1], weights[2], int(corner),
+            L.ptr(out), L.ptr(aux), L.stream_ptr()), "pcd_roi_head_loss_forward")
+        ctx.save_for_backward(cls2, rcnn_reg, cls_labels, reg_valid, rois, gt_ct, gt_src, aux)
+        ctx.meta = (tuple(code_weights), tuple(weights), int(corner), rcnn_cls.shape)
+        ctx.mark_non_differentiable(aux)
+        return out, aux
+
+    @staticmethod
+    def backward(ctx, g_out, _g_aux):
+        cls2, rcnn_reg, cls_labels, reg_valid, rois, gt_ct, gt_src, aux = ctx.saved_tensors
+        code_weights, weights, corner, cls_shape = ctx.meta
+        d_cls, d_reg = _like(cls2), _like(rcnn_reg)
+        g = g_out.detach().to(torch.float32)[0:1].contiguous()           # only rcnn_loss is differentiated
+        cw = L.host_f32(code_weights)
+        L.check(L.lib().pcd_roi_head_loss_backward(
+            L.ptr(cls2), _dt(cls2), int(cls2.stride(0)), L.ptr(rcnn_reg), _dt(rcnn_reg), int(rcnn_reg.stride(0)), L.ptr(cls_labels),
+            L.ptr(reg_valid), L.ptr(rois), L.ptr(gt_ct), L.ptr(gt_src), int(rcnn_reg.shape[0]), cw, weights[0], weights[1],
+            weights[2], corner, L.ptr(aux), L.ptr(g), L.ptr(d_cls), L.ptr(d_reg), L.stream_ptr()), "pcd_roi_head_loss_backward")
+        return d_cls.reshape(cls_shape), d_reg, None, None, None, None, None, None, None, None
+
+
+def roi_loss(rcnn_cls, rcnn_reg, rcnn_cls_labels, reg_valid_mask, rois, gt_of_rois, gt_of_rois_src, code_weights, cls_weight,
+             reg_weight, corner_weight, corner):
+    """(out f32 [5], aux f32 [4]) on the device; out[0] = rcnn_loss is differentiable in rcnn_cls [B*R] / [B*R, 1] and rcnn_reg
+    [B*R, 7] (f32 or bf16)."""
+    n = int(rcnn_reg.shape[0])
+    f = lambda t, w: t.detach().reshape(n, w).contiguous().float()       # noqa: E731
+    return _RoiLoss.apply(rcnn_cls, rcnn_reg, rcnn_cls_labels.detach().reshape(n).contiguous().float(),
+                          reg_valid_mask.detach().reshape(n).contiguous().long(), f(rois, 7), f(gt_of_rois, 8), f(gt_of_rois_src, 8),
+                          [float(v) for v in code_weights], (float(cls_weight), float(reg_weight), float(corner_weight)), bool(corner))
+
+
+def decode_boxes(rois, box_preds):
+    """pcd_roi_head_decode: rois [B, N, 7], box_preds [B*N, 7] (f32 / bf16) -> batch_box_preds f32 [B, N, 7]."""
+    _dev("PVRCNNHead.generate_predicted_boxes", rois, box_preds)
+    if rois.dim() != 3 or rois.shape[2] != 7:
+        raise L.PcdError(f"roi head decode: rois {tuple(rois.shape)}, want [B, N, 7] (code_size 7)")
+    n = int(rois.shape[0] * rois.shape[1])
+    bp = box_preds.detach().reshape(-1, box_preds.shape[-1])
+    if tuple(bp.shape) != (n, 7) or bp.dtype not in (torch.float32, torch.bfloat16):
+        raise L.PcdError(f"roi head decode: box_preds {tuple(box_preds.shape)} {box_preds.dtype}, want [{n}, 7] f32 / bf16")
+    if bp.stride(1) != 1:
+        bp = bp.contiguous()
+    r = rois.detach().contiguous().float()
+    out = torch.empty((int(rois.shape[0]), int(rois.shape[1]), 7), dtype=torch.float32, device=rois.device)
+    L.check(L.lib().pcd_roi_head_decode(L.ptr(r), L.ptr(bp), _dt(bp), int(bp.stride(0)) if n else 7, n, L.ptr(out), L.stream_ptr()),
+            "pcd_roi_head_decode")
+    return out
+
+
+class WeightedSmoothL1Loss(nn.Module):
+    """The holder of `reg_loss_func.code_weights` (loss_utils.py:77-141: a plain attribute in the reference too, no
+    parameter, no buffer); the arithmetic runs inside pcd_roi_head_loss_*."""
+
+    def __init__(self, beta=1.0 / 9.0, code_weights=None):
+        super().__init__()
+        self.beta = beta
+        self.code_weights = None if code_weights is None else [float(v) for v in code_weights]
+
+
+class PVRCNNHead(nn.Module):
+    """pvrcnn_head.py:8-175 + roi_head_template.py:11-261 (module docstring)."""
+
+    # Outside capture assign_targets reads the sampler's status word back and raises, as the reference does, when a frame had
+    # neither foreground nor background RoIs (one sync per step).  Under capture nothing can be read: call
+    # proposal_target_layer.check_status() between replays.  False: never read back; the caller polls.
+    check_status_eagerly = True
+
+    def __init__(self, input_channels, model_cfg, num_class=1, **kwargs):
+        super().__init__()
+        self.model_cfg = model_cfg
+        self.num_class = int(num_class)                 # (detector3d_template.py passes 1 for CLASS_AGNOSTIC: True)
+        self._refuse(model_cfg, int(num_class))
+        self.code_size = 7
+        ta, lc = _get(model_cfg, 'TARGET_CONFIG'), _get(model_cfg, 'LOSS_CONFIG')
+        self.proposal_target_layer = ProposalTargetLayer(roi_sampler_cfg=ta)
+        lw = _get(lc, 'LOSS_WEIGHTS')
+        self.reg_loss_func = WeightedSmoothL1Loss(code_weights=lw['code_weights'])
+        self.loss_weights = (float(lw['rcnn_cls_weight']), float(lw['rcnn_reg_weight']), float(lw.get('rcnn_corner_weight', 0.0)))
+        self.corner_loss = bool(_get(lc, 'CORNER_LOSS_REGULARIZATION', False))
+        self.forward_ret_dict = None
+
+        pool = _get(model_cfg, 'ROI_GRID_POOL')
+        self.grid_size = int(_get(pool, 'GRID_SIZE'))
+        mlps = [[input_channels] + list(m) for m in _get(pool, 'MLPS')]     # build_local_aggregation_module (pointnet2_modules.py:10-27)
+        self.roi_grid_pool_layer = StackSAModuleMSG(radii=list(_get(pool, 'POOL_RADIUS')), nsamples=list(_get(pool, 'NSAMPLE')),
+                                                    mlps=mlps, use_xyz=True, pool_method='max_pool')
+        num_c_out = sum(m[-1] for m in mlps)
+        pre_channel = self.grid_size ** 3 * num_c_out
+        dp = _get(model_cfg, 'DP_RATIO')
+        shared_fc = list(_get(model_cfg, 'SHARED_FC'))
+        shared_fc_list = []
+        for k in range(0, shared_fc.__len__()):
+            shared_fc_list.extend([nn.Conv1d(pre_channel, shared_fc[k], kernel_size=1, bias=False), nn.BatchNorm1d(shared_fc[k]),
+                                   nn.ReLU()])
+            pre_channel = shared_fc[k]
+            if k != shared_fc.__len__() - 1 and dp > 0:
+                shared_fc_list.append(nn.Dropout(dp))
+        self.shared_fc_layer = nn.Sequential(*shared_fc_list)
+        self.cls_layers = self.make_fc_layers(input_channels=pre_channel, output_channels=self.num_class,
+                                              fc_list=_get(model_cfg, 'CLS_FC'))
+        self.reg_layers = self.make_fc_layers(input_channels=pre_channel, output_channels=self.code_size * self.num_class,
+                                              fc_list=_get(model_cfg, 'REG_FC'))
+        self.init_weights(weight_init='xavier')
+
+    @staticmethod
+    def _refuse(model_cfg, num_class):
+        """the configurations outside the scope of the kernels: a PcdError that names the key"""
+        def no(key, why):
+            raise L.PcdError(f"PVRCNNHead: {key} {why} is not supported by the HIP RoI head")
+        name = _get(model_cfg, 'NAME', 'PVRCNNHead')
+        if name != 'PVRCNNHead':
+            no('NAME', f"= {name!r}")
+        ta = _get(model_cfg, 'TARGET_CONFIG')
+        if ta is None:
+            no('TARGET_CONFIG', 'missing')
+        coder = _get(ta, 'BOX_CODER', None)
+        if coder != 'ResidualCoder':
+            no('TARGET_CONFIG.BOX_CODER', f"= {coder!r}")
+        if _get(ta, 'BOX_CODER_CONFIG', None):
+            no('TARGET_CONFIG.BOX_CODER_CONFIG', f"= {dict(_get(ta, 'BOX_CODER_CONFIG'))!r} (code_size 7, no sin / cos heading)")
+        lc = _get(model_cfg, 'LOSS_CONFIG')
+        if lc is None:
+            no('LOSS_CONFIG', 'missing')
+        if _get(lc, 'CLS_LOSS', None) != 'BinaryCrossEntropy':
+            no('LOSS_CONFIG.CLS_LOSS', f"= {_get(lc, 'CLS_LOSS', None)!r}")
+        if _get(lc, 'REG_LOSS', None) != 'smooth-l1':
+            no('LOSS_CONFIG.REG_LOSS', f"= {_get(lc, 'REG_LOSS', None)!r}")
+        lw = _get(lc, 'LOSS_WEIGHTS', None)
+        for key in ('rcnn_cls_weight', 'rcnn_reg_weight', 'code_weights'):
+            if lw is None or key not in lw:
+                no(f'LOSS_CONFIG.LOSS_WEIGHTS.{key}', 'missing')
+        if len(lw['code_weights']) != 7:
+            no('LOSS_CONFIG.LOSS_WEIGHTS.code_weights', f"of length {len(lw['code_weights'])} (code_size 7)")
+        if _get(lc, 'CORNER_LOSS_REGULARIZATION', False) and 'rcnn_corner_weight' not in lw:
+            no('LOSS_CONFIG.LOSS_WEIGHTS.rcnn_corner_weight', 'missing')
+        nms = _get(model_cfg, 'NMS_CONFIG')
+        for mode in ('TRAIN', 'TEST'):
+            cfg = _get(nms, mode, None) if nms is not None else None
+            if cfg is None:
+                no(f'NMS_CONFIG.{mode}', 'missing')
+            if _get(cfg, 'MULTI_CLASSES_NMS', False):
+                no(f'NMS_CONFIG.{mode}.MULTI_CLASSES_NMS', '= True')
+            if _get(cfg, 'NMS_TYPE') not in ('nms_gpu', 'nms_normal_gpu'):
+                no(f'NMS_CONFIG.{mode}.NMS_TYPE', f"= {_get(cfg, 'NMS_TYPE')!r}")
+        if not _get(model_cfg, 'CLASS_AGNOSTIC', False) and num_class > 1:
+            no('CLASS_AGNOSTIC', f"= False with num_class = {num_class} (CrossEntropy RoI classification)")
+        if num_class > 1:
+            no('num_class', f"= {num_class} with CLASS_AGNOSTIC = True (the detector passes 1; the reference's BinaryCrossEntropy "
+                            "and box decoding take one logit and one box per RoI)")
+        if _get(_get(model_cfg, 'ROI_GRID_POOL'), 'NAME', 'StackSAModuleMSG') != 'StackSAModuleMSG':
+            no('ROI_GRID_POOL.NAME', f"= {_get(_get(model_cfg, 'ROI_GRID_POOL'), 'NAME')!r}")
+
+    def make_fc_layers(self, input_channels, output_channels, fc_list):
+        """roi_head_template.py:29-43"""
+        fc_layers = []
+        pre_channel = input_channels
+        dp = _get(self.model_cfg, 'DP_RATIO')
+        for k in range(0, fc_list.__len__()):
+            fc_layers.extend([nn.Conv1d(pre_channel, fc_list[k], kernel_size=1, bias=False), nn.BatchNorm1d(fc_list[k]), nn.ReLU()])
+            pre_channel = fc_list[k]
+            if dp >= 0 and k == 0:
+                fc_layers.append(nn.Dropout(dp))
+        fc_layers.append(nn.Conv1d(pre_channel, output_channels, kernel_size=1, bias=True))
+        return nn.Sequential(*fc_layers)
+
+    def init_weights(self, weight_init='xavier'):
+        """pvrcnn_head.py:44-62"""
+        if weight_init == 'kaiming':
+            init_func = nn.init.kaiming_normal_
+        elif weight_init == 'xavier':
+            init_func = nn.init.xavier_normal_
+        elif weight_init == 'normal':
+            init_func = nn.init.normal_
+        else:
+            raise NotImplementedError
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d) or isinstance(m, nn.Conv1d):
+                if weight_init == 'normal':
+                    init_func(m.weight, mean=0, std=0.001)
+                else:
+                    init_func(m.weight)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+        nn.init.normal_(self.reg_layers[-1].weight, mean=0, std=0.001)
+
+    @torch.no_grad()
+    def proposal_layer(self, batch_dict, nms_config):
+        """roi_head_template.py:45-102.  Per frame: top NMS_PRE_MAXSIZE by score, com_amd.iou3d_nms.nms_sorted (the kernels
+        behind nms_gpu, without its read-back of the survivor count), the first NMS_POST_MAXSIZE survivors; rows behind
+        them are zero, as in the reference."""
+        if batch_dict.get('rois', None) is not None:
+            return batch_dict
+        batch_size = batch_dict['batch_size']
+        batch_box_preds = batch_dict['batch_box_preds']
+        batch_cls_preds = batch_dict['batch_cls_preds']
+        post, pre = int(_get(nms_config, 'NMS_POST_MAXSIZE')), int(_get(nms_config, 'NMS_PRE_MAXSIZE'))
+        normal = _get(nms_config, 'NMS_TYPE') == 'nms_normal_gpu'
+        rois = batch_box_preds.new_zeros((batch_size, post, batch_box_preds.shape[-1]))
+        roi_scores = batch_box_preds.new_zeros((batch_size, post))
+        roi_labels = batch_box_preds.new_zeros((batch_size, post), dtype=torch.long)
+        for index in range(batch_size):
+            if batch_dict.get('batch_index', None) is not None:
+                assert batch_cls_preds.shape.__len__() == 2
+                batch_mask = (batch_dict['batch_index'] == index)
+            else:
+                assert batch_dict['batch_cls_preds'].shape.__len__() == 3
+                batch_mask = index
+            box_preds = batch_box_preds[batch_mask]
+            cls_preds = batch_cls_preds[batch_mask]
+            cur_roi_scores, cur_roi_labels = torch.max(cls_preds, dim=1)
+            k = min(pre, int(box_preds.shape[0]))
+            if k == 0:
+                continue
+            _, indices = torch.topk(cur_roi_scores, k=k)
+            keep, num = iou3d_nms.nms_sorted(box_preds[indices][:, 0:7], float(_get(nms_config, 'NMS_THRESH')), normal=normal)
+            m = min(post, k)
+            live = torch.arange(m, device=keep.device) < num.to(torch.int64)
+            selected = indices[torch.where(live, keep[:m], torch.zeros_like(keep[:m]))]
+            rois[index, :m, :] = box_preds[selected] * live.unsqueeze(-1).to(box_preds.dtype)
+            roi_scores[index, :m] = cur_roi_scores[selected] * live.to(cur_roi_scores.dtype)
+            roi_labels[index, :m] = cur_roi_labels[selected] * live.to(torch.long)
+        batch_dict['rois'] = rois
+        batch_dict['roi_scores'] = roi_scores
+        batch_dict['roi_labels'] = roi_labels + 1
+        batch_dict['has_class_labels'] = True if batch_cls_preds.shape[-1] > 1 else False
+        batch_dict.pop('batch_index', None)
+        return batch_dict
+
+    def assign_targets(self, batch_dict, uniforms=None, sampled_inds=None):
+        """roi_head_template.py:104-134: the seven keys of ProposalTargetLayer with 'gt_of_rois' after the canonical
+        transformation, plus 'gt_of_rois_src' (and 'sampled_inds')."""
+        with torch.no_grad():
+            targets_dict = self.proposal_target_layer.forward(batch_dict, uniforms=uniforms, sampled_inds=sampled_inds)
+        if self.check_status_eagerly:                   # (a no-op while the stream is being captured)
+            self.proposal_target_layer.check_status()
+        targets_dict['gt_of_rois'] = targets_dict.pop('gt_of_rois_canonical')
+        return targets_dict
+
+    def _loss(self, forward_ret_dict, weights=None, corner=None):
+        f = forward_ret_dict
+        weights = self.loss_weights if weights is None else weights
+        return roi_loss(f['rcnn_cls'], f['rcnn_reg'].reshape(-1, self.code_size), f['rcnn_cls_labels'], f['reg_valid_mask'],
+                        f['rois'], f['gt_of_rois'], f['gt_of_rois_src'], self.reg_loss_func.code_weights, *weights,
+                        self.corner_loss if corner is None else corner)
+
+    def get_box_reg_layer_loss(self, forward_ret_dict):
+        """roi_head_template.py:136-198: (rcnn_loss_reg with the corner term, tb_dict); tb_dict['rcnn_loss_reg'] is the
+        smooth-L1 term alone, as the reference logs it.  (The fused launch with the classification weight 0; get_loss takes
+        all terms from ONE launch.)"""
+        out, aux = self._loss(forward_ret_dict, (0.0, self.loss_weights[1], self.loss_weights[2]))
+        tb_dict = {'rcnn_loss_reg': aux[2].detach()}
+        if self.corner_loss:
+            tb_dict['rcnn_loss_corner'] = out[3].detach()
+        return out[0], tb_dict
+
+    def get_box_cls_layer_loss(self, forward_ret_dict):
+        """roi_head_template.py:200-218 (the fused launch with the regression weights 0)"""
+        out, _ = self._loss(forward_ret_dict, (self.loss_weights[0], 0.0, 0.0), False)
+        return out[0], {'rcnn_loss_cls': out[1].detach()}
+
+    def get_loss(self, tb_dict=None):
+        """roi_head_template.py:220-231; the tb_dict values are device scalars"""
+        tb_dict = {} if tb_dict is None else tb_dict
+        out, aux = self._loss(self.forward_ret_dict)
+        o = out.detach()
+        tb_dict['rcnn_loss_cls'] = o[1]
+        tb_dict['rcnn_loss_reg'] = aux[2].detach()
+        if self.corner_loss:
+            tb_dict['rcnn_loss_corner'] = o[3]
+        tb_dict['rcnn_loss'] = o[0]
+        return out[0], tb_dict
+
+    def generate_predicted_boxes(self, batch_size, rois, cls_preds, box_preds):
+        """roi_head_template.py:233-261"""
+        batch_cls_preds = cls_preds.view(batch_size, -1, cls_preds.shape[-1])
+        return batch_cls_preds, decode_boxes(rois.reshape(batch_size, -1, rois.shape[-1]), box_preds)
+
+    def roi_grid_pool(self, batch_dict):
+        """pvrcnn_head.py:64-109: the code RoIGridPool runs (com_amd/hotpath/pvrcnn_stage2.py)"""
+        return roi_grid_pool(self.roi_grid_pool_layer, batch_dict, self.grid_size)
+
+    def forward(self, batch_dict):
+        """pvrcnn_head.py:134-175"""
+        nms = _get(self.model_cfg, 'NMS_CONFIG')
+        targets_dict = self.proposal_layer(batch_dict, nms_config=_get(nms, 'TRAIN' if self.training else 'TEST'))
+        if self.training:
+            targets_dict = batch_dict.get('roi_targets_dict', None)
+            if targets_dict is None:
+                targets_dict = self.assign_targets(batch_dict)
+                batch_dict['rois'] = targets_dict['rois']
+                batch_dict['roi_labels'] = targets_dict['roi_labels']
+        pooled_features = self.roi_grid_pool(batch_dict)  # (BxN, 6x6x6, C)
+        grid_size = self.grid_size
+        batch_size_rcnn = pooled_features.shape[0]
+        pooled_features = pooled_features.permute(0, 2, 1).contiguous().view(batch_size_rcnn, -1, grid_size, grid_size, grid_size)
+        shared_features = self.shared_fc_layer(pooled_features.view(batch_size_rcnn, -1, 1))
+        rcnn_cls = self.cls_layers(shared_features).transpose(1, 2).contiguous().squeeze(dim=1)  # (B, 1 or 2)
+        rcnn_reg = self.reg_layers(shared_features).transpose(1, 2).contiguous().squeeze(dim=1)  # (B, C)
+        if not self.training:
+            batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(
+                batch_size=batch_dict['batch_size'], rois=batch_dict['rois'], cls_preds=rcnn_cls, box_preds=rcnn_reg)
+            batch_dict['batch_cls_preds'] = batch_cls_preds
+            batch_dict['batch_box_preds'] = batch_box_preds
+            batch_dict['cls_preds_normalized'] = False
+        else:
+            targets_dict['rcnn_cls'] = rcnn_cls
+            targets_dict['rcnn_reg'] = rcnn_reg
+            self.forward_ret_dict = targets_dict
+        return batch_dict

@@ -1305,6 +1305,81 @@ int pcd_roiaware_pool3d_backward(const int *pts_idx_of_voxels, const int *argmax
                                  int out_y, int out_z, int channels, int max_pts_each_voxel, int pool_method, int num_pts,
                                  float *grad_in, void *stream);
 
+/* ============================================================================================
+ * (f6) The second half of PVRCNNHead: proposal targets, the RoI loss, box decoding -- replaces the host loops of
+ *      pcdet/models/roi_heads/target_assigner/proposal_target_layer.py and pcdet/models/roi_heads/roi_head_template.py.
+ *      code_size is 7: rois [batch][num_rois][7], gt_boxes [batch][num_gt][8] (7 box floats + class), all f32 and dense.
+ *      No entry point reads anything back, allocates or has a data-dependent shape: all are capturable.
+ *   pcd_roi_head_max_overlaps: proposal_target_layer.py:89-105 (the trailing-zero-row scan, boxes_iou3d_gpu + torch.max)
+ *                and :195-228 (get_max_iou_with_same_class).  Per frame the valid GT rows are those up to the last row whose
+ *                eight values do not sum to 0 (none: ONE all-zero box).  max_overlaps f32 / gt_assignment int32
+ *                [batch][num_rois]: the largest rotated 3-D IoU (iou3d_nms_utils.py:49-82, clamp 1e-6; the BEV overlap is
+ *                the code of pcd_boxes_overlap_bev) and the LOWEST index of a GT row that attains it.  same_class != 0: only
+ *                GT rows with (long)class == roi_labels[.] compete; a RoI without one gets 0.0 and index 0.
+ *   pcd_roi_head_sample_targets: proposal_target_layer.py:13-62, :107-192 (subsample_rois, sample_bg_inds, gather, labels)
+ *                + roi_head_template.py:104-134 (canonical transformation).  One workgroup per frame.  Lists in ascending RoI
+ *                order: fg (iou >= min(reg_fg, cls_fg)), hard bg (cls_bg_lo <= iou < reg_fg), easy bg (iou < cls_bg_lo).
+ *                uniforms f32 [batch][num_rois + rois_per_image] in [0, 1): the first num_rois are one key per RoI -- the
+ *                k foreground RoIs with the smallest keys fill the first k slots in ascending key order (ties by index); the
+ *                last rois_per_image are one per slot j -- a slot drawn with replacement takes
+ *                list[min(int(u_j * n), n - 1)] (f32 product).  hard_bg_table int32 [rois_per_image + 1] (device):
+ *                entry bg = int(bg * HARD_BG_RATIO), computed on the host.  Slots: fg, hard bg, easy bg.  Outputs for the
+ *                slots: sampled_inds int32 [batch][R], rois [..][7], roi_scores, roi_labels int64, gt_iou_of_rois,
+ *                gt_of_rois_src [..][8], gt_of_rois [..][8] (centre and heading relative to the RoI, rotated by -ry, heading
+ *                folded into [-pi/2, pi/2]), reg_valid_mask int64 (iou > reg_fg), rcnn_cls_labels: f32 soft labels
+ *                (PCD_ROI_SCORE_ROI_IOU) or int64 with -1 (PCD_ROI_SCORE_CLS).  given_inds != 0: sampled_inds is an INPUT
+ *                (clamped to the RoIs) and only the gather runs (uniforms / hard_bg_table may be NULL).  A frame with
+ *                neither fg nor bg (NaN IoUs; the reference raises) takes RoI 0 for every slot and adds 1 to *status
+ *                (device int32, cleared by the caller).  PCD_ERR_UNSUPPORTED: num_rois or rois_per_image above 2048.
+ *   pcd_roi_head_loss_forward / _backward: roi_head_template.py:136-231.  rcnn_cls [num_rows] (elements cls_stride
+ *                apart), rcnn_reg [num_rows][7] (rows reg_stride apart), f32 or bf16; rcnn_cls_labels f32, reg_valid_mask
+ *                int64, rois / gt_of_rois / gt_of_rois_src as written by pcd_roi_head_sample_targets.  BinaryCrossEntropy on
+ *                the f32 sigmoid with both logs clamped at -100, rows with label >= 0, / max(count, 1); smooth-L1 (beta 1/9,
+ *                code_weights_host: 7 HOST floats, nan target -> prediction) on ResidualCoder targets against the RoI with
+ *                centre and heading zeroed (sizes clamped at 1e-5) over rows with reg_valid_mask > 0, / max(fg_sum, 1);
+ *                corner_loss != 0: + the corner regulariser (decode, rotate by the RoI heading, + centre; min over the GT and
+ *                its pi-flipped copy of the eight corner distances, smooth-L1 beta 1, mean), 0 when fg_sum == 0.  out = 5
+ *                device floats: rcnn_loss, rcnn_loss_cls, rcnn_loss_reg (corner included), rcnn_loss_corner, fg_sum.  aux =
+ *                4 device floats the backward reads: max(valid rows, 1), max(fg_sum, 1), the smooth-L1 term alone (what the
+ *                reference logs as rcnn_loss_reg), 0.  One workgroup, fixed summation order, no atomics: bit-reproducible.
+ *                backward: d_rcnn_cls / d_rcnn_reg (layout and dtype of the inputs, every element written) = *grad_out x the
+ *                derivative; the derivative through a zero corner distance is 0.
+ *   pcd_roi_head_decode: generate_predicted_boxes (roi_head_template.py:233-261): ResidualCoder.decode_torch against the RoI
+ *                with its centre zeroed, rotation by the RoI heading, + centre.  box_preds [num_rows][7] f32 or bf16 (rows
+ *                row_stride apart), rois [num_rows][7]; batch_box_preds f32 [num_rows][7].
+ * ============================================================================================ */
+#define PCD_ROI_SCORE_ROI_IOU 0
+#define PCD_ROI_SCORE_CLS 1
+struct PcdRoiSampler {
+    int batch, num_rois, num_gt, rois_per_image;
+    int fg_rois_per_image;      /* int(np.round(FG_RATIO * ROI_PER_IMAGE)) */
+    int score_type;             /* PCD_ROI_SCORE_* */
+    int given_inds;
+    float reg_fg_thresh, cls_fg_thresh, cls_bg_thresh, cls_bg_thresh_lo;
+    float cls_span;             /* CLS_FG_THRESH - CLS_BG_THRESH, the difference taken in double */
+};
+int pcd_roi_head_max_overlaps(const float *rois, const long long *roi_labels, const float *gt_boxes, int batch, int num_rois,
+                              int num_gt, int same_class, float *max_overlaps, int *gt_assignment, void *stream);
+int pcd_roi_head_sample_targets(const struct PcdRoiSampler *cfg, const float *rois, const float *roi_scores,
+                                const long long *roi_labels, const float *gt_boxes, const float *max_overlaps,
+                                const int *gt_assignment, const float *uniforms, const int *hard_bg_table, int *sampled_inds,
+                                float *out_rois, float *out_roi_scores, long long *out_roi_labels, float *out_gt_iou_of_rois,
+                                float *out_gt_of_rois_src, float *out_gt_of_rois, long long *out_reg_valid_mask,
+                                void *out_rcnn_cls_labels, int *status, void *stream);
+int pcd_roi_head_loss_forward(const void *rcnn_cls, int cls_dtype, long long cls_stride, const void *rcnn_reg, int reg_dtype,
+                              long long reg_stride, const float *rcnn_cls_labels, const long long *reg_valid_mask,
+                              const float *rois, const float *gt_of_rois, const float *gt_of_rois_src, int num_rows,
+                              const float *code_weights_host, float cls_weight, float reg_weight, float corner_weight,
+                              int corner_loss, float *out, float *aux, void *stream);
+int pcd_roi_head_loss_backward(const void *rcnn_cls, int cls_dtype, long long cls_stride, const void *rcnn_reg, int reg_dtype,
+                               long long reg_stride, const float *rcnn_cls_labels, const long long *reg_valid_mask,
+                               const float *rois, const float *gt_of_rois, const float *gt_of_rois_src, int num_rows,
+                               const float *code_weights_host, float cls_weight, float reg_weight, float corner_weight,
+                               int corner_loss, const float *aux, const float *grad_out, void *d_rcnn_cls, void *d_rcnn_reg,
+                               void *stream);
+int pcd_roi_head_decode(const float *rois, const void *box_preds, int dtype, long long row_stride, int num_rows,
+                        float *batch_box_preds, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
