@@ -6,264 +6,92 @@ stream; torch is only the owner of device memory and streams.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libpcdops_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-PCD_F32 = 0
-PCD_BF16 = 1
-
-_vp = ctypes.c_void_p
-_i = ctypes.c_int
-_sz = ctypes.c_size_t
-
-# name -> (restype, argtypes); must list EVERY symbol declared in include/pcd_ops.h
-PROTOTYPES = {
-    "pcd_version": (_i, []),
-    "pcd_error_string": (ctypes.c_char_p, [_i]),
-    "pcd_build_arch": (ctypes.c_char_p, []),
-    "pcd_last_hip_error_string": (ctypes.c_char_p, []),
-    "pcd_set_last_hip_error": (None, [_i]),
-    "pcd_set_option": (_i, [ctypes.c_char_p, _i]),
-    "pcd_get_option": (_i, [ctypes.c_char_p, _vp]),
-    "pcd_voxelize_hard_workspace_bytes": (_sz, [_i, _i, _i]),
-    "pcd_voxelize_hard": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                               _i, _vp, _vp, _sz, _vp]),
-    "pcd_voxelize_hard_sorted_workspace_bytes": (_sz, [_i, _i, _i, _vp, _vp, _i]),
-    "pcd_voxelize_hard_sorted_rank_words": (_i, [_i, _vp, _vp, _i, _vp, _vp]),
-    "pcd_voxelize_hard_sorted": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                                      _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_voxelize_hard_yxz_workspace_bytes": (_sz, [_i, _i, _i, _vp, _vp, _i, _i]),
-    "pcd_voxelize_hard_yxz": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                                   _i, _vp, _i, _vp, _sz, _vp, _sz, _vp]),
-    "pcd_voxelize_hard_host": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
-    "pcd_mean_vfe": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "pcd_voxelize_dynamic_workspace_bytes": (_sz, [_i, _i, _i, _vp, _vp]),
-    "pcd_voxelize_dynamic_mean": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_segment_max_workspace_bytes": (_sz, [_i, _i]),
-    "pcd_segment_max": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_segment_max_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "pcd_rulebook_subm_workspace_bytes": (_sz, [_i, _i]),
-    "pcd_rulebook_subm": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "pcd_rulebook_conv_workspace_bytes": (_sz, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_rulebook_conv_classes_workspace_bytes": (_sz, [_i]),
-    "pcd_rulebook_conv_classes": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_sparse_conv_dgrad_classes": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp,
-                                           _i, _vp, _vp, _vp]),
-    "pcd_sparse_conv_dgrad_classes_tiles": (_i, [_i, _i]),
-    "pcd_sparse_conv_gather_gemm_tiles": (_i, [_i, _i, _i, _i, _i]),
-    "pcd_sparse_conv_gather_gemm_tiles_dir": (_i, [_i, _i, _i, _i, _i, _i]),
-    "pcd_sparse_conv_gather_gemm_variant": (_i, [_i, _i, _i, _i, _i, _i]),
-    "pcd_subm_window_tile_rows": (_i, [_i, _i]),
-    "pcd_subm_window_partial_rows": (_i, [_i, _i]),
-    "pcd_subm_window_set_trace": (_i, [_vp]),
-    "pcd_subm_window_plan_bytes": (_sz, [_i, _i, _i]),
-    "pcd_subm_window_plan": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
-    "pcd_subm_window_plan_cm": (_i, [_vp, _i, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _vp, _i, _vp, _vp]),
-    "pcd_subm_window_packed_weight_bytes": (_sz, [_i, _i]),
-    "pcd_subm_window_pack_weight": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "pcd_subm_window_pack_weights_batched": (_i, [_vp, _i, _i, _vp]),
-    "pcd_subm_window_wgrad_splits": (_i, [_i]),
-    "pcd_sparse_conv_subm_window_wgrad": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_sparse_conv_subm_window": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "pcd_sparse_conv_subm_window_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "pcd_rulebook_conv_rank_layout": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_rulebook_subm_ranked_workspace_bytes": (_sz, [_i, _i]),
-    "pcd_rulebook_subm_pairs_workspace_bytes": (_sz, [_i, _i]),
-    "pcd_rulebook_subm_pairs": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "pcd_rulebook_conv_pairs": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "pcd_rulebook_subm_ranked": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz,
-                                      _vp, _i]),
-    "pcd_rulebook_subm_ranked4": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz,
-                                       _vp, _i]),
-    "pcd_colmap_bytes": (_sz, [_i, _vp, _i]),
-    "pcd_colmap_counts_offset": (_sz, [_i, _vp, _i, _vp]),
-    "pcd_colmap_from_rows_workspace_bytes": (_sz, [_i, _vp]),
-    "pcd_colmap_from_rows": (_i, [_vp, _i, _vp, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
-    "pcd_rulebook_subm_cm_workspace_bytes": (_sz, [_i]),
-    "pcd_rulebook_subm_cm": (_i, [_vp, _i, _i, _vp, _vp, _sz, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "pcd_rulebook_conv_cm_workspace_bytes": (_sz, [_i, _i, _vp, _vp, _vp, _vp]),
-    "pcd_rulebook_conv_cm_count": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _sz, _vp]),
-    "pcd_rulebook_conv_cm_fill": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp,
-                                       _vp, _i, _vp, _vp, _sz, _vp]),
-    "pcd_rulebook_conv_cm_build": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp,
-                                        _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_conv_out_shape": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_rulebook_conv_count": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _i]),
-    "pcd_rulebook_conv_fill": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp,
-                                    _vp, _sz, _vp, _i]),
-    "pcd_rulebook_conv_build": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp,
-                                     _i, _vp, _vp, _vp, _sz, _vp, _i]),
-    "pcd_debug_stamp": (_i, [_vp, _vp]),
-    "pcd_debug_stream_create_cu_mask": (_i, [_vp, _i, _vp]),
-    "pcd_debug_spin": (_i, [_i, ctypes.c_ulonglong, _vp, _vp]),
-    "pcd_debug_spin_shape": (_i, [_i, _i, _i, _i, ctypes.c_ulonglong, _vp]),
-    "pcd_pull_from_host": (_i, [_vp, _i, _vp, _vp, _sz, _i, _vp]),
-    "pcd_counter_add": (_i, [_vp, _i, _vp]),
-    "pcd_conv2d_packed_weight_bytes": (_sz, [_i, _i, _i]),
-    "pcd_conv2d_pack_weight": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "pcd_conv2d_pack_weights_batched": (_i, [_vp, _i, _i, _vp]),
-    "pcd_conv2d_3x3_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
-    "pcd_conv2d_3x3_nhwc_ld": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
-    "pcd_conv2d_wgrad_3x3_splits": (_i, [_i, _i, _i, _i, _i]),
-    "pcd_conv2d_wgrad_3x3_nhwc": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "pcd_conv2d_3x3_tiles": (_i, [_i, _i, _i]),
-    "pcd_conv2d_3x3_nhwc_bn": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
-    "pcd_conv2d_planes_nhwc": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp]),
-    "pcd_sparse_conv_gather_gemm_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
-    "pcd_sparse_conv_wgrad_f32": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "pcd_packed_weight_bytes": (_sz, [_i, _i, _i, _i]),
-    "pcd_pack_weight": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "pcd_pack_weights_batched": (_i, [_vp, _i, _i, _vp]),
-    "pcd_sparse_conv_gather_gemm": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp,
-                                         _vp]),
-    "pcd_sparse_conv_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "pcd_sparse_conv_wgrad": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
-    "pcd_sparse_conv_wgrad_v2": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
-    "pcd_sparse_conv_wgrad_classes": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
-                                           _vp, _i]),
-    "pcd_sparse_conv_dgrad_classes_v2": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp,
-                                              _vp, _vp]),
-    "pcd_sparse_conv_gather_gemm_packed": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
-    "pcd_rulebook_conv_cm_build_compact": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _i,
-                                                _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_rulebook_conv_expand_nbr_out": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "pcd_rulebook_conv_expand_nbr_in": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "pcd_sparse_conv_wgrad_reduce": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
-    "pcd_sparse_conv_wgrad_reduce_batched": (_i, [_vp, _i, _vp]),
-    "pcd_sparse_conv_wgrad_os_splits": (_i, [_i, _i, _i, _i]),
-    "pcd_sparse_conv_wgrad_os": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
-    "pcd_bev_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "pcd_bev_scatter": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "pcd_bev_gather": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "pcd_bev_scatter_nhwc": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "pcd_bev_gather_nhwc": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "pcd_bn_workspace_bytes": (_sz, [_i]),
-    "pcd_col_sum": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_bn_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _i,
-                            _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
-    "pcd_bn_forward_ld": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _i,
-                               _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
-    "pcd_bn_backward_ld": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
-                                _i, _vp, _vp, _sz, _vp]),
-    "pcd_adam_flat_workspace_bytes": (_sz, []),
-    "pcd_adam_flat_step": (_i, [_vp, _vp, _vp, _vp, _sz, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _sz,
-                                _vp]),
-    "pcd_adam_flat_step_v2": (_i, [_vp, _vp, _vp, _vp, _sz, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                   ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp,
-                                   _vp, _sz, _vp]),
-    "pcd_adam_flat_step_v3": (_i, [_vp, _vp, _vp, _vp, _sz, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                   ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _i,
-                                   _vp, _vp, _vp, _sz, _vp]),
-    "pcd_adam_flat_step_v4": (_i, [_vp, _vp, _i, _vp, _vp, _sz, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                   ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _i,
-                                   _vp, _vp, _vp, _sz, _vp]),
-    "pcd_stream_capture_id": (_i, [_vp, _vp]),
-    "pcd_dot_bf16_workspace_bytes": (_sz, []),
-    "pcd_dot_bf16": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
-    "pcd_scale_bf16": (_i, [_vp, _vp, _sz, _vp, _vp]),
-    "pcd_static_overflow_check": (_i, [_vp, _i, _vp, _vp]),
-    "pcd_com_cluster_groups": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
-    "pcd_com_assign_workspace_bytes": (_sz, [_i, _i]),
-    "pcd_com_assign_targets": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, ctypes.c_float, _i, _vp, _vp,
-                                    _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "pcd_com_loss_workspace_bytes": (_sz, [_i, _i]),
-    "pcd_com_loss_forward": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i,
-                                  _vp, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
-                                  _vp, _sz, _vp]),
-    "pcd_com_loss_backward": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i,
-                                   _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
-    "pcd_centerhead_loss_workspace_bytes": (_sz, [_i]),
-    "pcd_centerhead_loss_forward": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i,
-                                         _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _sz, _vp]),
-    "pcd_centerhead_loss_backward": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp,
-                                          _vp, _vp, _i, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
-    "pcd_centerhead_assign_workspace_bytes": (_sz, [_i, _i]),
-    "pcd_centerhead_assign_targets": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, ctypes.c_float, _i, _vp,
-                                           _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_anchor_assign_workspace_bytes": (_sz, [_i, _i]),
-    "pcd_anchor_assign_targets": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_anchor_loss_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "pcd_anchor_loss_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp,
-                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _sz, _vp]),
-    "pcd_anchor_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp,
-                                      _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp]),
-    "pcd_anchor_decode": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, ctypes.c_float,
-                               ctypes.c_float, _vp, _vp, _vp]),
-    "pcd_anchor_cur_cluster": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
-    "pcd_anchor_cur_groups": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "pcd_anchor_cur_loss_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "pcd_anchor_cur_loss_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp,
-                                         ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp,
-                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_anchor_cur_loss_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i,
-                                          _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp,
-                                          _vp, _vp]),
-    "pcd_ball_query_stack": (_i, [_i, _i, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_group_points_stack": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_group_points_stack_grad": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_stack_farthest_point_sampling": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_stack_fps_coop_workspace_bytes": (_sz, [_i]),
-    "pcd_stack_fps_buckets_workspace_bytes": (_sz, [_i, _i]),
-    "pcd_stack_farthest_point_sampling_buckets": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
-    "pcd_stack_farthest_point_sampling_coop": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
-    "pcd_three_nn_stack": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_three_interpolate_stack": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_three_interpolate_stack_grad": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_voxel_query_stack": (_i, [_i, _i, _i, _i, _i, ctypes.c_float, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_fp8_packed_weight_bytes": (_sz, [_i, _i, _i]),
-    "pcd_fp8_pack_weight": (_i, [_vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp]),
-    "pcd_fp8_quantize": (_i, [_vp, _i, _i, _vp, _i, _i, _i, ctypes.c_float, _vp, _vp]),
-    "pcd_fp8_dequantize": (_i, [_vp, _sz, ctypes.c_float, _vp, _vp]),
-    "pcd_sparse_conv_gather_gemm_fp8": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i,
-                                             ctypes.c_float, _vp, _i, _i, _vp]),
-    "pcd_pillar_decorate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "pcd_pfn_relu_pool": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "pcd_pfn_relu_pool_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "pcd_boxes_overlap_bev": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp]),
-    "pcd_boxes_iou_bev_host": (_i, [_vp, _i, _vp, _i, _vp]),
-    "pcd_points_in_boxes_host": (_i, [_vp, _i, _vp, _i, _vp]),
-    "pcd_points_in_boxes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "pcd_point_head_assign_targets": (_i, [_vp, _i, _vp, _i, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i, _vp, _vp,
-                                           _vp]),
-    "pcd_point_head_loss_workspace_bytes": (_sz, [_i]),
-    "pcd_point_head_loss_forward": (_i, [_vp, _i, ctypes.c_longlong, _vp, _vp, _i, _i, ctypes.c_float, _vp, _vp, _sz, _vp]),
-    "pcd_point_head_loss_backward": (_i, [_vp, _vp, _i, ctypes.c_longlong, _vp, _vp, _i, _i, ctypes.c_float, _vp, _vp]),
-    "pcd_roiaware_pool3d_forward": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "pcd_roiaware_pool3d_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "pcd_roi_head_max_overlaps": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "pcd_roi_head_sample_targets": (_i, [_vp] * 20),
-    "pcd_roi_head_loss_forward": (_i, [_vp, _i, ctypes.c_longlong, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _i, _vp,
-                                       ctypes.c_float, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp]),
-    "pcd_roi_head_loss_backward": (_i, [_vp, _i, ctypes.c_longlong, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _i, _vp,
-                                        ctypes.c_float, ctypes.c_float, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp]),
-    "pcd_roi_head_decode": (_i, [_vp, _vp, _i, ctypes.c_longlong, _i, _vp, _vp]),
-    "pcd_nms_workspace_bytes": (_sz, [_i]),
-    "pcd_nms_bev": (_i, [_vp, _i, ctypes.c_float, _i, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_centerhead_postproc_workspace_bytes": (_sz, [_vp, _vp]),
-    "pcd_centerhead_postproc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pcd_bn_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
-                             _i, _vp, _vp, _sz, _vp]),
-    "pcd_bn_backward_colsum_rows": (_i, [_i, _i, _i]),
-    "pcd_col_sum_finalize": (_i, [_vp, _i, _vp]),
-}
-
-_lib = None
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "pcd_ops.h")
 
 
 class PcdError(RuntimeError):
     pass
 
 
+# The header is the one record of the ABI: prototypes and integer constants are parsed from it at import (plain `re` over
+# the few shapes its declarations have -- regularise an odd declaration in the header rather than teach this C).
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong,
+            "uint64_t": ctypes.c_ulonglong}
+
+
+def _strip_comments(text):
+    return re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+
+
+def _ctype(c_type, decl):
+    """ctypes type of one C return / parameter type (its name already removed); an unknown one is an error, never a guess."""
+    words = [w for w in c_type.replace("*", " * ").replace("[", " * [").split() if w != "const"]
+    if "*" in words:
+        return ctypes.c_char_p if words == ["char", "*"] else ctypes.c_void_p
+    try:
+        return _SCALARS[" ".join(words)]
+    except KeyError:
+        raise PcdError(f"include/pcd_ops.h: unknown type '{c_type.strip()}' in declaration `{decl}`") from None
+
+
+def parse_prototypes(text):
+    """name -> (restype, argtypes) of every `ret pcd_name(args);` in the text of a C header."""
+    text = re.sub(r"^[ \t]*#.*$", " ", _strip_comments(text), flags=re.M)              # preprocessor lines
+    text = re.sub(r"\{[^{}]*\}", " ", text).replace('extern "C" {', " ")                 # struct / enum bodies
+    protos = {}
+    for stmt in text.split(";"):
+        decl = " ".join(stmt.split()).lstrip("} ")
+        m = re.fullmatch(r"(.*?)\b(pcd_\w+) ?\((.*)\)", decl)
+        if m is None:
+            if decl and decl.split()[0] not in ("typedef", "struct", "enum"):
+                raise PcdError(f"include/pcd_ops.h: cannot parse `{decl}`")
+            continue
+        ret, name, params = m.groups()
+        params = [] if params.strip() == "void" else [q.strip() for q in params.split(",")]
+        # a parameter is `type name` or `type name[n]`: the last identifier is its name
+        args = [_ctype(re.sub(r"\w+\s*(\[[^\]]*\])?$", r"\1", q), decl) for q in params]
+        protos[name] = (None if ret.strip() == "void" else _ctype(ret, decl), args)
+    return protos
+
+
+def parse_constants(text):
+    """name -> value of every `#define PCD_NAME <integer expression>` (literals, negatives, earlier PCD_ names)."""
+    consts = {}
+    for name, expr in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(PCD_\w+)[ \t]+(\S.*)$", _strip_comments(text), flags=re.M):
+        try:
+            if not re.fullmatch(r"[\w\s()+*-]+", expr):
+                raise SyntaxError(expr)
+            consts[name] = int(eval(expr, {"__builtins__": {}}, consts))
+        except (SyntaxError, NameError, TypeError):
+            raise PcdError(f"include/pcd_ops.h: #define {name} {expr.strip()} is not an integer expression") from None
+    return consts
+
+
+with open(HEADER) as _f:
+    _header_text = _f.read()
+PROTOTYPES = parse_prototypes(_header_text)      # name -> (restype, argtypes) of EVERY function include/pcd_ops.h declares
+CONSTANTS = parse_constants(_header_text)        # ... and its integer #defines, also module attributes: _lib.PCD_BN_EXT_MID
+globals().update(CONSTANTS)
+del _f, _header_text
+# the short names some of them had before they were read from the header
+for _k in ("COLSUM_MAX_JOBS", "WGRAD_MAX_JOBS", "COUNT_CHECK_MAX", "POSTPROC_MAX_HEADS", "POSTPROC_MAX_CLASSES", "POSTPROC_MAX_K",
+           "BN_MID_ROWS", "BN_EXT_MID", "BN_COUNTER_STRIDE"):
+    globals()[_k] = CONSTANTS["PCD_" + _k]
+
+_lib = None
+
+
 class PcdColsumJob(ctypes.Structure):
     """include/pcd_ops.h: struct PcdColsumJob."""
     _fields_ = [("partial", ctypes.c_void_p), ("out", ctypes.c_void_p), ("rows", ctypes.c_int), ("c", ctypes.c_int)]
-
-
-COLSUM_MAX_JOBS = 32
 
 
 class PcdWgradReduceJob(ctypes.Structure):
@@ -273,18 +101,9 @@ class PcdWgradReduceJob(ctypes.Structure):
                 ("layout", ctypes.c_int), ("cout_write", ctypes.c_int), ("cin_write", ctypes.c_int)]
 
 
-WGRAD_MAX_JOBS = 32
-COUNT_CHECK_MAX = 24
-
-
 class PcdCountCheck(ctypes.Structure):
     """include/pcd_ops.h: struct PcdCountCheck (static-shape overflow guard)."""
     _fields_ = [("count", ctypes.c_void_p * COUNT_CHECK_MAX), ("cap", ctypes.c_int32 * COUNT_CHECK_MAX)]
-
-
-POSTPROC_MAX_HEADS = 8     # include/pcd_ops.h: PCD_POSTPROC_MAX_HEADS
-POSTPROC_MAX_CLASSES = 16  # include/pcd_ops.h: PCD_POSTPROC_MAX_CLASSES
-POSTPROC_MAX_K = 4096      # include/pcd_ops.h: PCD_POSTPROC_MAX_K
 
 
 class PcdPostprocHead(ctypes.Structure):
@@ -302,11 +121,6 @@ class PcdPostprocConfig(ctypes.Structure):
                 ("voxel_y", ctypes.c_float), ("pc_x", ctypes.c_float), ("pc_y", ctypes.c_float)]
 
 
-BN_MID_ROWS = 16          # include/pcd_ops.h: PCD_BN_MID_ROWS
-BN_EXT_MID = -1           # include/pcd_ops.h: PCD_BN_EXT_MID
-BN_COUNTER_STRIDE = 32    # include/pcd_ops.h: PCD_BN_COUNTER_STRIDE
-
-
 class PcdComCurriculum(ctypes.Structure):
     """include/pcd_ops.h: struct PcdComCurriculum (LOSS_CURRICULUM of the COM head)."""
     _fields_ = [("ucl", ctypes.c_int), ("fix_threshold", ctypes.c_int), ("straight", ctypes.c_int),
@@ -316,22 +130,11 @@ class PcdComCurriculum(ctypes.Structure):
                 ("conf_classes", ctypes.c_int), ("conf_groups", ctypes.c_int)]
 
 
-PCD_COM_CLUSTER_X5 = 0
-
-
 class PcdAnchorCurriculum(ctypes.Structure):
     """include/pcd_ops.h: struct PcdAnchorCurriculum (LOSS_CURRICULUM of the anchor curriculum head)."""
     _fields_ = [("ucl", ctypes.c_int), ("oto", ctypes.c_int), ("sm", ctypes.c_int), ("sma", ctypes.c_int),
                 ("norm", ctypes.c_int), ("smt", ctypes.c_float), ("pos_norm", ctypes.c_float), ("neg_norm", ctypes.c_float),
                 ("offset", ctypes.c_double), ("ema", ctypes.c_double)]
-
-
-PCD_ANCHOR_CUR_GROUPS = 96
-PCD_ANCHOR_CUR_ACCUM = 3 + 2 * PCD_ANCHOR_CUR_GROUPS
-PCD_ANCHOR_CUR_CLUSTER_BASE, PCD_ANCHOR_CUR_CLUSTER_X1, PCD_ANCHOR_CUR_CLUSTER_CAR, PCD_ANCHOR_CUR_CLUSTER_CAR_X2 = 0, 1, 2, 3
-
-
-PCD_ROI_SCORE_ROI_IOU, PCD_ROI_SCORE_CLS = 0, 1
 
 
 class PcdRoiSampler(ctypes.Structure):
@@ -401,7 +204,7 @@ def get_option(key):
 def check(code, what):
     if code != 0:
         msg = lib().pcd_error_string(code).decode()
-        if code == -5:
+        if code == CONSTANTS["PCD_ERR_LAUNCH"]:
             msg += " [" + lib().pcd_last_hip_error_string().decode() + "]"
         raise PcdError(f"{what} failed: {msg} (code {code})")
 
@@ -426,3 +229,29 @@ def ptr(t):
 def stream_ptr():
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def workspace(nbytes, device, floor=256):
+    """A scratch buffer of at least `floor` bytes (a zero-byte query still gets a valid pointer)."""
+    import torch
+    return torch.empty((max(int(nbytes), floor),), dtype=torch.uint8, device=device)
+
+
+def dtype_code(t):
+    """PCD_F32 / PCD_BF16 of a feature tensor."""
+    import torch
+    if t.dtype == torch.float32:
+        return CONSTANTS["PCD_F32"]
+    if t.dtype == torch.bfloat16:
+        return CONSTANTS["PCD_BF16"]
+    raise PcdError(f"unsupported feature dtype {t.dtype} (float32 / bfloat16 only)")
+
+
+def require_device(what, *tensors, verb="needs", allow_none=False):
+    """Raise unless every one of `tensors` is a HIP device tensor (allow_none: None entries pass); returns the first."""
+    import torch
+    for t in tensors:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda) and not (allow_none and t is None):
+            noun = "a HIP device tensor" if len(tensors) == 1 else "HIP device tensors"
+            raise PcdError(f"{what} {verb} {noun} (there is no CPU fallback)")
+    return tensors[0] if tensors else None

@@ -788,16 +788,6 @@ extern "C" int pcd_conv2d_3x3_nhwc_bn(const void *x, int x_cs, int batch, int he
     return PCD_OK;
 }
 
-extern "C" int pcd_conv2d_3x3_nhwc_ld(const void *x, int x_cs, int batch, int height, int width, int cin,
-                                      const void *packed_w, int cout, const float *bias, void *y, int y_cs, void *stream) {
-    return pcd_conv2d_3x3_nhwc_bn(x, x_cs, batch, height, width, cin, packed_w, cout, bias, y, y_cs, nullptr, stream);
-}
-
-extern "C" int pcd_conv2d_3x3_nhwc(const void *x, int batch, int height, int width, int cin, const void *packed_w,
-                                   int cout, const float *bias, void *y, void *stream) {
-    return pcd_conv2d_3x3_nhwc_bn(x, cin, batch, height, width, cin, packed_w, cout, bias, y, cout, nullptr, stream);
-}
-
 
 template <int KIND, bool GATHER>
 static int launch_planes(const void *x, int batch, int hi, int wi, int cin, const void *packed_w, int cout,

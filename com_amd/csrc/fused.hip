@@ -779,17 +779,6 @@ extern "C" int pcd_bn_forward_ld(const void *x, const void *residual, int dtype,
     return PCD_OK;
 }
 
-extern "C" int pcd_bn_forward(const void *x, const void *residual, int dtype, int n, int c,
-                              const float *gamma, const float *beta, float eps, float momentum,
-                              int training, float *running_mean, float *running_var, int relu, void *y,
-                              float *save_mean, float *save_invstd, const int32_t *n_dev,
-                              const float *ext_partial, int ext_rows, void *workspace, size_t workspace_bytes,
-                              void *stream) {
-    return pcd_bn_forward_ld(x, residual, dtype, n, c, gamma, beta, eps, momentum, training, running_mean, running_var,
-                             relu, y, c, save_mean, save_invstd, n_dev, ext_partial, ext_rows, workspace,
-                             workspace_bytes, stream);
-}
-
 __global__ __launch_bounds__(1024) void col_sum_finalize_kernel(const float *__restrict__ partial, int nblocks,
                                                                 int c, float *out) {
     __shared__ double lds[2 * 1024];
@@ -885,18 +874,7 @@ extern "C" int pcd_bn_backward_ld(const void *dy, int dy_ld, const void *x, cons
     return PCD_OK;
 }
 
-extern "C" int pcd_bn_backward(const void *dy, const void *x, const void *y, int dtype, int n, int c,
-                               const float *gamma, const float *beta, const float *save_mean,
-                               const float *save_invstd,
-                               int relu, int training, void *dx, void *dresidual, float *dgamma,
-                               float *dbeta, const int32_t *n_dev, const float *ext_partial, int ext_rows,
-                               float *colsum_partial, void *workspace, size_t workspace_bytes, void *stream) {
-    return pcd_bn_backward_ld(dy, c, x, y, dtype, n, c, gamma, beta, save_mean, save_invstd, relu, training, dx, dresidual,
-                              dgamma, dbeta, n_dev, ext_partial, ext_rows, colsum_partial, workspace, workspace_bytes,
-                              stream);
-}
-
-// rows of the colsum_partial buffer pcd_bn_backward fills ([rows][c] f32): the grid of its apply pass
+// rows of the colsum_partial buffer pcd_bn_backward_ld fills ([rows][c] f32): the grid of its apply pass
 extern "C" int pcd_bn_backward_colsum_rows(int dtype, int n, int c) {
     if (n < 0 || c <= 0 || (dtype != PCD_F32 && dtype != PCD_BF16)) return PCD_ERR_INVALID_ARG;
     if (!shape_ok(c, dtype)) return PCD_ERR_UNSUPPORTED;

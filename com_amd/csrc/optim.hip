@@ -184,34 +184,6 @@ extern "C" int pcd_static_overflow_check(const PcdCountCheck *table_host, int n,
 
 extern "C" size_t pcd_adam_flat_workspace_bytes(void) { return ws_piece(NORM_BLOCKS, sizeof(double)); }
 
-extern "C" int pcd_adam_flat_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n,
-                                  float lr, float beta1, float beta2, float eps, float weight_decay,
-                                  float max_norm, float pre_divisor, float *step_dev, float *norm_out,
-                                  void *workspace, size_t workspace_bytes, void *stream) {
-    return pcd_adam_flat_step_v2(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, max_norm,
-                                 pre_divisor, 0, nullptr, step_dev, norm_out, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pcd_adam_flat_step_v2(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n,
-                                     float lr, float beta1, float beta2, float eps, float weight_decay,
-                                     float max_norm, float pre_divisor, int decoupled_wd, const float *hyper_dev,
-                                     float *step_dev, float *norm_out, void *workspace, size_t workspace_bytes,
-                                     void *stream) {
-    return pcd_adam_flat_step_v3(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, max_norm,
-                                 pre_divisor, decoupled_wd, const_cast<float *>(hyper_dev), nullptr, 0, step_dev,
-                                 norm_out, workspace, workspace_bytes, stream);
-}
-
-extern "C" int pcd_adam_flat_step_v3(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n,
-                                     float lr, float beta1, float beta2, float eps, float weight_decay,
-                                     float max_norm, float pre_divisor, int decoupled_wd, float *hyper_dev,
-                                     const float *schedule_dev, int schedule_len, float *step_dev, float *norm_out,
-                                     void *workspace, size_t workspace_bytes, void *stream) {
-    return pcd_adam_flat_step_v4(param, const_cast<float *>(grad), 0, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay,
-                                 max_norm, pre_divisor, decoupled_wd, hyper_dev, schedule_dev, schedule_len, step_dev, norm_out,
-                                 workspace, workspace_bytes, stream);
-}
-
 extern "C" int pcd_adam_flat_step_v4(float *param, float *grad, int zero_grad, float *exp_avg, float *exp_avg_sq, size_t n,
                                      float lr, float beta1, float beta2, float eps, float weight_decay,
                                      float max_norm, float pre_divisor, int decoupled_wd, float *hyper_dev,

@@ -2000,10 +2000,6 @@ extern "C" int pcd_sparse_conv_gather_gemm_tiles_dir(int n_rows_in, int c_in, in
     return rc == PCD_OK ? tiles : rc;
 }
 
-extern "C" int pcd_sparse_conv_gather_gemm_tiles(int n_rows_in, int c_in, int kvol, int n_rows_out, int c_out) {
-    return pcd_sparse_conv_gather_gemm_tiles_dir(n_rows_in, c_in, kvol, n_rows_out, c_out, 0);
-}
-
 extern "C" int pcd_sparse_conv_gather_gemm_variant(int n_rows_in, int c_in, int kvol, int n_rows_out, int c_out,
                                                    int is_dgrad) {
     int v = -12345;
@@ -2020,17 +2016,6 @@ extern "C" int pcd_sparse_conv_dgrad_classes_tiles(int vcap, int n_rows_in) {
     if (vcap < 0 || n_rows_in < 0) return PCD_ERR_INVALID_ARG;
     if (vcap == 0 || n_rows_in == 0) return 0;
     return (pcd_div_up(pcd_div_up(vcap, 64 * cls_mi(n_rows_in)), 8) + 8) * 8;
-}
-
-extern "C" int pcd_sparse_conv_dgrad_classes(const void *dy, int n_dy_rows, int c_dy, const void *packed_w,
-                                             const int32_t *nbr_in, int nbr_stride, const int *ksize_host,
-                                             const int *stride_host, const int *pad_host, const int *dil_host,
-                                             const int32_t *perm, const int32_t *vstart_dev, int vcap,
-                                             int n_rows_in, int c_in, void *dx, int dx_dtype, const void *addend,
-                                             const PcdBnReduce *bn_reduce, void *stream) {
-    return pcd_sparse_conv_dgrad_classes_v2(dy, n_dy_rows, c_dy, packed_w, nbr_in, nbr_stride, 0, ksize_host, stride_host, pad_host,
-                                            dil_host, perm, vstart_dev, vcap, n_rows_in, c_in, dx, dx_dtype, addend, bn_reduce,
-                                            stream);
 }
 
 // nbr_compact = 1: `nbr_in` is the class-compact table nbr_cls [8][nbr_stride] of pcd_rulebook_conv_cm_build_compact
@@ -2083,15 +2068,6 @@ extern "C" size_t pcd_sparse_conv_wgrad_workspace_bytes(int kvol, int cin, int c
     int splits, per;
     wgrad_plan(pmax, cin, cout, &splits, &per);
     return (size_t)splits * cout * kvol * cin * sizeof(float);
-}
-
-extern "C" int pcd_sparse_conv_wgrad(const void *x, int n_x, int cin_pad, int cin, const void *dy, int n_dy,
-                                     int cout,
-                                     const int32_t *pairs, const int32_t *pair_num, int kvol, int pmax,
-                                     float *dweight, void *workspace, size_t workspace_bytes,
-                                     void *stream) {
-    return pcd_sparse_conv_wgrad_v2(x, n_x, nullptr, cin_pad, cin, dy, n_dy, cout, pairs, pair_num, kvol, pmax, dweight,
-                                    workspace, workspace_bytes, stream);
 }
 
 static int wgrad_impl(const void *x, int n_x, const int32_t *n_x_dev, int cin_pad, int cin, const void *dy, int n_dy, int cout,
@@ -2192,7 +2168,7 @@ extern "C" int pcd_sparse_conv_wgrad_reduce(int kvol, int cin, int cout, int pma
     PCD_ENTER();
     if (kvol <= 0 || cin <= 0 || cout <= 0 || pmax < 0 || !dweight) return PCD_ERR_INVALID_ARG;
     size_t n = (size_t)cout * kvol * cin;
-    if (pmax == 0) return PCD_OK;  // pcd_sparse_conv_wgrad already zeroed dweight
+    if (pmax == 0) return PCD_OK;  // pcd_sparse_conv_wgrad_v2 already zeroed dweight
     if (!workspace) return PCD_ERR_WORKSPACE;
     if (wgrad128_use(cin, cout)) {
         wgrad_tiles_reduce_kernel<<<(unsigned)kvol * 16, 256, 0, (hipStream_t)stream>>>(workspace, kvol, dweight);
@@ -2222,7 +2198,7 @@ extern "C" int pcd_sparse_conv_wgrad_reduce_batched(const PcdWgradReduceJob *job
             q.cout_write < 0 || q.cout_write > q.cout || q.cin_write < 0 || q.cin_write > q.cin ||
             (q.cin_write > 0 && q.cin_write < q.cin && (q.layout != 0 || q.splits <= 0)))
             return PCD_ERR_INVALID_ARG;
-        if (q.pmax == 0 && q.splits <= 0) continue;   // pcd_sparse_conv_wgrad already zeroed dweight
+        if (q.pmax == 0 && q.splits <= 0) continue;   // pcd_sparse_conv_wgrad_v2 already zeroed dweight
         if (!q.workspace) return PCD_ERR_WORKSPACE;
         int splits, per;
         if (q.splits <= 0 && wgrad128_use(q.cin, q.cout)) {

@@ -166,7 +166,7 @@ def one_cycle(step, total_steps, lr_max=3e-3, moms=(0.95, 0.85), div_factor=10.0
 
 class FlatAdam:
     """clip_grad_norm_ + Adam on the flat buffers of a FlatGradBucket with flattened parameters, through
-    pcd_adam_flat_step_v2: two passes over the buffers in three launches instead of torch's norm + scalar kernels +
+    pcd_adam_flat_step_v4: two passes over the buffers in three launches instead of torch's norm + scalar kernels +
     scaling pass + multi-tensor Adam.  `step()` expects bucket.flat to hold the SUM of the ranks' gradients
     (all_reduce_sum) and divides by `world` itself.
 
@@ -200,7 +200,7 @@ class FlatAdam:
             self._hyper_host = self._hyper_host.pin_memory()
         self._hyper_ev = [None] * 64
         self._hyper_i = 0
-        self.ws = torch.empty((max(int(L.lib().pcd_adam_flat_workspace_bytes()), 256),), dtype=torch.uint8, device=p.device)
+        self.ws = L.workspace(L.lib().pcd_adam_flat_workspace_bytes(), p.device)
         self.schedule = None
 
     @property

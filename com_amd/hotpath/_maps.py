@@ -6,7 +6,8 @@ from types import SimpleNamespace
 import torch
 
 from .. import _lib as L
-from ..ops import _dtype_code as dtype_code  # noqa: F401
+
+dtype_code = L.dtype_code
 
 
 def like(t):

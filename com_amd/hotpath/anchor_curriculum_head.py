@@ -48,20 +48,14 @@ SAVED_FLOATS = 8          # com_amd/csrc/anchorhead_common.h: SV_FLOATS
 TABLE_FLOATS = 4          # include/pcd_ops.h: epoch_table row
 
 
-def _dev(t, what):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda):
-        raise L.PcdError(f"{what} needs a HIP device tensor (there is no CPU fallback)")
-    return t
-
-
 def cluster(gt_boxes, true_object, occupancy_ratio, facade_type, variant=L.PCD_ANCHOR_CUR_CLUSTER_BASE):
     """[B, M] int64 difficulty groups of one of the four `cluster` methods.  true_object=None (the reference would fail
     on `None == 1`) is rejected."""
     if true_object is None:
         raise L.PcdError("cluster needs data_dict['true_object'] (COMAug's marker of real vs pasted objects)")
-    gt = _dev(gt_boxes, "cluster").contiguous().float()
+    gt = L.require_device("cluster", gt_boxes).contiguous().float()
     B, M, code = gt.shape
-    to, occ, fac = (_dev(t, "cluster").contiguous().float() for t in (true_object, occupancy_ratio, facade_type))
+    to, occ, fac = (L.require_device("cluster", t).contiguous().float() for t in (true_object, occupancy_ratio, facade_type))
     assert to.shape == (B, M) and occ.shape == (B, M) and fac.shape == (B, M)
     group = torch.empty((B, M), dtype=torch.int64, device=gt.device)
     L.check(L.lib().pcd_anchor_cur_cluster(L.ptr(gt), B, M, code, L.ptr(to), L.ptr(occ), L.ptr(fac), int(variant),
@@ -73,7 +67,7 @@ def anchor_groups(targets, group):
     """`groups` int32 [B, N] of curri_axis_aligned_target_assigner.py:246-311: the box's group at the positives, 0 at the
     background anchors, -1 at the ignored ones."""
     labels, gt_index = targets['box_cls_labels'], targets['box_gt_index']
-    group = _dev(group, "assign_targets").contiguous().to(torch.int64)
+    group = L.require_device("assign_targets", group).contiguous().to(torch.int64)
     B, N = labels.shape
     if group.dim() != 2 or group.shape[0] != B:
         raise L.PcdError(f"assign_targets: group {tuple(group.shape)}, want [{B}, M] (one value per gt box)")
@@ -211,8 +205,7 @@ class _AnchorCurLoss(torch.autograd.Function):
         lib = L.lib()
         out = torch.empty((4,), dtype=torch.float32, device=preds.device)
         saved = torch.empty((SAVED_FLOATS,), dtype=torch.float32, device=preds.device)
-        ws = torch.empty((max(int(lib.pcd_anchor_cur_loss_workspace_bytes(B, tab.H, tab.W, tab.A)), 256),), dtype=torch.uint8,
-                         device=preds.device)
+        ws = L.workspace(lib.pcd_anchor_cur_loss_workspace_bytes(B, tab.H, tab.W, tab.A), preds.device)
         cur = ctypes.cast(ctypes.pointer(lf.struct), ctypes.c_void_p)
         L.check(lib.pcd_anchor_cur_loss_forward(
             L.ptr(cls), L.ptr(box), L.ptr(dr), _dt(preds), _strides3([cls, box, dr]), L.ptr(labels), L.ptr(targets),

@@ -20,9 +20,7 @@ from .. import _lib as L
 from ._maps import dtype_code as _dt, like as _like
 from .dense2d import _get
 
-KIND_FLOATS = 10      # include/pcd_ops.h: PCD_ANCHOR_KIND_FLOATS
-CLASS_FLOATS = 4      # include/pcd_ops.h: PCD_ANCHOR_CLASS_FLOATS
-MAX_KINDS = 32        # include/pcd_ops.h: PCD_ANCHOR_MAX_KINDS
+KIND_FLOATS, CLASS_FLOATS, MAX_KINDS = L.PCD_ANCHOR_KIND_FLOATS, L.PCD_ANCHOR_CLASS_FLOATS, L.PCD_ANCHOR_MAX_KINDS
 
 
 class AnchorGenerator:
@@ -184,7 +182,7 @@ def assign_targets(tab, gt_boxes):
     weights = torch.empty((B, N), dtype=torch.float32, device=dev)
     gt_index = torch.empty((B, N), dtype=torch.int32, device=dev)
     num_pos = torch.empty((B,), dtype=torch.int32, device=dev)
-    ws = torch.empty((max(int(lib.pcd_anchor_assign_workspace_bytes(B, M)), 256),), dtype=torch.uint8, device=dev)
+    ws = L.workspace(lib.pcd_anchor_assign_workspace_bytes(B, M), dev)
     L.check(lib.pcd_anchor_assign_targets(L.ptr(gt) if M else None, B, M, L.ptr(tab.kinds), tab.A, L.ptr(tab.classes), tab.C,
                                           L.ptr(tab.shifts), tab.H, tab.W, L.ptr(labels), L.ptr(targets), L.ptr(weights),
                                           L.ptr(gt_index), L.ptr(num_pos), L.ptr(ws), ws.numel(), L.stream_ptr()),
@@ -214,8 +212,7 @@ class _AnchorLoss(torch.autograd.Function):
         B = int(preds.shape[0])
         lib = L.lib()
         out = torch.empty((4,), dtype=torch.float32, device=preds.device)
-        ws = torch.empty((max(int(lib.pcd_anchor_loss_workspace_bytes(B, tab.H, tab.W, tab.A)), 256),), dtype=torch.uint8,
-                         device=preds.device)
+        ws = L.workspace(lib.pcd_anchor_loss_workspace_bytes(B, tab.H, tab.W, tab.A), preds.device)
         L.check(lib.pcd_anchor_loss_forward(
             L.ptr(cls), L.ptr(box), L.ptr(dr), _dt(preds), _strides3([cls, box, dr]), L.ptr(labels), L.ptr(targets),
             L.ptr(num_pos), B, tab.H, tab.W, tab.A, tab.num_class, tab.num_dir_bins, L.ptr(tab.kinds), L.ptr(code_weights),

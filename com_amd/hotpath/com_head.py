@@ -18,20 +18,14 @@ from .. import _lib as L
 from . import _maps
 
 
-def _dev(t, what):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda):
-        raise L.PcdError(f"{what} needs a HIP device tensor (there is no CPU fallback)")
-    return t
-
-
 def cluster(gt_boxes, true_object, occupancy_ratio, facade_type):
     """[B, M] int64 difficulty groups (cars 1..96, pedestrians / cyclists 1..15, 0 = padding or not a real object).
     true_object=None (the reference would fail on `None == 1`) is rejected."""
-    gt = _dev(gt_boxes, "cluster").contiguous().float()
+    gt = L.require_device("cluster", gt_boxes).contiguous().float()
     B, M, code = gt.shape
     if true_object is None:
         raise L.PcdError("cluster needs data_dict['true_object'] (COMAug's marker of real vs pasted objects)")
-    to, occ, fac = (_dev(t, "cluster").contiguous().float() for t in (true_object, occupancy_ratio, facade_type))
+    to, occ, fac = (L.require_device("cluster", t).contiguous().float() for t in (true_object, occupancy_ratio, facade_type))
     assert to.shape == (B, M) and occ.shape == (B, M) and fac.shape == (B, M)
     group = torch.empty((B, M), dtype=torch.int64, device=gt.device)
     L.check(L.lib().pcd_com_cluster_groups(L.ptr(gt), B, M, code, L.ptr(to), L.ptr(occ), L.ptr(fac),
@@ -47,19 +41,18 @@ def assign_targets(gt_boxes, feature_map_size, class_names, class_names_each_hea
     -- the group tensor -- is None), heatmap_mask [B, C, H, W] ones.  feature_map_size = [H, W].
     Every head filters on the ORIGINAL class ids (the reference rewrites gt_boxes' class column in place while
     filtering, curriculum_center_head.py:260, which later heads then see; identical for the single-head COM configs)."""
-    gt = _dev(gt_boxes, "assign_targets").contiguous().float()
+    gt = L.require_device("assign_targets", gt_boxes).contiguous().float()
     B, M, code = gt.shape
     H, W = int(feature_map_size[0]), int(feature_map_size[1])
-    npgt = _dev(npgt, "assign_targets").contiguous().float()
+    npgt = L.require_device("assign_targets", npgt).contiguous().float()
     assert npgt.shape == (B, M), "gt_boxes.shape[:-1] == npgt.shape (curriculum_center_head.py:236)"
     group = None
     if true_object is not None:
-        group = _dev(true_object, "assign_targets").contiguous().to(torch.int64)
+        group = L.require_device("assign_targets", true_object).contiguous().to(torch.int64)
         assert group.shape == (B, M)
     cols = 5 if group is not None else 4
     lib = L.lib()
-    ws = torch.empty((max(int(lib.pcd_com_assign_workspace_bytes(B, num_max_objs)), 256),), dtype=torch.uint8,
-                     device=gt.device)
+    ws = L.workspace(lib.pcd_com_assign_workspace_bytes(B, num_max_objs), gt.device)
     ret = {'heatmaps': [], 'target_boxes': [], 'inds': [], 'masks': [], 'heatmap_masks': [], 'radius_map': [],
            'heatmap_mask': []}
     gate = int(epoch <= epoch_threshold)

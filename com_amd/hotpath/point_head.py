@@ -50,7 +50,7 @@ class _PointClsLoss(torch.autograd.Function):
         n = int(logits.shape[0])
         lib = L.lib()
         out = torch.empty((4,), dtype=torch.float32, device=logits.device)
-        ws = torch.empty((max(int(lib.pcd_point_head_loss_workspace_bytes(n)), 256),), dtype=torch.uint8, device=logits.device)
+        ws = L.workspace(lib.pcd_point_head_loss_workspace_bytes(n), logits.device)
         L.check(lib.pcd_point_head_loss_forward(L.ptr(logits), _dt(logits), int(logits.stride(0)), L.ptr(labels), L.ptr(num_pos),
                                                 n, num_class, cls_weight, L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr()),
                 "pcd_point_head_loss_forward")

@@ -33,12 +33,6 @@ from .pvrcnn_stage2 import StackSAModuleMSG, roi_grid_pool
 SCORE_TYPES = {'roi_iou': L.PCD_ROI_SCORE_ROI_IOU, 'cls': L.PCD_ROI_SCORE_CLS}
 
 
-def _dev(name, *tensors):
-    for t in tensors:
-        if not t.is_cuda:
-            raise L.PcdError(f"{name} needs HIP device tensors (there is no CPU fallback)")
-
-
 def _shapes(name, rois, gt_boxes):
     if rois.dim() != 3 or rois.shape[2] != 7 or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 8 or gt_boxes.shape[0] != rois.shape[0]:
         raise L.PcdError(f"{name}: rois {tuple(rois.shape)}, gt_boxes {tuple(gt_boxes.shape)}; want [B, N, 7] and [B, M, 8] "
@@ -48,7 +42,7 @@ def _shapes(name, rois, gt_boxes):
 def max_overlaps(rois, roi_labels, gt_boxes, same_class=False):
     """pcd_roi_head_max_overlaps: (max_overlaps f32 [B, N], gt_assignment int32 [B, N]); proposal_target_layer.py:89-105,
     :195-228."""
-    _dev("roi head max_overlaps", rois, gt_boxes, roi_labels)
+    L.require_device("roi head max_overlaps", rois, gt_boxes, roi_labels)
     _shapes("roi head max_overlaps", rois, gt_boxes)
     r, g, lab = rois.contiguous().float(), gt_boxes.contiguous().float(), roi_labels.contiguous().long()
     B, N, M = int(r.shape[0]), int(r.shape[1]), int(g.shape[1])
@@ -114,7 +108,7 @@ class ProposalTargetLayer(nn.Module):
         c = self.roi_sampler_cfg
         rois, gt = batch_dict['rois'], batch_dict['gt_boxes']
         scores, labels = batch_dict['roi_scores'], batch_dict['roi_labels']
-        _dev("ProposalTargetLayer", rois, gt, scores, labels)
+        L.require_device("ProposalTargetLayer", rois, gt, scores, labels)
         _shapes("ProposalTargetLayer", rois, gt)
         B, N, M, R = int(rois.shape[0]), int(rois.shape[1]), int(gt.shape[1]), self.rois_per_image
         if 'batch_size' in batch_dict and int(batch_dict['batch_size']) != B:
@@ -173,7 +167,7 @@ class _RoiLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rcnn_cls, rcnn_reg, cls_labels, reg_valid, rois, gt_ct, gt_src, code_weights, weights, corner):
-        _dev("PVRCNNHead.get_loss", rcnn_cls, rcnn_reg, cls_labels, reg_valid, rois, gt_ct, gt_src)
+        L.require_device("PVRCNNHead.get_loss", rcnn_cls, rcnn_reg, cls_labels, reg_valid, rois, gt_ct, gt_src)
         n = int(rcnn_reg.shape[0])
         cls2 = rcnn_cls.reshape(n, -1) if rcnn_cls.dim() != 2 else rcnn_cls
         if rcnn_reg.dim() != 2 or rcnn_reg.shape[1] != 7 or rcnn_reg.stride(1) != 1 or cls2.shape[1] != 1 or n < 1:
@@ -222,7 +216,7 @@ def roi_loss(rcnn_cls, rcnn_reg, rcnn_cls_labels, reg_valid_mask, rois, gt_of_ro
 
 def decode_boxes(rois, box_preds):
     """pcd_roi_head_decode: rois [B, N, 7], box_preds [B*N, 7] (f32 / bf16) -> batch_box_preds f32 [B, N, 7]."""
-    _dev("PVRCNNHead.generate_predicted_boxes", rois, box_preds)
+    L.require_device("PVRCNNHead.generate_predicted_boxes", rois, box_preds)
     if rois.dim() != 3 or rois.shape[2] != 7:
         raise L.PcdError(f"roi head decode: rois {tuple(rois.shape)}, want [B, N, 7] (code_size 7)")
     n = int(rois.shape[0] * rois.shape[1])

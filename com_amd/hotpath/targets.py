@@ -16,8 +16,7 @@ def assign_targets(gt_boxes, feature_map_size, class_names, class_names_each_hea
     B, M, code = gt.shape
     H, W = int(feature_map_size[0]), int(feature_map_size[1])
     lib = L.lib()
-    ws = torch.empty((max(int(lib.pcd_centerhead_assign_workspace_bytes(B, num_max_objs)), 256),), dtype=torch.uint8,
-                     device=gt.device)
+    ws = L.workspace(lib.pcd_centerhead_assign_workspace_bytes(B, num_max_objs), gt.device)
     ret = {'heatmaps': [], 'target_boxes': [], 'inds': [], 'masks': [], 'heatmap_masks': []}
     for head_names in class_names_each_head:
         cmap = _maps.head_class_map(class_names, head_names)

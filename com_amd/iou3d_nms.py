@@ -80,7 +80,7 @@ def nms_sorted(boxes_sorted, thresh, normal=False):
     keep = torch.empty((max(n, 1),), dtype=torch.int64, device=b.device)
     num = torch.zeros((1,), dtype=torch.int32, device=b.device)
     lib = L.lib()
-    ws = torch.empty((max(int(lib.pcd_nms_workspace_bytes(n)), 256),), dtype=torch.uint8, device=b.device)
+    ws = L.workspace(lib.pcd_nms_workspace_bytes(n), b.device)
     L.check(lib.pcd_nms_bev(L.ptr(b), n, float(thresh), int(bool(normal)), L.ptr(keep), L.ptr(num), L.ptr(ws),
                             ws.numel(), L.stream_ptr()), "pcd_nms_bev")
     return keep, num

@@ -45,22 +45,8 @@ def _triple(v):
     return [int(v)] * 3
 
 
-def _ws(nbytes, device):
-    return torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=device)
-
-
-def _dtype_code(t):
-    if t.dtype == torch.float32:
-        return PCD_F32
-    if t.dtype == torch.bfloat16:
-        return PCD_BF16
-    raise L.PcdError(f"unsupported feature dtype {t.dtype} (float32 / bfloat16 only)")
-
-
 def _require_cuda(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise L.PcdError("hot-path ops need HIP device tensors (there is no CPU fallback)")
+    L.require_device("hot-path ops", *tensors, verb="need", allow_none=True)
 
 
 STAMPS = None          # tools: {"buf": int64 device tensor, "names": [...]} -> stamp(name) records the device clock
@@ -214,7 +200,7 @@ def pow2_ge8(c):
 USE_COLUMN_MAPS = True      # z-fastest chains build their rulebooks from column maps (colmap.hip); False: flat key-space bitmaps
 
 # row orders of key-numbered levels (pcd_ops.h: PCD_ROWS_ZYX / PCD_ROWS_YXZ)
-ROWS_ZYX, ROWS_YXZ = 0, 1
+ROWS_ZYX, ROWS_YXZ = L.PCD_ROWS_ZYX, L.PCD_ROWS_YXZ
 ROW_ORDERS = {"first": ROWS_ZYX, "key": ROWS_ZYX, "zyx": ROWS_ZYX, "yxz": ROWS_YXZ}
 
 
@@ -275,7 +261,7 @@ def voxelize_hard(points, frame_offsets, point_cloud_range, voxel_size, max_poin
     else:
         ws_bytes = lib.pcd_voxelize_hard_workspace_bytes(n, max_points, batch)
         entry = lib.pcd_voxelize_hard
-    ws = _ws(ws_bytes, dev)
+    ws = L.workspace(ws_bytes, dev)
     def buf(key, shape, dtype, want=True):
         if not want:
             return None
@@ -375,7 +361,7 @@ def voxelize_dynamic_mean(points_b, batch_size, point_cloud_range, voxel_size, r
     wsb = lib.pcd_voxelize_dynamic_workspace_bytes(n, C, batch_size, rng, vs)
     if wsb == 0:
         raise L.PcdError("pcd_voxelize_dynamic: key space too large for 32-bit keys")
-    ws = _ws(wsb, dev)
+    ws = L.workspace(wsb, dev)
     cap = max(n, 1)
     feat = torch.empty((cap, C), dtype=torch.float32, device=dev)
     coords = torch.empty((cap, 4), dtype=torch.int32, device=dev)
@@ -437,7 +423,7 @@ def segment_max(x, seg, m):
     lib = L.lib()
     out = torch.empty((m, c), dtype=torch.float32, device=x.device)
     arg = torch.empty((m, c), dtype=torch.int32, device=x.device)
-    ws = _ws(lib.pcd_segment_max_workspace_bytes(m, c), x.device)
+    ws = L.workspace(lib.pcd_segment_max_workspace_bytes(m, c), x.device)
     L.check(lib.pcd_segment_max(L.ptr(x), L.ptr(seg), n, c, m, L.ptr(out), L.ptr(arg), L.ptr(ws), ws.numel(),
                                 L.stream_ptr()), "pcd_segment_max")
     return out, arg
@@ -535,7 +521,7 @@ class Rulebook:
             n, dev = self.nbr_out.shape[1], self.nbr_out.device
             self._pairs = torch.empty((self.kvol, 2, n), dtype=torch.int32, device=dev)
             self._pair_num = torch.empty((self.kvol,), dtype=torch.int32, device=dev)
-            ws = _ws(lib.pcd_rulebook_subm_pairs_workspace_bytes(n, self.kvol), dev)
+            ws = L.workspace(lib.pcd_rulebook_subm_pairs_workspace_bytes(n, self.kvol), dev)
             L.check(lib.pcd_rulebook_subm_pairs(L.ptr(self.nbr_out), n, self.kvol, L.ptr(self._pairs),
                                                 L.ptr(self._pair_num), 0, L.ptr(self.n_in_dev), L.ptr(ws), ws.numel(),
                                                 L.stream_ptr()), "pcd_rulebook_subm_pairs")
@@ -544,7 +530,7 @@ class Rulebook:
             n, dev = self.nbr_in.shape[1], self.nbr_in.device
             self._pairs = torch.empty((self.kvol, 2, n), dtype=torch.int32, device=dev)
             self._pair_num = torch.empty((self.kvol,), dtype=torch.int32, device=dev)
-            ws = _ws(lib.pcd_rulebook_subm_pairs_workspace_bytes(n, self.kvol), dev)
+            ws = L.workspace(lib.pcd_rulebook_subm_pairs_workspace_bytes(n, self.kvol), dev)
             L.check(lib.pcd_rulebook_conv_pairs(L.ptr(self.nbr_in), n, self.kvol, L.ptr(self._pairs), L.ptr(self._pair_num), 1,
                                                 L.ptr(self.n_in_dev), L.ptr(ws), ws.numel(), L.stream_ptr()),
                     "pcd_rulebook_conv_pairs")
@@ -635,7 +621,7 @@ def colmap_from_rows(indices, batch_size, spatial_shape, n_dev=None, out=None):
         buf = out.buf
     else:
         buf = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    ws = _ws(lib.pcd_colmap_from_rows_workspace_bytes(batch_size, L.host_i32(shp)), dev)
+    ws = L.workspace(lib.pcd_colmap_from_rows_workspace_bytes(batch_size, L.host_i32(shp)), dev)
     L.check(lib.pcd_colmap_from_rows(L.ptr(indices), n, L.ptr(n_dev), batch_size, L.host_i32(shp), L.ptr(buf), buf.numel(),
                                      L.ptr(ws), ws.numel(), L.stream_ptr()), "pcd_colmap_from_rows")
     return ColumnMap(buf, max(n, 1), indices, shp, batch_size)
@@ -665,7 +651,7 @@ def rulebook_subm(indices, batch_size, spatial_shape, ksize=3, dilation=1, want_
     win_plan = finish = None
     if isinstance(rank, ColumnMap) and rank.matches(indices, shp, ks) and dl == [1, 1, 1]:
         def full_table():
-            ws = _ws(lib.pcd_rulebook_subm_cm_workspace_bytes(n), dev)
+            ws = L.workspace(lib.pcd_rulebook_subm_cm_workspace_bytes(n), dev)
             L.check(lib.pcd_rulebook_subm_cm(L.ptr(indices), n, batch_size, L.host_i32(shp), L.ptr(rank.buf),
                                              rank.buf.numel(), rank.cap, L.ptr(nbr), L.ptr(pairs), L.ptr(pair_num),
                                              int(pad_pairs), L.ptr(n_dev), L.ptr(ws), ws.numel(), L.stream_ptr()),
@@ -673,8 +659,7 @@ def rulebook_subm(indices, batch_size, spatial_shape, ksize=3, dilation=1, want_
         T = _plan_key(*window) if (window is not None and not want_pairs and n > 0) else (0, 0)
         if T[0] > 0:
             # plan (+ table, or only the multi-pass tiles' columns of it) in one pass over the column map
-            win_plan = (T, torch.empty((max(int(lib.pcd_subm_window_plan_bytes(n, int(window[0]), int(window[1]))), 32),),
-                                       dtype=torch.uint8, device=dev))
+            win_plan = (T, L.workspace(lib.pcd_subm_window_plan_bytes(n, int(window[0]), int(window[1])), dev, floor=32))
 
             def meta_plan():                     # (the table is not there to be counted: a full build on the side, profiling only)
                 tmp = rulebook_subm(indices, batch_size, spatial_shape, ksize, dilation, want_pairs=False, n_dev=n_dev, rank=rank)
@@ -691,7 +676,7 @@ def rulebook_subm(indices, batch_size, spatial_shape, ksize=3, dilation=1, want_
             with _Timed("rulebook_subm_cm", meta):
                 full_table()
     elif isinstance(rank, RankMap) and rank.matches(indices, shp, ks):
-        ws = _ws(lib.pcd_rulebook_subm_ranked_workspace_bytes(n, K), dev)
+        ws = L.workspace(lib.pcd_rulebook_subm_ranked_workspace_bytes(n, K), dev)
         with _Timed("rulebook_subm_ranked", meta):
             entry = lib.pcd_rulebook_subm_ranked4 if rank.prefix_words == 4 else lib.pcd_rulebook_subm_ranked
             L.check(entry(L.ptr(indices), n, batch_size, L.host_i32(shp), L.host_i32(ks),
@@ -699,7 +684,7 @@ def rulebook_subm(indices, batch_size, spatial_shape, ksize=3, dilation=1, want_
                           L.ptr(pairs), L.ptr(pair_num), int(pad_pairs), L.ptr(n_dev),
                           L.ptr(ws), ws.numel(), L.stream_ptr(), int(rank.order)), "pcd_rulebook_subm_ranked")
     else:
-        ws = _ws(lib.pcd_rulebook_subm_workspace_bytes(n, K), dev)
+        ws = L.workspace(lib.pcd_rulebook_subm_workspace_bytes(n, K), dev)
         with _Timed("rulebook_subm", meta):
             L.check(lib.pcd_rulebook_subm(L.ptr(indices), n, batch_size, L.host_i32(shp), L.host_i32(ks),
                                           L.host_i32(dl), L.ptr(nbr), L.ptr(pairs), L.ptr(pair_num), int(pad_pairs),
@@ -770,7 +755,7 @@ def rulebook_conv(indices, batch_size, spatial_shape, ksize, stride, padding, di
         if wsb == 0:
             raise L.PcdError("pcd_rulebook_conv: bad geometry or key space too large")
     cm = be is _COLMAP_BUILD
-    ws = _ws(wsb, dev)
+    ws = L.workspace(wsb, dev)
     n_out_dev = torch.empty((1,), dtype=torch.int32, device=dev)      # always written by the scan launch
     static = PLAN is not None and PLAN.active
     ncls = st[0] * st[1] * st[2]
@@ -885,7 +870,7 @@ def rulebook_conv(indices, batch_size, spatial_shape, ksize, stride, padding, di
     if want_classes and classes is None:
         # (two-phase build: the parity classes in a pass of their own)
         rb.classes = perm, vstart, vcap = _parity_classes(n, ncls, dev)
-        cws = _ws(lib.pcd_rulebook_conv_classes_workspace_bytes(n), dev)
+        cws = L.workspace(lib.pcd_rulebook_conv_classes_workspace_bytes(n), dev)
         with _Timed("rulebook_conv_classes", lambda: dict(bytes=0, flops=0, rows=n, pairs=0)):
             L.check(lib.pcd_rulebook_conv_classes(L.ptr(indices), n, L.host_i32(st), L.host_i32(pd), CLS_TILE,
                                                   L.ptr(perm), vcap, L.ptr(vstart), L.ptr(n_dev), L.ptr(cws),
@@ -1028,7 +1013,7 @@ def dgrad_classes(dy, packed_w, rb, c_in, out_dtype, addend=None, bn_reduce=None
         L.check(L.lib().pcd_sparse_conv_dgrad_classes_v2(
             L.ptr(dy), dy.shape[0], dy.shape[1], L.ptr(packed_w), L.ptr(tab), tab.shape[1], compact,
             L.host_i32(rb.ksize), L.host_i32(rb.stride), L.host_i32(rb.padding), L.host_i32(rb.dilation), L.ptr(perm),
-            L.ptr(vstart), vcap, rb.n_in, c_in, L.ptr(dx), _dtype_code(dx), L.ptr(addend), _byref(bnr),
+            L.ptr(vstart), vcap, rb.n_in, c_in, L.ptr(dx), L.dtype_code(dx), L.ptr(addend), _byref(bnr),
             L.stream_ptr()),
             "pcd_sparse_conv_dgrad_classes_v2")
     return dx
@@ -1141,12 +1126,12 @@ def gather_gemm(x, packed_w, bias, nbr, kvol, flip_k, n_rows_out, c_out, out_dty
             assert not flip_k and nbr.shape[0] * 3 == kvol
             L.check(L.lib().pcd_sparse_conv_gather_gemm_packed(
                 L.ptr(x), x.shape[0], x.shape[1], L.ptr(packed_w), L.ptr(bias), L.ptr(nbr), nbr.shape[1], kvol, n_rows_out,
-                L.ptr(n_dev), c_out, L.ptr(y), _dtype_code(y), L.ptr(addend), _byref(bnr), L.stream_ptr()),
+                L.ptr(n_dev), c_out, L.ptr(y), L.dtype_code(y), L.ptr(addend), _byref(bnr), L.stream_ptr()),
                 "pcd_sparse_conv_gather_gemm_packed")
             return y
         L.check(L.lib().pcd_sparse_conv_gather_gemm(
             L.ptr(x), x.shape[0], x.shape[1], L.ptr(packed_w), L.ptr(bias), L.ptr(nbr), nbr.shape[1], kvol, int(flip_k), n_rows_out,
-            L.ptr(n_dev), c_out, L.ptr(y), _dtype_code(y), L.ptr(addend), _byref(bnr), L.stream_ptr()),
+            L.ptr(n_dev), c_out, L.ptr(y), L.dtype_code(y), L.ptr(addend), _byref(bnr), L.stream_ptr()),
             "pcd_sparse_conv_gather_gemm")
     return y
 
@@ -1173,8 +1158,7 @@ def subm_window_plan(rb, c_in, c_out):
     if T not in cache:
         lib = L.lib()
         n = rb.nbr_out.shape[1]                  # (a plan of another tile size than the one the build made: from the table)
-        plan = torch.empty((max(int(lib.pcd_subm_window_plan_bytes(n, int(c_in), int(c_out))), 32),), dtype=torch.uint8,
-                           device=rb.nbr_out.device)
+        plan = L.workspace(lib.pcd_subm_window_plan_bytes(n, int(c_in), int(c_out)), rb.nbr_out.device, floor=32)
         L.check(lib.pcd_subm_window_plan(L.ptr(rb.nbr_out), n, n, L.ptr(rb.n_out_dev), int(c_in), int(c_out), L.ptr(plan),
                                          L.stream_ptr()), "pcd_subm_window_plan")
         cache[T] = plan
@@ -1353,7 +1337,7 @@ def wgrad(x, cin, dy, pairs, pair_num, kvol, out=None, defer=None, nbr_out=None,
     def tile_job(pmax):
         """the reduction of the pair kernels' per-tile partials over `pmax` pairs, with a workspace of its own when deferred"""
         wsb = lib.pcd_sparse_conv_wgrad_workspace_bytes(kvol, cin, cout, pmax)
-        ws = _ws(wsb, x.device) if defer is None else torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
+        ws = L.workspace(wsb, x.device) if defer is None else torch.empty((max(wsb, 16),), dtype=torch.uint8, device=x.device)
         return WgradJob(ws, dw, kvol, cin, cout, pmax, layout=1 if conv2d_layout else 0, cout_write=cout_write)
 
     wide = cin == 128 and cout == 128 and x_w == 128     # (wgrad128_kernel: cuts the concatenated pair lists into equal chunks)
@@ -1598,19 +1582,19 @@ def bev_scatter(features, indices, batch_size, spatial_shape, channels=None, n_d
     n, cs = features.shape
     C = channels if channels is not None else cs
     lib = L.lib()
-    ws = _ws(lib.pcd_bev_workspace_bytes(batch_size, D, H, W), features.device)
+    ws = L.workspace(lib.pcd_bev_workspace_bytes(batch_size, D, H, W), features.device)
     if channels_last:
         out = torch.empty((batch_size, H, W, C * D), dtype=features.dtype, device=features.device)
         e = features.element_size()
         with _Timed("bev_scatter_nhwc", lambda: dict(bytes=n * (C * e + 16) + out.numel() * e, flops=0, rows=n, pairs=0)):
-            L.check(lib.pcd_bev_scatter_nhwc(L.ptr(features), C, cs, _dtype_code(features), L.ptr(indices), n,
+            L.check(lib.pcd_bev_scatter_nhwc(L.ptr(features), C, cs, L.dtype_code(features), L.ptr(indices), n,
                                              L.ptr(n_dev), batch_size, D, H, W, L.ptr(out), L.ptr(ws), ws.numel(),
                                              L.stream_ptr()), "pcd_bev_scatter_nhwc")
         return out.permute(0, 3, 1, 2)
     out = torch.empty((batch_size, C * D, H, W), dtype=features.dtype, device=features.device)
     e = features.element_size()                  # read N5 (C e + 16), write B C D H W e
     with _Timed("bev_scatter", lambda: dict(bytes=n * (C * e + 16) + out.numel() * e, flops=0, rows=n, pairs=0)):
-        L.check(lib.pcd_bev_scatter(L.ptr(features), C, cs, _dtype_code(features), L.ptr(indices), n, L.ptr(n_dev),
+        L.check(lib.pcd_bev_scatter(L.ptr(features), C, cs, L.dtype_code(features), L.ptr(indices), n, L.ptr(n_dev),
                                     batch_size, D, H, W, L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr()),
                 "pcd_bev_scatter")
     return out
@@ -1629,14 +1613,14 @@ def bev_gather(dout, indices, batch_size, spatial_shape, channels, c_stride=None
         dout = dout.contiguous(memory_format=torch.channels_last)        # memory = [B][H][W][C*D]
         e = dout.element_size()
         with _Timed("bev_gather_nhwc", lambda: dict(bytes=n * (2 * channels * e + 16), flops=0, rows=n, pairs=0)):
-            L.check(L.lib().pcd_bev_gather_nhwc(L.ptr(dout), channels, cs, _dtype_code(dout), L.ptr(indices), n,
+            L.check(L.lib().pcd_bev_gather_nhwc(L.ptr(dout), channels, cs, L.dtype_code(dout), L.ptr(indices), n,
                                                 L.ptr(n_dev), batch_size, D, H, W, L.ptr(df), L.stream_ptr()),
                     "pcd_bev_gather_nhwc")
         return df
     dout = dout.contiguous()
     e = dout.element_size()
     with _Timed("bev_gather", lambda: dict(bytes=n * (2 * channels * e + 16), flops=0, rows=n, pairs=0)):
-        L.check(L.lib().pcd_bev_gather(L.ptr(dout), channels, cs, _dtype_code(dout), L.ptr(indices), n,
+        L.check(L.lib().pcd_bev_gather(L.ptr(dout), channels, cs, L.dtype_code(dout), L.ptr(indices), n,
                                        L.ptr(n_dev), batch_size, D, H, W, L.ptr(df), L.stream_ptr()),
                 "pcd_bev_gather")
     return df
@@ -1667,11 +1651,11 @@ def bn_forward(x, residual, gamma, beta, eps, momentum, training, running_mean, 
         y, y_ld = torch.empty_like(x), c
     save_mean = torch.empty((c,), dtype=torch.float32, device=dev)
     save_invstd = torch.empty((c,), dtype=torch.float32, device=dev)
-    ws = _ws(lib.pcd_bn_workspace_bytes(c), dev)
+    ws = L.workspace(lib.pcd_bn_workspace_bytes(c), dev)
     e = x.element_size()                         # 2 N C e (3 with residual) per pass
     with _Timed("bn_forward", lambda: dict(bytes=(3 if residual is not None else 2) * n * c * e, flops=0, rows=n,
                                            pairs=0)):
-        L.check(lib.pcd_bn_forward_ld(L.ptr(x), L.ptr(residual), _dtype_code(x), n, c, L.ptr(gamma), L.ptr(beta),
+        L.check(lib.pcd_bn_forward_ld(L.ptr(x), L.ptr(residual), L.dtype_code(x), n, c, L.ptr(gamma), L.ptr(beta),
                                       float(eps), float(momentum), int(training), L.ptr(running_mean),
                                       L.ptr(running_var), int(relu), L.ptr(y), int(y_ld), L.ptr(save_mean),
                                       L.ptr(save_invstd), L.ptr(n_dev), L.ptr(partials[0]) if partials else None,
@@ -1700,15 +1684,15 @@ def bn_backward(dy, x, y, gamma, save_mean, save_invstd, relu, training, want_dr
     dres = torch.empty_like(x) if want_dres else None
     dgamma = dgamma_out if _usable_out(dgamma_out, c) else torch.empty((c,), dtype=torch.float32, device=dev)
     dbeta = dbeta_out if _usable_out(dbeta_out, c) else torch.empty((c,), dtype=torch.float32, device=dev)
-    ws = _ws(lib.pcd_bn_workspace_bytes(c), dev)
+    ws = L.workspace(lib.pcd_bn_workspace_bytes(c), dev)
     cpart, crows = None, 0
     if colsum:
-        crows = _tiles(lib.pcd_bn_backward_colsum_rows(_dtype_code(x), n, c), "pcd_bn_backward_colsum_rows")
+        crows = _tiles(lib.pcd_bn_backward_colsum_rows(L.dtype_code(x), n, c), "pcd_bn_backward_colsum_rows")
         cpart = torch.empty((max(crows, 1), c), dtype=torch.float32, device=dev)
     e = x.element_size()                         # reads dy, x (, y), writes dx (, dres)
     with _Timed("bn_backward", lambda: dict(bytes=(3 + (y is not None) + bool(want_dres)) * n * c * e, flops=0,
                                             rows=n, pairs=0)):
-        L.check(lib.pcd_bn_backward_ld(L.ptr(dy), int(dy_ld), L.ptr(x), L.ptr(y), _dtype_code(x), n, c, L.ptr(gamma),
+        L.check(lib.pcd_bn_backward_ld(L.ptr(dy), int(dy_ld), L.ptr(x), L.ptr(y), L.dtype_code(x), n, c, L.ptr(gamma),
                                        L.ptr(beta), L.ptr(save_mean), L.ptr(save_invstd), int(relu), int(training),
                                        L.ptr(dx), L.ptr(dres), L.ptr(dgamma), L.ptr(dbeta), L.ptr(n_dev),
                                        L.ptr(partials[0]) if partials else None, partials[1] if partials else 0,
@@ -1747,7 +1731,7 @@ def col_sum(x, n_dev=None, out=None):
     lib = L.lib()
     if not _usable_out(out, c):
         out = torch.empty((c,), dtype=torch.float32, device=x.device)
-    ws = _ws(lib.pcd_bn_workspace_bytes(c), x.device)
-    L.check(lib.pcd_col_sum(L.ptr(x), _dtype_code(x), n, c, L.ptr(out), L.ptr(n_dev), L.ptr(ws), ws.numel(),
+    ws = L.workspace(lib.pcd_bn_workspace_bytes(c), x.device)
+    L.check(lib.pcd_col_sum(L.ptr(x), L.dtype_code(x), n, c, L.ptr(out), L.ptr(n_dev), L.ptr(ws), ws.numel(),
                             L.stream_ptr()), "pcd_col_sum")
     return out

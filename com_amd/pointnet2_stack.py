@@ -119,7 +119,7 @@ class StackFarthestPointSampling(Function):
                                                                max_cnt, L.ptr(ws), ws.numel(), L.stream_ptr())
             if rc == 0:
                 return out
-            if rc != -2:                                         # PCD_ERR_UNSUPPORTED: a frame beyond the bucket tables
+            if rc != L.PCD_ERR_UNSUPPORTED:                      # a frame beyond the bucket tables
                 L.check(rc, "pcd_stack_farthest_point_sampling_buckets")
         if max_cnt >= COOP_FPS_MIN_POINTS and FPS_LARGE == "coop":
             # large frames: 256 / B workgroups share a frame (same selected points; see pointnet2.hip)
@@ -133,7 +133,7 @@ class StackFarthestPointSampling(Function):
                 # one-workgroup-per-frame kernel below computes the same indices
                 global COOP_FPS_TIMEOUTS
                 COOP_FPS_TIMEOUTS += 1
-            elif rc != -2:                                       # PCD_ERR_UNSUPPORTED: too many frames / slice too large
+            elif rc != L.PCD_ERR_UNSUPPORTED:                    # too many frames / slice too large
                 L.check(rc, "pcd_stack_farthest_point_sampling_coop")
         temp = torch.full((xyz.shape[0],), 1e10, dtype=torch.float32, device=xyz.device)
         L.check(lib.pcd_stack_farthest_point_sampling(B, L.ptr(xyz.float()), L.ptr(temp), L.ptr(cnt),

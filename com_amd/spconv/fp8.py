@@ -34,7 +34,7 @@ def quantize(x, scale, cb=None, n_dev=None):
         while cb < c:
             cb <<= 1
     out = torch.empty((n, cb), dtype=torch.uint8, device=x.device)
-    L.check(L.lib().pcd_fp8_quantize(L.ptr(x), ops._dtype_code(x), n, L.ptr(n_dev), c, x.stride(0), cb,
+    L.check(L.lib().pcd_fp8_quantize(L.ptr(x), L.dtype_code(x), n, L.ptr(n_dev), c, x.stride(0), cb,
                                      1.0 / float(scale), L.ptr(out), L.stream_ptr()), "pcd_fp8_quantize")
     return out
 

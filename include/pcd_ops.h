@@ -58,7 +58,11 @@ extern "C" {
 
 /* ---- library info -------------------------------------------------------------------------- */
 int pcd_version(void);                    /* 10000*major + 100*minor + patch; 0.2.0: the two entry points of the
-                                             plane-form dense weight gradient left the ABI */
+                                             plane-form dense weight gradient left the ABI; 0.3.0: the entry points whose
+                                             successors take a superset of their arguments left it.  A missing lower
+                                             version number (pcd_adam_flat_step_v4 without _v3, pcd_sparse_conv_wgrad_v2
+                                             without the unsuffixed form, _ld / _bn / _dir without the plain form) means
+                                             "retired": the survivors keep their names */
 const char *pcd_error_string(int code);
 const char *pcd_build_arch(void);         /* "gfx950" */
 /* text of the HIP runtime error behind the calling thread's last PCD_ERR_LAUNCH */
@@ -386,15 +390,15 @@ int pcd_rulebook_conv_expand_nbr_in(const int32_t *nbr_cls, int vcap, const int3
                                     const int *ksize_host, const int *stride_host, int n, int32_t *nbr_in, void *stream);
 
 /* Optional per-channel reductions of the OUTPUT tile in the epilogue of pcd_sparse_conv_gather_gemm /
- * pcd_sparse_conv_dgrad_classes (bf16 outputs only; NULL or mode 0 = off).  The BatchNorm1d that follows every conv of
+ * pcd_sparse_conv_dgrad_classes_v2 (bf16 outputs only; NULL or mode 0 = off).  The BatchNorm1d that follows every conv of
  * the reference backbones (spconv_backbone.py:21-25,50-66) needs these sums; taking them while the values are still in
  * registers replaces one streaming pass per BatchNorm and direction:
- *   mode 1 (forward)       partial[t] = { sum y, sum y^2 } of the rounded outputs  -> pcd_bn_forward(ext_partial)
+ *   mode 1 (forward)       partial[t] = { sum y, sum y^2 } of the rounded outputs  -> pcd_bn_forward_ld(ext_partial)
  *   mode 2 (data gradient) the output is dy of the BatchNorm(+ReLU) whose output was the conv's input:
  *                          partial[t] = { sum dz, sum dz*xhat }, dz = relu ? dy*(y > 0) : dy, xhat = (x-mean)*invstd;
  *                          y = that BatchNorm's output = the conv's own input features (required when relu)
- *                                                                               -> pcd_bn_backward(ext_partial)
- * One row [2][c_out] per workgroup tile t; partial_rows must be >= pcd_sparse_conv_gather_gemm_tiles(..) /
+ *                                                                               -> pcd_bn_backward_ld(ext_partial)
+ * One row [2][c_out] per workgroup tile t; partial_rows must be >= pcd_sparse_conv_gather_gemm_tiles_dir(..) /
  * pcd_sparse_conv_dgrad_classes_tiles(..), which is also the row count to hand to the BatchNorm call.
  * mean / invstd must be 16-byte aligned.  Fixed summation order (deterministic). */
 typedef struct PcdBnReduce {
@@ -406,7 +410,7 @@ typedef struct PcdBnReduce {
     float *partial;           /* out: [partial_rows][2][c_out] f32 */
     int partial_rows;
     /* Optional: the launch itself folds the partial rows into the PCD_BN_MID_ROWS rows the BatchNorm apply passes start
-     * from (otherwise pcd_bn_forward / _backward run a small kernel for that -- one more dependent launch on the chain):
+     * from (otherwise pcd_bn_forward_ld / pcd_bn_backward_ld run a small kernel for that -- one more dependent launch on the chain):
      * mid [PCD_BN_MID_ROWS][2][c_out] f64, handed to the BatchNorm call as ext_partial with ext_rows = PCD_BN_EXT_MID;
      * counters [PCD_BN_MID_ROWS * PCD_BN_COUNTER_STRIDE] i32 (one counter per 128-byte line) must be ZERO when the launch
      * starts and are zero again when it ends (keep them in a buffer zeroed once); partial_rows must then equal the
@@ -424,19 +428,13 @@ typedef struct PcdBnReduce {
  *   perm   [vcap] i32 : virtual row -> input row (stable inside a class), -1 = padding; every class starts at a
  *                       multiple of `tile`; vcap >= round_up(n, tile) + (sd*sh*sw) * tile
  *   vstart [sd*sh*sw + 1] i32 on the DEVICE: first virtual row of every class, last entry = end.
- * pcd_sparse_conv_dgrad_classes then runs, per class, only that class's offsets (bit-identical to
+ * pcd_sparse_conv_dgrad_classes_v2 then runs, per class, only that class's offsets (bit-identical to
  * pcd_sparse_conv_gather_gemm on nbr_in; c_dy >= 32, a power of two; tile must be 256). */
 size_t pcd_rulebook_conv_classes_workspace_bytes(int n);
 int pcd_rulebook_conv_classes(const int32_t *indices, int n, const int *stride_host, const int *pad_host, int tile,
                               int32_t *perm, int vcap, int32_t *vstart_dev, const int32_t *n_dev, void *workspace,
                               size_t workspace_bytes, void *stream);
-int pcd_sparse_conv_dgrad_classes(const void *dy, int n_dy_rows, int c_dy, const void *packed_w,
-                                  const int32_t *nbr_in, int nbr_stride, const int *ksize_host,
-                                  const int *stride_host, const int *pad_host, const int *dil_host,
-                                  const int32_t *perm, const int32_t *vstart_dev, int vcap, int n_rows_in, int c_in,
-                                  void *dx, int dx_dtype, const void *addend, const PcdBnReduce *bn_reduce,
-                                  void *stream);
-/* v2: nbr_compact = 1 reads the class-compact table nbr_cls [8][nbr_stride] (pcd_rulebook_conv_cm_build_compact; nbr_stride = the
+/* nbr_compact = 1 reads the class-compact table nbr_cls [8][nbr_stride] (pcd_rulebook_conv_cm_build_compact; nbr_stride = the
  * permutation's capacity) instead of nbr_in [kvol][nbr_stride]: coalesced table reads instead of a gather through perm. */
 int pcd_sparse_conv_dgrad_classes_v2(const void *dy, int n_dy_rows, int c_dy, const void *packed_w, const int32_t *nbr_in,
                                      int nbr_stride, int nbr_compact, const int *ksize_host, const int *stride_host,
@@ -486,27 +484,22 @@ int pcd_sparse_conv_gather_gemm(const void *x, int n_rows_in, int c_in, const vo
                                 const int32_t *nbr, int nbr_stride, int kvol, int flip_k,
                                 int n_rows_out, const int32_t *n_rows_out_dev, int c_out, void *y,
                                 int y_dtype, const void *addend, const PcdBnReduce *bn_reduce, void *stream);
-/* number of workgroup tiles (= partial rows of bn_reduce) of that launch; < 0: error code */
-int pcd_sparse_conv_gather_gemm_tiles(int n_rows_in, int c_in, int kvol, int n_rows_out, int c_out);
-/* same for a launch that is a DATA GRADIENT (flip_k != 0 or bn_reduce->mode == 2): the library may pick a different
- * kernel (tile height) for the two directions */
+/* number of workgroup tiles (= partial rows of bn_reduce) of that launch; < 0: error code.  is_dgrad: the launch is a DATA
+ * GRADIENT (flip_k != 0 or bn_reduce->mode == 2): the library may pick a different kernel (tile height) for the two directions */
 int pcd_sparse_conv_gather_gemm_tiles_dir(int n_rows_in, int c_in, int kvol, int n_rows_out, int c_out, int is_dgrad);
 /* which kernel that launch runs: 0 = gather_gemm_kernel (fragment loads), 1 = ggw_kernel (LDS-DMA, loader / consumer
  * waves); for profiling tools that group launches by kernel name */
 int pcd_sparse_conv_gather_gemm_variant(int n_rows_in, int c_in, int kvol, int n_rows_out, int c_out, int is_dgrad);
 
 /* dW[cout][k][cin] = sum_{(i,o) in pairs[k]} dY[o][cout] * X[i][cin]   (f32, parameter layout).
- * Two launches: pcd_sparse_conv_wgrad fills partial results in `workspace` (MFMA kernel) -- per row-range slabs, or at
+ * Two launches: pcd_sparse_conv_wgrad_v2 fills partial results in `workspace` (MFMA kernel) -- per row-range slabs, or at
  * 128 x 128 channels one tile per (equal-pair chunk, offset) behind a small header --,
  * pcd_sparse_conv_wgrad_reduce sums them in a fixed order into dweight (deterministic, no atomics).
  * `dweight` of the first call is only used when pmax == 0 (it is zeroed); it may be NULL otherwise.
  * pairs[k][0] (rows of x, n_x_rows of them) must be ascending inside each k (canonical order): the
  * kernel partitions the work by ranges of x rows and binary-searches the pair list. */
 size_t pcd_sparse_conv_wgrad_workspace_bytes(int kvol, int cin, int cout, int pmax);
-int pcd_sparse_conv_wgrad(const void *x, int n_x_rows, int cin_pad, int cin, const void *dy, int n_dy_rows, int cout,
-                          const int32_t *pairs, const int32_t *pair_num, int kvol, int pmax,
-                          float *dweight, void *workspace, size_t workspace_bytes, void *stream);
-/* v2: n_x_dev (may be NULL) = device-side count of the real rows of x when n_x is a capacity (static-shape mode): the
+/* n_x = rows of x; n_x_dev (may be NULL) = device-side count of the real rows of x when n_x is a capacity (static-shape mode): the
  * row-range splits then partition the real rows, so no workgroup -- and no XCD -- is left with an empty range */
 int pcd_sparse_conv_wgrad_v2(const void *x, int n_x, const int32_t *n_x_dev, int cin_pad, int cin, const void *dy,
                              int n_dy, int cout, const int32_t *pairs, const int32_t *pair_num, int kvol, int pmax,
@@ -534,7 +527,7 @@ typedef struct PcdWgradReduceJob {
     const void *workspace;
     float *dweight;
     int kvol, cin, cout, pmax;
-    int splits;              /* 0: as planned by pcd_sparse_conv_wgrad; > 0: slabs written by pcd_sparse_conv_wgrad_os */
+    int splits;              /* 0: as planned by pcd_sparse_conv_wgrad_v2; > 0: slabs written by pcd_sparse_conv_wgrad_os */
     int layout;              /* of dweight: 0 = [cout][K][cin] (spconv weights), 1 = [cout][cin][K] (nn.Conv2d weights
                               * [cout, cin, 3, 3]: the dense 3x3 convs of the BEV stack write straight into .grad) */
     int cout_write;          /* 0 = cout; else only the first cout_write output channels are reduced and written (dweight
@@ -600,18 +593,8 @@ size_t pcd_bn_workspace_bytes(int c);
 /* out[c] = sum over the n rows of x [n][c] (bias gradient); workspace = pcd_bn_workspace_bytes(c). */
 int pcd_col_sum(const void *x, int dtype, int n, int c, float *out, const int32_t *n_dev, void *workspace,
                 size_t workspace_bytes, void *stream);
-int pcd_bn_forward(const void *x, const void *residual, int dtype, int n, int c, const float *gamma,
-                   const float *beta, float eps, float momentum, int training, float *running_mean,
-                   float *running_var, int relu, void *y, float *save_mean, float *save_invstd,
-                   const int32_t *n_dev, const float *ext_partial, int ext_rows, void *workspace,
-                   size_t workspace_bytes, void *stream);
-int pcd_bn_backward(const void *dy, const void *x, const void *y, int dtype, int n, int c,
-                    const float *gamma, const float *beta, const float *save_mean, const float *save_invstd,
-                    int relu, int training, void *dx, void *dresidual, float *dgamma, float *dbeta,
-                    const int32_t *n_dev, const float *ext_partial, int ext_rows, float *colsum_partial,
-                    void *workspace, size_t workspace_bytes, void *stream);
-/* The same two calls for a BatchNorm whose OUTPUT (forward) / output GRADIENT (backward) is a column block of a wider
- * row-major matrix: y_ld / dy_ld = row stride in elements (>= c, a multiple of the 16-byte piece).  Lets the two
+/* The OUTPUT (forward) / output GRADIENT (backward) of the BatchNorm may be a column block of a wider row-major matrix:
+ * y_ld / dy_ld = row stride in elements (>= c, a multiple of the 16-byte piece; c for a matrix of its own).  Lets the two
  * deblock BatchNorms of BaseBEVBackbone write straight into the concatenated map and read their halves of its
  * gradient (base_bev_backbone.py:103-108 torch.cat) without a copy either way. */
 int pcd_bn_forward_ld(const void *x, const void *residual, int dtype, int n, int c, const float *gamma,
@@ -649,28 +632,16 @@ int pcd_col_sum_finalize(const PcdColsumJob *jobs_host, int n_jobs, void *stream
  *   receives the gradient norm.  n % 4 == 0, buffers 16-byte aligned.  Two passes over the buffers, 3 launches.
  * ============================================================================================ */
 size_t pcd_adam_flat_workspace_bytes(void);
-int pcd_adam_flat_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr,
-                       float beta1, float beta2, float eps, float weight_decay, float max_norm, float pre_divisor,
-                       float *step_dev, float *norm_out, void *workspace, size_t workspace_bytes, void *stream);
-/* v2: decoupled_wd != 0 gives the reference's adam_onecycle rule -- OptimWrapper(true_wd=True, bn_wd=True),
+/* decoupled_wd != 0 gives the reference's adam_onecycle rule -- OptimWrapper(true_wd=True, bn_wd=True),
  * tools/train_utils/optimization/__init__.py:19-32 + fastai_optim.py:135-150: every parameter is first multiplied
  * by (1 - lr * weight_decay), then Adam runs WITHOUT a weight-decay term; decoupled_wd == 0 is torch.optim.Adam's L2
- * form (v1).  hyper_dev (may be NULL): device float[2] = {lr, beta1} of THIS step, overriding the host arguments, so a
+ * form.  hyper_dev (may be NULL): device float[2] = {lr, beta1} of THIS step, overriding the host arguments, so a
  * OneCycle schedule (learning_schedules_fastai.py:60-77: lr and MOMS vary every step) can drive a replayed hipGraph;
- * the bias correction uses the current beta1 like torch.optim.Adam does. */
-int pcd_adam_flat_step_v2(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr,
-                          float beta1, float beta2, float eps, float weight_decay, float max_norm, float pre_divisor,
-                          int decoupled_wd, const float *hyper_dev, float *step_dev, float *norm_out, void *workspace,
-                          size_t workspace_bytes, void *stream);
-/* v3: the WHOLE OneCycle schedule as a device table schedule_dev[schedule_len][2] = {lr, beta1} per update
- * (learning_schedules_fastai.py:60-77 evaluated once on the host): the kernel reads row min(*step_dev, len - 1) itself
- * -- no lookup launches in front of the step -- and mirrors the pair into hyper_dev (may be NULL).  schedule_dev ==
- * NULL: v2 behaviour. */
-int pcd_adam_flat_step_v3(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr,
-                          float beta1, float beta2, float eps, float weight_decay, float max_norm, float pre_divisor,
-                          int decoupled_wd, float *hyper_dev, const float *schedule_dev, int schedule_len,
-                          float *step_dev, float *norm_out, void *workspace, size_t workspace_bytes, void *stream);
-/* v3 + zero_grad: the gradient buffer is cleared as it is consumed (the next step's zero_grad without a fill launch). */
+ * the bias correction uses the current beta1 like torch.optim.Adam does.
+ * schedule_dev (may be NULL): the WHOLE OneCycle schedule as a device table schedule_dev[schedule_len][2] = {lr, beta1} per
+ * update (learning_schedules_fastai.py:60-77 evaluated once on the host): the kernel reads row min(*step_dev, len - 1) itself
+ * -- no lookup launches in front of the step -- and mirrors the pair into hyper_dev.
+ * zero_grad != 0: the gradient buffer is cleared as it is consumed (the next step's zero_grad without a fill launch). */
 int pcd_adam_flat_step_v4(float *param, float *grad, int zero_grad, float *exp_avg, float *exp_avg_sq, size_t n, float lr,
                           float beta1, float beta2, float eps, float weight_decay, float max_norm, float pre_divisor,
                           int decoupled_wd, float *hyper_dev, const float *schedule_dev, int schedule_len, float *step_dev,
@@ -1124,17 +1095,14 @@ int pcd_conv2d_pack_weight(const float *weight, int cin, int cout, int mode, voi
  * cout padded to 32, mode, first workgroup, 16-byte pieces = packed bytes / 16}, total_blocks = sum of
  * ceil(pieces / 256) (rows ordered by first workgroup) */
 int pcd_conv2d_pack_weights_batched(const void *table, int n, int total_blocks, void *stream);
-int pcd_conv2d_3x3_nhwc(const void *x, int batch, int height, int width, int cin, const void *packed_w, int cout,
-                        const float *bias, void *y, void *stream);
-/* the same conv on CHANNEL BLOCKS of wider maps: x_cs / y_cs = channels per pixel of the buffers x / y point into
- * (>= cin / cout, multiples of 8): the five branches of a SeparateHead (center_head.py:11-46) read their 64 channels of
- * one 320-channel activation and their data gradients fill its gradient block by block -- no slice copies, no adds */
-int pcd_conv2d_3x3_nhwc_ld(const void *x, int x_cs, int batch, int height, int width, int cin, const void *packed_w,
-                           int cout, const float *bias, void *y, int y_cs, void *stream);
-/* ... and with the BatchNorm sums of the sparse path's PcdBnReduce taken in its epilogue (y_cs == cout required): mode 1 on
- * the forward launch for the BatchNorm behind the conv, mode 2 on the data-gradient launch for the BatchNorm whose output
+/* The conv on CHANNEL BLOCKS of wider maps: x_cs / y_cs = channels per pixel of the buffers x / y point into
+ * (>= cin / cout, multiples of 8; cin / cout for maps of their own): the five branches of a SeparateHead (center_head.py:11-46)
+ * read their 64 channels of one 320-channel activation and their data gradients fill its gradient block by block -- no slice
+ * copies, no adds.
+ * bn_reduce (NULL = off; y_cs == cout required): the BatchNorm sums of the sparse path's PcdBnReduce taken in the epilogue: mode 1
+ * on the forward launch for the BatchNorm behind the conv, mode 2 on the data-gradient launch for the BatchNorm whose output
  * was the conv's input (x / y = that BatchNorm's input / output as [pixels][cout] bf16).  partial_rows must equal
- * pcd_conv2d_3x3_tiles(batch, height, width); hand partial / mid to pcd_bn_forward / _backward as ext_partial. */
+ * pcd_conv2d_3x3_tiles(batch, height, width); hand partial / mid to pcd_bn_forward_ld / pcd_bn_backward_ld as ext_partial. */
 int pcd_conv2d_3x3_tiles(int batch, int height, int width);
 int pcd_conv2d_3x3_nhwc_bn(const void *x, int x_cs, int batch, int height, int width, int cin, const void *packed_w,
                            int cout, const float *bias, void *y, int y_cs, const PcdBnReduce *bn_reduce, void *stream);

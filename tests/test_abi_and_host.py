@@ -27,9 +27,58 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(handle, name), f"{name} declared in pcd_ops.h but not exported"
     assert sorted(_lib.PROTOTYPES) == declared, "ctypes prototypes out of sync with the header"
     lib = _lib.lib()
-    assert lib.pcd_version() >= 200
+    assert lib.pcd_version() >= 300
     assert lib.pcd_build_arch() == b"gfx950"
     assert lib.pcd_error_string(-3).decode().startswith("batch")
+
+
+def test_prototypes_are_derived_from_the_header_type_for_type():
+    """_lib.PROTOTYPES is parsed from include/pcd_ops.h: one declaration of every kind against its signature written out
+    by hand (float runs, long long strides, size_t both ways, unsigned long long *, const char * both ways, a struct pointer,
+    array parameters behind /*[n]*/ comments, (void))."""
+    from com_amd import _lib
+    i, vp, sz, f, ll = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_float, ctypes.c_longlong
+    want = {
+        "pcd_adam_flat_step_v4": (i, [vp, vp, i, vp, vp, sz, f, f, f, f, f, f, f, i, vp, vp, i, vp, vp, vp, sz, vp]),
+        "pcd_roi_head_loss_forward": (i, [vp, i, ll, vp, i, ll, vp, vp, vp, vp, vp, i, vp, f, f, f, i, vp, vp, vp]),
+        "pcd_nms_workspace_bytes": (sz, [i]),
+        "pcd_nms_bev": (i, [vp, i, f, i, vp, vp, vp, sz, vp]),
+        "pcd_stream_capture_id": (i, [vp, vp]),
+        "pcd_error_string": (ctypes.c_char_p, [i]),
+        "pcd_set_option": (i, [ctypes.c_char_p, i]),
+        "pcd_set_last_hip_error": (None, [i]),
+        "pcd_roi_head_sample_targets": (i, [vp] * 20),
+        "pcd_voxelize_hard_sorted_rank_words": (i, [i, vp, vp, i, vp, vp]),
+        "pcd_version": (i, []),
+    }
+    for name, (res, args) in want.items():
+        got_res, got_args = _lib.PROTOTYPES[name]
+        assert got_res is res, name
+        assert len(got_args) == len(args) and all(a is b for a, b in zip(got_args, args)), (name, got_args)
+    one = _lib.parse_prototypes("int pcd_a(const float *x /*[6]*/, const int shape[3],\n unsigned long long n, double d);")
+    assert one == {"pcd_a": (i, [vp, vp, ctypes.c_ulonglong, ctypes.c_double])}
+
+
+def test_header_parser_refuses_what_it_does_not_know():
+    """An unknown type is an error that names the declaration, never a guessed default."""
+    from com_amd import _lib
+    for bad in ("int pcd_good(int n);\nint pcd_bad(int n, short flags);", "wchar_t pcd_bad(void);", "int pcd_bad(int);"):
+        with pytest.raises(_lib.PcdError, match="pcd_bad"):
+            _lib.parse_prototypes(bad)
+    with pytest.raises(_lib.PcdError, match="PCD_BAD"):
+        _lib.parse_constants("#define PCD_BAD sizeof(int)")
+
+
+def test_integer_constants_are_read_from_the_header():
+    from com_amd import _lib
+    from com_amd.hotpath import anchor_head
+    text = open(os.path.join(ROOT, "include", "pcd_ops.h")).read()
+    assert "#define PCD_ANCHOR_CUR_ACCUM (3 + 2 * PCD_ANCHOR_CUR_GROUPS)" in text and "#define PCD_BN_EXT_MID (-1)" in text
+    assert _lib.PCD_ANCHOR_CUR_ACCUM == 195 and _lib.PCD_BN_EXT_MID == -1 and _lib.BN_EXT_MID == -1
+    assert _lib.PCD_ERR_UNSUPPORTED == -2 and _lib.PCD_ERR_LAUNCH == -5 and _lib.PCD_BF16 == 1
+    assert _lib.parse_constants("#define PCD_A 4 /* x */\n#define PCD_B (PCD_A * 2 - 1)\n#define PCD_GUARD_H_\n") == {"PCD_A": 4, "PCD_B": 7}
+    assert anchor_head.MAX_KINDS == _lib.PCD_ANCHOR_MAX_KINDS == 32 and _lib.POSTPROC_MAX_K == _lib.PCD_POSTPROC_MAX_K == 4096
+    assert _lib.WGRAD_MAX_JOBS == _lib.PCD_WGRAD_MAX_JOBS and _lib.COUNT_CHECK_MAX == _lib.PCD_COUNT_CHECK_MAX
 
 
 def test_header_lists_exactly_the_tuning_options_of_the_library():
@@ -52,16 +101,20 @@ def test_header_lists_exactly_the_tuning_options_of_the_library():
 
 def test_retired_kernels_are_out_of_the_library():
     """The measured-slower kernels were retired: the library exports none of their entry points (the
-    five of the former EXPERIMENTS build and the two of the plane-form dense weight gradient), has no 128-channel window
-    configuration, and rejects their option keys like any unknown key."""
+    five of the former EXPERIMENTS build and the two of the plane-form dense weight gradient), nor the entry points whose
+    successors take a superset of their arguments (ABI 0.3.0); it has no 128-channel window configuration, and rejects the
+    retired option keys like any unknown key."""
     from com_amd import _lib
     default = ctypes.CDLL(_lib.LIB_PATH)
     retired = ["pcd_sparse_conv_gather_gemm_zfast", "pcd_sparse_conv_pairs", "pcd_sparse_conv_pairs_seg",
                "pcd_sparse_conv_pairs_seg_bytes", "pcd_sparse_conv_pairs_tiles",
-               "pcd_conv2d_wgrad_planes_splits", "pcd_conv2d_wgrad_planes_nhwc"]
+               "pcd_conv2d_wgrad_planes_splits", "pcd_conv2d_wgrad_planes_nhwc",
+               "pcd_adam_flat_step", "pcd_adam_flat_step_v2", "pcd_adam_flat_step_v3", "pcd_sparse_conv_wgrad",
+               "pcd_sparse_conv_dgrad_classes", "pcd_bn_forward", "pcd_bn_backward", "pcd_conv2d_3x3_nhwc",
+               "pcd_conv2d_3x3_nhwc_ld", "pcd_sparse_conv_gather_gemm_tiles"]
     for name in retired:
         assert not hasattr(default, name), f"{name} was retired: it must not be in the library"
-    assert not set(retired) & set(_declared_symbols())
+    assert not set(retired) & set(_declared_symbols()) and not set(retired) & set(_lib.PROTOTYPES)
     lib = _lib.lib()
     assert lib.pcd_subm_window_tile_rows(128, 128) == 0 and lib.pcd_subm_window_tile_rows(64, 64) > 0
     value = ctypes.c_int()
@@ -73,17 +126,21 @@ def test_retired_kernels_are_out_of_the_library():
 
 
 def test_header_structs_match_ctypes_mirrors(tmp_path):
-    """The by-value / by-pointer structs of the C ABI (PcdBnReduce, PcdColsumJob, PcdWgradReduceJob) as gcc lays
-    them out from include/pcd_ops.h == the ctypes.Structure mirrors in com_amd/_lib.py (size and field offsets)."""
+    """Every by-value / by-pointer struct of the C ABI as gcc lays it out from include/pcd_ops.h == its ctypes.Structure
+    mirror in com_amd/_lib.py (size and every field offset).  PcdRoiSampler has no typedef: C names it `struct PcdRoiSampler`."""
     import subprocess
     from com_amd import _lib
-    structs = {"PcdBnReduce": _lib.PcdBnReduce, "PcdColsumJob": _lib.PcdColsumJob,
-               "PcdWgradReduceJob": _lib.PcdWgradReduceJob, "PcdComCurriculum": _lib.PcdComCurriculum}
+    mirrors = {n: c for n, c in vars(_lib).items() if isinstance(c, type) and issubclass(c, ctypes.Structure)}
+    assert sorted(mirrors) == ["PcdAnchorCurriculum", "PcdBnReduce", "PcdColsumJob", "PcdComCurriculum", "PcdCountCheck",
+                               "PcdPostprocConfig", "PcdPostprocHead", "PcdRoiSampler", "PcdWgradReduceJob"]
+    header = open(os.path.join(ROOT, "include", "pcd_ops.h")).read()
+    structs = {(n if f"}} {n};" in header else f"struct {n}"): c for n, c in mirrors.items()}
+    assert "struct PcdRoiSampler" in structs
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "pcd_ops.h"', 'int main(void) {']
     for name, st in structs.items():
-        lines.append(f'printf("{name} size %zu\\n", sizeof({name}));')
+        lines.append(f'printf("{name}|size|%zu\\n", sizeof({name}));')
         for field, _ in st._fields_:
-            lines.append(f'printf("{name} {field} %zu\\n", offsetof({name}, {field}));')
+            lines.append(f'printf("{name}|{field}|%zu\\n", offsetof({name}, {field}));')
     lines += ['return 0; }']
     src = tmp_path / "abi.c"
     src.write_text("\n".join(lines))
@@ -92,7 +149,7 @@ def test_header_structs_match_ctypes_mirrors(tmp_path):
     got = {}
     for line in subprocess.check_output([str(exe)]).decode().split("\n"):
         if line:
-            a, b, c = line.split()
+            a, b, c = line.split("|")
             got[(a, b)] = int(c)
     for name, st in structs.items():
         assert got[(name, "size")] == ctypes.sizeof(st), name
