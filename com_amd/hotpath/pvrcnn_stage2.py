@@ -4,6 +4,7 @@ natives of com_amd.pointnet2_stack with the reference's module names and dataflo
   * `StackSAModuleMSG`          pcdet/ops/pointnet2/pointnet2_stack/pointnet2_modules.py:31-110 (ball query + grouping in
                                 HIP; the shared 1x1-conv MLPs + max-pool stay torch, as in the reference)
   * `get_voxel_centers`         pcdet/utils/common_utils.py:66-82
+  * `generate_voxel2pinds`      pcdet/utils/common_utils.py:244-252 (the dense voxel -> row map of Voxel R-CNN's pooling)
   * `sample_keypoints`          VoxelSetAbstraction.get_sampled_points, FPS branch
   * `sectorized_proposal_centric_sampling` (+ `sample_points_with_roi`, `sector_fps`)   its SPC branch (PV-RCNN++)
                                 (pcdet/models/backbones_3d/pfe/voxel_set_abstraction.py:236-263): farthest point sampling of
@@ -36,6 +37,19 @@ def get_voxel_centers(voxel_coords, downsample_times, voxel_size, point_cloud_ra
     vs = torch.tensor(voxel_size, device=centers.device).float() * downsample_times
     pc = torch.tensor(point_cloud_range[0:3], device=centers.device).float()
     return (centers + 0.5) * vs + pc
+
+
+def generate_voxel2pinds(sparse_tensor, out=None):
+    """int32 [B, Z, Y, X]: the row of the voxel at (b, z, y, x), -1 where there is none (common_utils.py:244-252).  Rows at or
+    beyond `sparse_tensor.num_rows` (a device count, when the row dimension is a capacity) are left out; nothing is read
+    back.  `out`: a map that is -1 everywhere, written in place (P.voxel2pinds_clear restores it)."""
+    shape = [int(sparse_tensor.batch_size)] + [int(v) for v in sparse_tensor.spatial_shape]
+    indices = sparse_tensor.indices
+    if out is None:
+        out = torch.full(shape, -1, dtype=torch.int32, device=indices.device)
+    elif list(out.shape) != shape:
+        raise P.L.PcdError(f"generate_voxel2pinds: out {tuple(out.shape)}, want {tuple(shape)}")
+    return P.voxel2pinds_scatter(indices.int().contiguous(), out, getattr(sparse_tensor, 'num_rows', None))
 
 
 class StackSAModuleMSG(nn.Module):

@@ -59,7 +59,8 @@ extern "C" {
 /* ---- library info -------------------------------------------------------------------------- */
 int pcd_version(void);                    /* 10000*major + 100*minor + patch; 0.2.0: the two entry points of the
                                              plane-form dense weight gradient left the ABI; 0.3.0: the entry points whose
-                                             successors take a superset of their arguments left it.  A missing lower
+                                             successors take a superset of their arguments left it; 0.4.0: the
+                                             pcd_voxel2pinds_* / pcd_voxel_pool_* entry points joined.  A missing lower
                                              version number (pcd_adam_flat_step_v4 without _v3, pcd_sparse_conv_wgrad_v2
                                              without the unsuffixed form, _ld / _bn / _dir without the plain form) means
                                              "retired": the survivors keep their names */
@@ -931,6 +932,59 @@ int pcd_three_interpolate_stack_grad(int N, int C, const float *grad_out, const 
 int pcd_voxel_query_stack(int M, int R1, int R2, int R3, int nsample, float radius, int z_range, int y_range, int x_range,
                           const float *new_xyz, const float *xyz, const int32_t *new_coords, const int32_t *point_indices,
                           int32_t *idx, void *stream);
+
+/* ============================================================================================
+ * (f5) Voxel R-CNN's RoI-grid pooling -- the hot path of NeighborVoxelSAModuleMSG
+ *      (pcdet/ops/pointnet2/pointnet2_stack/voxel_pool_modules.py:70-130) as query + fused gather / max-pool, with no
+ *      [M][C][nsample] tensor anywhere.  Row numbers are GLOBAL rows of the stacked level (no per-frame offsets, no
+ *      *_batch_cnt); float32 / int32; every call is capturable (no host read-back).
+ *
+ *   pcd_voxel2pinds_scatter / _clear   common_utils.py:244-252 (generate_voxel2pinds -> spconv's scatter_point_inds):
+ *      indices [N][4] (b, z, y, x), map int32 [B][Z][Y][X]; scatter writes the row number, clear writes -1 at the same
+ *      cells (a map filled with -1 ONCE stays reusable at the cost of N stores per step instead of a fill of the volume).
+ *      num_rows: optional device int32[1], the real row count when N is a capacity; rows at or beyond it, and rows whose
+ *      coordinates lie outside the map, are ignored by both.
+ *
+ *   pcd_voxel_pool_query   voxel_query_gpu.cu:10-88 (first nsample hits in (dz, dy, dx) scan order, probes clipped at the
+ *      grid borders, new_coords [M][4] (b, z, y, x) anywhere -- also outside the grid; a frame index outside [0, B) is an
+ *      empty ball) + voxel_query_utils.py:39-40,85-91 + the statistics voxel_pool_modules.py:104-109 feeds to BatchNorm2d.
+ *      PCD_VOXEL_POOL_GROUP lanes share a query and probe consecutive cells of the scan order (ballot + prefix popcount
+ *      keep the order; a group stops once it has nsample hits).  nsample <= PCD_VOXEL_POOL_MAX_NSAMPLE.
+ *        idx [M][nsample]  global rows; slots behind the last hit repeat the first hit; an empty ball is all 0
+ *        cnt [M]           distinct hits, capped at nsample (0: empty ball)
+ *        partial           double [pcd_div_up(M, PCD_VOXEL_POOL_QUERIES_PER_WG)][9]: per-workgroup sums over the slots of
+ *                          r = xyz[idx] - new_xyz (a repeated slot as often as it is repeated, an empty ball as r = 0):
+ *                          x, y, z, xx, xy, xz, yy, yz, zz
+ *        moments           double [9]: the partials joined in a fixed order (bit-reproducible)
+ *
+ *   pcd_voxel_pool_fwd     voxel_pool_modules.py:99-116 behind mlps_in, with mlps_pos (Conv2d(3, C) + BatchNorm2d) folded
+ *      to the affine A [C][3], b [C]:  out[m][c] = max_s relu(fin[idx[m][s]][c] + (A_c . r[m][s] + b_c)) over the cnt[m]
+ *      distinct slots, strict > in ascending s (what max_pool2d selects over the padded row); an empty ball gives
+ *      relu(b_c).  arg [M][C] uint8: the winning slot.  1 <= C <= PCD_VOXEL_POOL_MAX_C; lanes run along c.
+ *
+ *   pcd_voxel_pool_bwd     its gradient through the saved winner: where out[m][c] > 0, d_fin[idx[m][arg]][c] += g[m][c]
+ *      (non-empty balls only: voxel_pool_modules.py:99 zeroes the grouped features of an empty one in place; fp32 atomics
+ *      into the caller-zeroed d_fin), dA_c += g r*, db_c += g -- these through per-workgroup partials
+ *      float [pcd_div_up(M, PCD_VOXEL_POOL_BWD_QUERIES_PER_WG)][C][4] joined in a fixed order into dA [C][3], db [C].
+ * ============================================================================================ */
+#define PCD_VOXEL_POOL_GROUP 16
+#define PCD_VOXEL_POOL_QUERIES_PER_WG 16
+#define PCD_VOXEL_POOL_BWD_QUERIES_PER_WG 128
+#define PCD_VOXEL_POOL_MAX_NSAMPLE 64
+#define PCD_VOXEL_POOL_MAX_C 128
+int pcd_voxel2pinds_scatter(const int32_t *indices, int N, const int32_t *num_rows, int32_t *map, int B, int Z, int Y, int X,
+                            void *stream);
+int pcd_voxel2pinds_clear(const int32_t *indices, int N, const int32_t *num_rows, int32_t *map, int B, int Z, int Y, int X,
+                          void *stream);
+int pcd_voxel_pool_query(int M, int N, int B, int Z, int Y, int X, int nsample, float radius, int z_range, int y_range,
+                         int x_range, const float *new_xyz, const float *xyz, const int32_t *new_coords, const int32_t *map,
+                         int32_t *idx, int32_t *cnt, double *partial, double *moments, void *stream);
+int pcd_voxel_pool_fwd(int M, int N, int C, int nsample, const float *fin, const float *A, const float *b, const float *xyz,
+                       const float *new_xyz, const int32_t *idx, const int32_t *cnt, float *out, unsigned char *arg,
+                       void *stream);
+int pcd_voxel_pool_bwd(int M, int N, int C, int nsample, const float *g, const float *out, const unsigned char *arg,
+                       const float *xyz, const float *new_xyz, const int32_t *idx, const int32_t *cnt, float *d_fin_zeroed,
+                       float *partial, float *dA, float *db, void *stream);
 
 /* ============================================================================================
  * (g) fp8 feature path (BASELINE config 5; build-side precision, the reference is fp32): OCP e4m3 activations and
