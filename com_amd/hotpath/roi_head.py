@@ -422,10 +422,8 @@ class PVRCNNHead(RoIHeadTemplate):
         super().__init__(num_class=num_class, model_cfg=model_cfg)
         pool = _get(model_cfg, 'ROI_GRID_POOL')
         self.grid_size = int(_get(pool, 'GRID_SIZE'))
-        mlps = [[input_channels] + list(m) for m in _get(pool, 'MLPS')]     # build_local_aggregation_module (pointnet2_modules.py:10-27)
-        self.roi_grid_pool_layer = StackSAModuleMSG(radii=list(_get(pool, 'POOL_RADIUS')), nsamples=list(_get(pool, 'NSAMPLE')),
-                                                    mlps=mlps, use_xyz=True, pool_method='max_pool')
-        num_c_out = sum(m[-1] for m in mlps)
+        # (StackSAModuleMSG or, for PV-RCNN++, VectorPoolAggregationModuleMSG: pointnet2_modules.py:10-27)
+        self.roi_grid_pool_layer, num_c_out = P.build_local_aggregation_module(input_channels=input_channels, config=pool)
         pre_channel = self.grid_size ** 3 * num_c_out
         dp = _get(model_cfg, 'DP_RATIO')
         shared_fc = list(_get(model_cfg, 'SHARED_FC'))
@@ -447,7 +445,8 @@ class PVRCNNHead(RoIHeadTemplate):
     def _refuse(cls, model_cfg, num_class):
         """the configurations outside the scope of the kernels: a PcdError that names the key"""
         no = super()._refuse(model_cfg, num_class)
-        if _get(_get(model_cfg, 'ROI_GRID_POOL'), 'NAME', 'StackSAModuleMSG') != 'StackSAModuleMSG':
+        if _get(_get(model_cfg, 'ROI_GRID_POOL'), 'NAME', 'StackSAModuleMSG') not in ('StackSAModuleMSG',
+                                                                                      'VectorPoolAggregationModuleMSG'):
             no('ROI_GRID_POOL.NAME', f"= {_get(_get(model_cfg, 'ROI_GRID_POOL'), 'NAME')!r}")
 
     def make_fc_layers(self, input_channels, output_channels, fc_list):

@@ -60,7 +60,8 @@ extern "C" {
 int pcd_version(void);                    /* 10000*major + 100*minor + patch; 0.2.0: the two entry points of the
                                              plane-form dense weight gradient left the ABI; 0.3.0: the entry points whose
                                              successors take a superset of their arguments left it; 0.4.0: the
-                                             pcd_voxel2pinds_* / pcd_voxel_pool_* entry points joined.  A missing lower
+                                             pcd_voxel2pinds_* / pcd_voxel_pool_* entry points joined; 0.5.0: the
+                                             pcd_vector_pool_* entry points joined.  A missing lower
                                              version number (pcd_adam_flat_step_v4 without _v3, pcd_sparse_conv_wgrad_v2
                                              without the unsuffixed form, _ld / _bn / _dir without the plain form) means
                                              "retired": the survivors keep their names */
@@ -985,6 +986,65 @@ int pcd_voxel_pool_fwd(int M, int N, int C, int nsample, const float *fin, const
 int pcd_voxel_pool_bwd(int M, int N, int C, int nsample, const float *g, const float *out, const unsigned char *arg,
                        const float *xyz, const float *new_xyz, const int32_t *idx, const int32_t *cnt, float *d_fin_zeroed,
                        float *partial, float *dA, float *db, void *stream);
+
+/* ============================================================================================
+ * (f6) PV-RCNN++'s VectorPool aggregation -- the five natives of pcdet/ops/pointnet2/pointnet2_stack/src/vector_pool_gpu.cu
+ *      behind VectorPoolAggregationModuleMSG (pointnet2_modules.py:160-470), without a neighbour list in global memory, an
+ *      atomic counter, a read-back or a buffer sized by the data: every call is capturable.  Stacked batches: rows of frame b
+ *      are the xyz_batch_cnt[b] rows behind those of frame b - 1; a query sees the rows of ITS frame only.  float32 / int32.
+ *      M == 0 or N == 0: success without a launch (the caller's buffers hold the empty result).
+ *
+ *   pcd_vector_pool_three_nn   query_stacked_local_neighbor_idxs_kernel + query_three_nn_by_stacked_local_idxs_kernel
+ *      (vector_pool_gpu.cu:19-205) and the resize loop of pointnet2_utils.py:331-347, fused.  A query's list is the first
+ *      min(PCD_VECTOR_POOL_MAX_NEIGHBORS, nsample > 0 ? nsample : PCD_VECTOR_POOL_MAX_NEIGHBORS) rows of its frame within
+ *      query_distance (the caller passes max_neighbour_distance * neighbor_distance_multiplier), in ascending row order;
+ *      neighbor_type 1 is the ball test dx^2 + dy^2 + dz^2 > r^2, anything else the cube test |d| > r per axis, both on
+ *      local = support - new in f32.  Per grid centre: the three smallest d = (cx-x)*(cx-x) + (cy-y)*(cy-y) + (cz-z)*(cz-z)
+ *      (f32, left to right, no contraction), ties to the earlier list position -- ordered by (d, position), which is what the
+ *      reference's sequential strict `<` yields.  One neighbour fills slots 2 and 3 with slot 1, two fill slot 3 with slot 1.
+ *      One wave per query: a cooperative coalesced scan (ballot + prefix popcount keep the row order, the scan ends at the
+ *      cap), the list as xyz + row in LDS, all G centres served from there.
+ *        idx [M][G][3]      global rows; all three -1 when the list is empty
+ *        dist2 [M][G][3]    squared distances; +inf when the list is empty (the reference's 1e40 stored as float)
+ *        neighbor_cnt [M]   length of the list
+ *
+ *   pcd_vector_pool_interpolate_forward / _backward   pointnet2_modules.py:220-238 (weights, three_interpolate, the nine
+ *      centre - neighbour coordinates, cat, new_features[empty_mask] = 0) as one pass:  out [M][G * (C + 9)], per cell the C
+ *      interpolated channels, then centre - neighbour_j in slot order; w_j = (1 / (sqrt(d2_j) + 1e-8)) / max(sum, 1e-8); an
+ *      empty cell (idx -1) is all zeros.  Backward: grad_support_features_zeroed [N][C] += w_j * grad_out[m][g][c] (fp32
+ *      atomics: not bit-reproducible; lanes run along c); idx and dist2 carry no gradient (pointnet2_modules.py:212).
+ *
+ *   pcd_vector_pool_voxel_query_forward / _backward   vector_pool_kernel_stack / vector_pool_grad_kernel_stack
+ *      (vector_pool_gpu.cu:243-458) for pooling_type 1 ("voxel_random_choice": the lowest row of each sub-voxel).  Cube / ball
+ *      test as above with r = max_neighbour_distance; grid_size_a = max_neighbour_distance * 2 / num_grid_a; cell =
+ *      floorf((local_a + r) / grid_size_a) per axis, combined x-major and THEN clamped to [0, G - 1]; a query stops once
+ *      min(G, nsample > 0 ? nsample : G) cells are filled.  G <= PCD_VECTOR_POOL_MAX_GRIDS.  pooling_type 0 and
+ *      num_c_in != num_c_out_each_grid are PCD_ERR_INVALID_ARG.  One wave per query, the frame's xyz staged through LDS.
+ *        new_features [M][G * c], new_local_xyz [M][3 * G] (0 where a cell is empty), point_cnt_of_grid [M][G] (0 / 1),
+ *        src_row [M][G] global row of the cell's point, -1: none (replaces the reference's grouped_idxs list)
+ *      Backward: grad_support_features_zeroed[src_row[m][g]][:] += grad_new_features[m][g][:] (fp32 atomics).
+ * ============================================================================================ */
+#define PCD_VECTOR_POOL_MAX_NEIGHBORS 1000
+#define PCD_VECTOR_POOL_MAX_GRIDS 64
+#define PCD_VECTOR_POOL_NN_QUERIES_PER_WG 2
+#define PCD_VECTOR_POOL_VQ_QUERIES_PER_WG 8
+int pcd_vector_pool_three_nn(int B, int M, int N, int G, const float *support_xyz, const int32_t *xyz_batch_cnt,
+                             const float *new_xyz, const float *new_xyz_grid_centers, const int32_t *new_xyz_batch_cnt,
+                             float query_distance, int nsample, int neighbor_type, int32_t *idx, float *dist2,
+                             int32_t *neighbor_cnt, void *stream);
+int pcd_vector_pool_interpolate_forward(int M, int N, int G, int C, const int32_t *idx, const float *dist2,
+                                        const float *support_xyz, const float *support_features,
+                                        const float *new_xyz_grid_centers, float *out, void *stream);
+int pcd_vector_pool_interpolate_backward(int M, int N, int G, int C, const int32_t *idx, const float *dist2,
+                                         const float *grad_out, float *grad_support_features_zeroed, void *stream);
+int pcd_vector_pool_voxel_query_forward(int B, int M, int N, int num_c_in, int num_c_out_each_grid, int num_grid_x,
+                                        int num_grid_y, int num_grid_z, float max_neighbour_distance, int nsample,
+                                        int neighbor_type, int pooling_type, const float *support_xyz,
+                                        const int32_t *xyz_batch_cnt, const float *support_features, const float *new_xyz,
+                                        const int32_t *new_xyz_batch_cnt, float *new_features, float *new_local_xyz,
+                                        int32_t *point_cnt_of_grid, int32_t *src_row, void *stream);
+int pcd_vector_pool_voxel_query_backward(int M, int N, int G, int C, const float *grad_new_features, const int32_t *src_row,
+                                         float *grad_support_features_zeroed, void *stream);
 
 /* ============================================================================================
  * (g) fp8 feature path (BASELINE config 5; build-side precision, the reference is fp32): OCP e4m3 activations and
