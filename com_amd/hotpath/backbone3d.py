@@ -147,7 +147,7 @@ class _RulebookPrefetcher:
         w = widths.pop()
         bf16 = t.features.dtype == torch.bfloat16
         tables = not bf16 or any(not c.window_capable() or getattr(c, "fp8_train", None) is not None
-                                 or (c._needs_backward(t) and not Fsp._window_wgrad(c.out_channels)) for c in group)
+                                 or (c._needs_backward(t) and not Fsp.window_wgrad(c.out_channels)) for c in group)
         return w, tables
 
     @staticmethod
@@ -223,7 +223,7 @@ class _BackboneBase(nn.Module):
             self._rb_units = units
         cur = torch.cuda.current_stream()
         dev = x0.features.device
-        side = Fsp._side_stream(dev, "rulebook")
+        side = Fsp.side_stream(dev, "rulebook")
         pf = _RulebookPrefetcher(self._rb_units, x0, side)
         x0.indice_dict["__prefetcher__"] = pf
         depth = max(1, int(self.prefetch_depth))
@@ -234,7 +234,7 @@ class _BackboneBase(nn.Module):
         # (first conv at 0.27 ms with its rulebook ready at 0.06).  (Building unit 0 on the MAIN stream instead let the first
         # conv start earlier, but the other units then ran beside the gather kernels from the start and finished later: the
         # step was no faster, 3.44 vs 3.42 ms.)
-        u0 = Fsp._side_stream(dev, "rulebook0")
+        u0 = Fsp.side_stream(dev, "rulebook0")
         u0.wait_stream(cur)
         pf.advance(stream=u0)
         pf.unit0_stream = u0
@@ -247,7 +247,7 @@ class _BackboneBase(nn.Module):
             # `_version`; the flat Adam kernel does not, and it is the update pack_after_update() follows)
             if self._packed_versions == [c.weight._version for c in self._conv_list]:
                 return
-        pack_side = Fsp._side_stream(dev)                      # the wgrad stream is idle during the forward
+        pack_side = Fsp.side_stream(dev)                      # the wgrad stream is idle during the forward
         pack_side.wait_stream(cur)
         with torch.cuda.stream(pack_side):
             self._pack_all()

@@ -6,12 +6,11 @@ parameters and state-dict keys, base_bev_backbone.py:37-51 / center_head.py:17-2
 anything the kernel does not cover (other kernel sizes / strides, CPU tensors, fp32 maps outside a bf16 autocast
 region, cin % 32 != 0) takes
 nn.Conv2d's own path."""
-import os
-
 import torch
 import torch.nn as nn
 
 from .. import ops
+from ..spconv import functional as Fsp
 
 ENABLED = True
 # The following BatchNorm's statistics are taken in the dense conv's epilogue (PcdBnReduce mode 1 of pcd_conv2d_3x3_nhwc_bn)
@@ -98,61 +97,16 @@ def _plane_pairs(mode_f, B, hi, wi, device):
     return pairs, num
 
 
-def _scheduled_backward(need_dx, want_w, want_b, wp, bp, direct_ok, dgrad, wgrad, bsum, keep):
-    """The backward schedule shared by the dense convs (as in the sparse convs, spconv/functional.py): the data gradient
-    is issued first on the current stream, the weight / bias gradients run on the side stream from an event recorded
-    before it; with DIRECT_GRAD they are written straight into .grad (the slab reduction deferred to ONE launch at the
-    join, in the parameter's own layout) and the join is lagged -- no copy, no AccumulateGrad add, no per-layer reduce
-    launch.  dgrad() -> dx; wgrad(direct) -> dw or None; bsum(direct) -> db or None; keep = tensors alive until the join."""
-    from ..spconv import functional as Fsp
-    dx = dw = db = None
-    cur = torch.cuda.current_stream()
-    side = ready = None
-    if Fsp.OVERLAP_WGRAD and need_dx and (want_w or want_b):
-        ready = torch.cuda.Event()
-        ready.record(cur)
-    if need_dx:
-        dx = dgrad()
-    if ready is not None:
-        side = Fsp._side_stream(keep[0].device)
-        side.wait_event(ready)
-
-    def direct(ps):          # (wp / bp: one parameter or a list of them -- all or none)
-        ps = ps if isinstance(ps, (list, tuple)) else [ps]
-        return len(ps) > 0 and all(Fsp.DIRECT_GRAD and direct_ok and p is not None and p.grad is not None
-                                   and p.grad.dtype == torch.float32 and p.grad.is_contiguous() for p in ps)
-    direct_w, direct_b = want_w and direct(wp), want_b and direct(bp)
-    deferred = (Fsp.WGRAD_JOIN_LAG > 0 and side is not None and (direct_w or not want_w)
-                and (direct_b or not want_b))
-    if direct_w and deferred:
-        for p in (wp if isinstance(wp, (list, tuple)) else [wp]):
-            Fsp._claim_direct(p, "w")
-    if direct_b and deferred:
-        for p in (bp if isinstance(bp, (list, tuple)) else [bp]):
-            Fsp._claim_direct(p, "b")
-    with torch.cuda.stream(side) if side is not None else Fsp._NullCtx():
-        if ops.STAMPS is not None:
-            Fsp._STAMP_SEQ[0] += 1
-            ops.stamp(f"d2w{Fsp._STAMP_SEQ[0]}")
-        if want_w:
-            dw = wgrad(direct_w and deferred)
-        if want_b:
-            db = bsum(direct_b and deferred)
-        if deferred:
-            ev = torch.cuda.Event()
-            ev.record(side)
-    if deferred:
-        Fsp._PENDING.append((ev,) + tuple(keep) + (None,))     # inputs stay alive until the lagged join
-        if len(Fsp._PENDING) > Fsp.WGRAD_JOIN_LAG:
-            cur.wait_event(Fsp._PENDING[-1 - Fsp.WGRAD_JOIN_LAG][0])
-            del Fsp._PENDING[:len(Fsp._PENDING) - Fsp.WGRAD_JOIN_LAG]
-    elif side is not None:
-        cur.wait_stream(side)
-        for t in (dw, db):
-            for u in (t if isinstance(t, (list, tuple)) else [t]):
-                if u is not None:
-                    u.record_stream(cur)
-    return dx, dw, db
+class _PacksAhead:
+    def _take_packs(self):
+        """(pack_f, pack_d) made ahead by Conv3x3Packs.run() since the last weight update, or (None, None)."""
+        pf = pd = None
+        ahead = getattr(self, "_packs_ahead", None)
+        if ahead is not None:                        # use them ONCE
+            self._packs_ahead = None
+            if ahead[2] == self.weight._version:     # (an in-place change since run() -- load_state_dict, broadcast,
+                pf, pd = ahead[0], ahead[1]          #  a manual edit -- bumps the version: pack again from the weights)
+        return pf, pd
 
 
 class _Conv3x3Function(torch.autograd.Function):
@@ -164,7 +118,6 @@ class _Conv3x3Function(torch.autograd.Function):
     def forward(ctx, x, weight, bias, pack_f, pack_d, bn_follows=False):
         # x: [B, C, H, W] bf16, channels_last storage
         # bn_follows: a training-mode BatchNorm consumes the output -> its statistics are taken in this launch's epilogue
-        from ..spconv import functional as Fsp
         xn = x.detach().permute(0, 2, 3, 1)
         assert xn.is_contiguous()
         cout = weight.shape[0]
@@ -198,7 +151,6 @@ class _Conv3x3Function(torch.autograd.Function):
         if cp != cout:
             dyn = torch.nn.functional.pad(dyn, (0, cp - cout))
         dyn = dyn.contiguous()
-        from ..spconv import functional as Fsp
         want_w = ctx.needs_input_grad[1]
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         wp, bp = ctx.weight_param, ctx.bias_param
@@ -207,21 +159,21 @@ class _Conv3x3Function(torch.autograd.Function):
             pd = pack_d if pack_d is not None else ops.conv2d_pack_weight(weight, 1)
             return ops.conv2d_3x3_nhwc(dyn, pd, cin).permute(0, 3, 1, 2)
 
-        def wgrad(direct):
+        def wgrad(direct, jobs):
             if ops.conv2d_wgrad_splits(B, H, W, cin, cp) > 0:      # the dense kernel (no pair lists)
                 if direct:
-                    ops.conv2d_wgrad(xn, dyn, cout, out=wp.grad, defer=Fsp._WGRAD_JOBS)
+                    ops.conv2d_wgrad(xn, dyn, cout, out=wp.grad, defer=jobs)
                     return None
                 return ops.conv2d_wgrad(xn, dyn, cout).to(weight.dtype)
             pairs, num = _dense_pairs(B, H, W, xn.device)
             if direct:   # (zero-padded output channels: only the real rows of the slabs are reduced into .grad)
                 ops.wgrad(xn.reshape(-1, cin), cin, dyn.reshape(-1, cp), pairs, num, 9, out=wp.grad,
-                          defer=Fsp._WGRAD_JOBS, conv2d_layout=True, cout_write=cout if cp != cout else 0)
+                          defer=jobs, conv2d_layout=True, cout_write=cout if cp != cout else 0)
                 return None
             dwk = ops.wgrad(xn.reshape(-1, cin), cin, dyn.reshape(-1, cp), pairs, num, 9)  # [cp, 9, cin] f32
             return dwk[:cout].permute(0, 2, 1).reshape(cout, cin, 3, 3).to(weight.dtype)
 
-        def bsum(direct):
+        def bsum(direct, jobs):
             if direct and cp == cout:
                 ops.col_sum(dyn.reshape(-1, cp), out=bp.grad)
                 return None
@@ -230,12 +182,12 @@ class _Conv3x3Function(torch.autograd.Function):
                 return None
             return ops.col_sum(dyn.reshape(-1, cp))[:cout]   # fp32 column sums in a fixed order
 
-        dx, dw, db = _scheduled_backward(ctx.needs_input_grad[0], want_w, want_b, wp, bp, True, dgrad, wgrad, bsum,
-                                         (xn, dyn))
+        dx, dw, db = Fsp.scheduled_backward(ctx.needs_input_grad[0], want_w, want_b, wp, bp, dgrad, wgrad, bsum,
+                                            [xn, dyn])
         return dx, dw, db, None, None, None
 
 
-class Conv3x3(nn.Conv2d):
+class Conv3x3(_PacksAhead, nn.Conv2d):
     """nn.Conv2d whose forward takes the HIP kernel when it applies (see the module docstring)."""
 
     def _fast(self, x):
@@ -259,16 +211,6 @@ class Conv3x3(nn.Conv2d):
         pf, pd = self._take_packs()
         follows = bool(self.bn_follows and self.training and torch.is_grad_enabled())
         return _Conv3x3Function.apply(x, self.weight, self.bias, pf, pd, follows)
-
-    def _take_packs(self):
-        pf = pd = None
-        ahead = getattr(self, "_packs_ahead", None)
-        if ahead is not None:                        # Conv3x3Packs.run() since the last weight update: use them ONCE
-            self._packs_ahead = None
-            if ahead[2] == self.weight._version:     # (an in-place change since run() -- load_state_dict, broadcast,
-                pf, pd = ahead[0], ahead[1]          #  a manual edit -- bumps the version: pack again from the weights)
-        return pf, pd
-
 
 class _ConvPlanesFunction(torch.autograd.Function):
     """The stride-2 3x3 conv (mode 2) and the k = stride transposed convs (modes 4, 6) of BaseBEVBackbone through the
@@ -300,7 +242,6 @@ class _ConvPlanesFunction(torch.autograd.Function):
         if dyn.dtype != torch.bfloat16:
             dyn = dyn.to(torch.bfloat16)
         dyn = dyn.contiguous()
-        from ..spconv import functional as Fsp
         wp = ctx.weight_param
         kk = {2: 9, 4: 4, 6: 1}[mode_f]
 
@@ -308,21 +249,21 @@ class _ConvPlanesFunction(torch.autograd.Function):
             pd = pack_d if pack_d is not None else ops.conv2d_pack_weight(weight, mode_f + 1)
             return ops.conv2d_planes_nhwc(mode_f + 1, dyn, pd, cin, (H, W)).permute(0, 3, 1, 2)
 
-        def wgrad(direct):
+        def wgrad(direct, jobs):
             pairs, num = _plane_pairs(mode_f, B, H, W, xn.device)
             if mode_f == 2:       # gathered rows = x (contraction c = cin), accumulated rows = dy (o = cout)
                 a, ca, b_, cb = xn.reshape(-1, cin), cin, dyn.reshape(-1, cout), cout
             else:                 # transposed convs: roles swapped -> dW [cin, K, cout] = the parameter's layout
                 a, ca, b_, cb = dyn.reshape(-1, cout), cout, xn.reshape(-1, cin), cin
             if direct:
-                ops.wgrad(a, ca, b_, pairs, num, kk, out=wp.grad, defer=Fsp._WGRAD_JOBS, conv2d_layout=True)
+                ops.wgrad(a, ca, b_, pairs, num, kk, out=wp.grad, defer=jobs, conv2d_layout=True)
                 return None
             dwk = ops.wgrad(a, ca, b_, pairs, num, kk)                    # [cb, K, ca] f32
             k = int(round(kk ** 0.5))
             return dwk.permute(0, 2, 1).reshape(cb, ca, k, k).to(weight.dtype)
 
-        dx, dw, _ = _scheduled_backward(ctx.needs_input_grad[0], ctx.needs_input_grad[1], False, wp, None, True, dgrad,
-                                        wgrad, None, (xn, dyn))
+        dx, dw, _ = Fsp.scheduled_backward(ctx.needs_input_grad[0], ctx.needs_input_grad[1], False, wp, None, dgrad,
+                                           wgrad, None, [xn, dyn])
         return dx, dw, None, None, None
 
 
@@ -338,20 +279,7 @@ def _bf16_region(x):
     return x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16)
 
 
-class _PlaneConvMixin:
-    MODE_F = None
-
-    def _take_packs(self):
-        pf = pd = None
-        ahead = getattr(self, "_packs_ahead", None)
-        if ahead is not None:
-            self._packs_ahead = None
-            if ahead[2] == self.weight._version:
-                pf, pd = ahead[0], ahead[1]
-        return pf, pd
-
-
-class Conv3x3S2(_PlaneConvMixin, nn.Conv2d):
+class Conv3x3S2(_PacksAhead, nn.Conv2d):
     """nn.Conv2d(k = 3, stride 2, padding 1, bias=False) -- the conv that opens a down-sampling block
     (base_bev_backbone.py:36-41: ZeroPad2d(1) + Conv2d(padding=0), the same arithmetic) -- through the plane kernels."""
     MODE_F = 2
@@ -370,7 +298,7 @@ class Conv3x3S2(_PlaneConvMixin, nn.Conv2d):
         return _ConvPlanesFunction.apply(_plane_input(x), self.weight, pf, pd, 2)
 
 
-class UpConvT(_PlaneConvMixin, nn.ConvTranspose2d):
+class UpConvT(_PacksAhead, nn.ConvTranspose2d):
     """nn.ConvTranspose2d(k = stride in {1, 2}, bias=False) -- the deblocks (base_bev_backbone.py:55-62) -- through the
     plane kernels (k = 2: four 1-tap planes written with stride 2, no intermediate + pixel shuffle pass)."""
 
@@ -423,7 +351,6 @@ class _BranchConvsFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dys):
         an, ws = ctx.saved_tensors[0], ctx.saved_tensors[1:]
-        from ..spconv import functional as Fsp
         B, H, W, C = an.shape
         n, width = len(ws), ctx.width
         cps = [_pad32(w.shape[0]) for w in ws]
@@ -451,7 +378,7 @@ class _BranchConvsFunction(torch.autograd.Function):
                 ops.conv2d_3x3_nhwc(dyp[i], pd, width, out=blk)
             return da.permute(0, 3, 1, 2)
 
-        def wgrad(direct):
+        def wgrad(direct, jobs):
             pairs, num = _dense_pairs(B, H, W, an.device)
             a2 = an.reshape(-1, C)
             res = []
@@ -463,7 +390,7 @@ class _BranchConvsFunction(torch.autograd.Function):
                 if ops.conv2d_wgrad_splits(B, H, W, width, cps[i]) > 0:
                     xblk = an[..., width * i:width * (i + 1)]
                     if direct:
-                        ops.conv2d_wgrad(xblk, dyp[i], cout, out=ctx.w_params[i].grad, defer=Fsp._WGRAD_JOBS)
+                        ops.conv2d_wgrad(xblk, dyp[i], cout, out=ctx.w_params[i].grad, defer=jobs)
                         res.append(None)
                     else:
                         res.append(ops.conv2d_wgrad(xblk, dyp[i], cout).to(ws[i].dtype))
@@ -471,7 +398,7 @@ class _BranchConvsFunction(torch.autograd.Function):
                 xb = a2[:, width * i:width * (i + 1)]
                 if direct:
                     ops.wgrad(xb, width, dyp[i].reshape(-1, cps[i]), pairs, num, 9, out=ctx.w_params[i].grad,
-                              defer=Fsp._WGRAD_JOBS, conv2d_layout=True, cout_write=cout if cps[i] != cout else 0,
+                              defer=jobs, conv2d_layout=True, cout_write=cout if cps[i] != cout else 0,
                               x_block=True)
                     res.append(None)
                 else:
@@ -479,7 +406,7 @@ class _BranchConvsFunction(torch.autograd.Function):
                     res.append(dwk[:cout].permute(0, 2, 1).reshape(cout, width, 3, 3).to(ws[i].dtype))
             return res
 
-        def bsum(direct):
+        def bsum(direct, jobs):
             res = []
             for i in range(n):
                 if dys[i] is None or not (ctx.has_bias[i] and ctx.needs_input_grad[4 + 2 * i]):
@@ -495,8 +422,8 @@ class _BranchConvsFunction(torch.autograd.Function):
 
         wps = [ctx.w_params[i] for i in live if ctx.needs_input_grad[3 + 2 * i]]
         bps = [ctx.b_params[i] for i in live if ctx.has_bias[i] and ctx.needs_input_grad[4 + 2 * i]]
-        dx, dws, dbs = _scheduled_backward(ctx.needs_input_grad[0], want_w, want_b, wps, bps, True, dgrad, wgrad, bsum,
-                                           (an, pad))
+        dx, dws, dbs = Fsp.scheduled_backward(ctx.needs_input_grad[0], want_w, want_b, wps, bps, dgrad, wgrad, bsum,
+                                              [an, pad])
         grads = [dx, None, None]
         for i in range(n):
             grads.append(dws[i] if dws is not None else None)
@@ -513,7 +440,6 @@ class Conv3x3Packs:
     (load_state_dict, checkpoint restore, dist.broadcast, manual edits: all bump `weight._version`) are dropped."""
 
     def __init__(self, model):
-        import ctypes  # noqa: F401
         from .. import _lib as L
         self.convs, self.modes = [], []
         extra = []
@@ -577,7 +503,6 @@ class BatchNormReLU2d(nn.BatchNorm2d):
         """out (optional): a [B, C, H, W] channel block of a wider channels-last map; when the fused training path
         runs, y is written THERE (self.wrote_out = True) and the returned tensor is that view -- otherwise `out` is
         ignored and the caller concatenates as usual."""
-        from ..spconv import functional as Fsp
         self.wrote_out = False
         if ENABLED and x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 \
                 and x.is_contiguous(memory_format=torch.channels_last):

@@ -180,8 +180,8 @@ class SparseConvolution(SparseModule):
                     and tuple(self.kernel_size) == (3, 3, 3)
                 # ... and so are the layers whose weight gradient runs over the window kernel's tiles
                 if not lazy and self.window_capable() and x.indice_dict.get("__row_order__", ops.ROWS_ZYX) == ops.ROWS_YXZ:
-                    from .functional import _window_wgrad
-                    lazy = _window_wgrad(self.out_channels)
+                    from .functional import window_wgrad
+                    lazy = window_wgrad(self.out_channels)
                 # z-fastest rows with a column map: the window plan comes out of the same pass as the rulebook; a caller that
                 # knows ALL consumers of this rulebook (the backbones' prefetcher: indice_dict["__subm_hint__"] = (width,
                 # tables needed)) can drop the neighbour table altogether -- alone, a layer keeps it for the others

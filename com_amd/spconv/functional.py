@@ -1,5 +1,7 @@
 """autograd.Function wrappers over the HIP kernels (binder convention of the reference's own ops:
 pcdet/ops/pointnet2/pointnet2_stack/pointnet2_utils.py:8-50)."""
+import contextlib
+
 import torch
 from torch.autograd import Function
 
@@ -26,7 +28,7 @@ USE_DGRAD_CLASSES = True      # strided-conv data gradient over parity-class row
 # BatchNorm output) and is only used when the consumer sees exactly that tensor.
 FUSE_BN_REDUCTIONS = True
 _SIDE = {}
-_PENDING = []   # [(event, tensors kept alive)] of weight-gradient launches not yet joined
+_PENDING = []   # [(event, [tensors kept alive])] of weight-gradient launches not yet joined
 
 
 _COLSUM_JOBS = []   # [(partial, rows, bias.grad)] of deferred bias gradients: one launch at the join
@@ -67,7 +69,7 @@ def join_deferred_wgrad():
     _STAMP_SEQ[0] = 0
     _SP_SEQ[0] = 0
     if _COLSUM_JOBS or _WGRAD_JOBS:
-        side = _side_stream((_COLSUM_JOBS or _WGRAD_JOBS)[0][0].device)
+        side = side_stream((_COLSUM_JOBS or _WGRAD_JOBS)[0][0].device)
         with torch.cuda.stream(side):
             if _WGRAD_JOBS:
                 ops.wgrad_reduce_batched(_WGRAD_JOBS)
@@ -88,19 +90,109 @@ def join_deferred_wgrad():
         _PENDING.clear()
 
 
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-def _side_stream(device, role="wgrad"):
+def side_stream(device, role="wgrad"):
+    """The process-wide second stream of `device` for `role`: "wgrad" (the backward schedule below) or a name of the
+    caller's own (the backbones' rulebook and pack streams)."""
     key = (device.type, device.index) if role == "wgrad" else (device.type, device.index, role)
     if key not in _SIDE:
         _SIDE[key] = torch.cuda.Stream(device=device)
     return _SIDE[key]
+
+
+def _as_list(p):
+    return list(p) if isinstance(p, (list, tuple)) else [p]
+
+
+def _direct_ok(params):
+    """DIRECT_GRAD and every parameter (one or a list: all or none) owns a contiguous fp32 `.grad` to write into."""
+    ps = _as_list(params)
+    return bool(DIRECT_GRAD) and len(ps) > 0 and all(
+        p is not None and p.grad is not None and p.grad.dtype == torch.float32 and p.grad.is_contiguous() for p in ps)
+
+
+def scheduled_backward(need_dx, want_w, want_b, wp, bp, dgrad, wgrad, bsum, keep, *, direct_without_deferral=False,
+                       flush=False, sparse_stamps=False):
+    """WHEN and WHERE a conv's backward issues its work -- the one schedule of the sparse convs (SparseConvFunction) and the
+    dense ones (hotpath.conv2d_fast); WHAT is launched is the callers' business:
+
+      dgrad() -> dx                 on the current stream, FIRST
+      wgrad(direct, jobs) -> dw     on the side stream, from an event recorded BEFORE dgrad()
+      bsum(direct, jobs) -> db      behind it on the side stream
+
+    The data gradient is issued first and the side branch forks from an event recorded before it: in a captured graph the
+    first successor of a node stays on its hardware queue, and the main chain (BatchNorm backward -> dgrad -> BatchNorm
+    backward ...) should be the one that never changes queues -- a cross-queue dependency costs several microseconds, a
+    same-queue one ~1.5 (profiles/README.md has what the other order cost).  Neither kernel fills the chip at B = 4, which
+    is why they overlap at all.  Without OVERLAP_WGRAD, or when no dx is wanted, everything runs on the current stream.
+
+    wp / bp: the parameter (or list of parameters, all or none) behind dw / db.  `direct`: write into its `.grad` and return
+    None (DIRECT_GRAD and a contiguous fp32 `.grad`; the parameter is then claimed: one contribution per step).  The
+    launch is DEFERRED when WGRAD_JOIN_LAG > 0, a side stream is in use and everything wanted is direct: `jobs` is then the
+    list that takes the slab reductions (wgrad) / column-sum finalisations (bsum), run in ONE launch each by
+    join_deferred_wgrad(), and the current stream waits for this layer's side work only WGRAD_JOIN_LAG layers later;
+    otherwise `jobs` is None and the join is eager.  `keep`: tensors the side kernels read, kept alive until that join; a
+    callback may append to it.
+
+    The two callers differ in two recorded ways, kept as they measured:
+      direct_without_deferral  sparse: direct whenever `.grad` is usable (deferred or not); dense (False): only when
+                               the launch is also deferred
+      flush                    sparse: once WGRAD_FLUSH_BYTES of slabs have piled up they are reduced on the side stream
+                               right behind this layer; dense (False): never
+    sparse_stamps: the diagnostics stamps are dg<n>e / wg<n>s under ops.STAMPS["sparse"] instead of d2w<n>."""
+    dx = dw = db = None
+    cur = torch.cuda.current_stream()
+    side = ready = None
+    if OVERLAP_WGRAD and need_dx and (want_w or want_b):
+        ready = torch.cuda.Event()
+        ready.record(cur)
+    if need_dx:
+        dx = dgrad()
+    if ready is not None:
+        side = side_stream(keep[0].device)
+        side.wait_event(ready)                   # dy is complete (recorded BEFORE the dgrad was issued)
+    direct_w, direct_b = want_w and _direct_ok(wp), want_b and _direct_ok(bp)
+    deferred = WGRAD_JOIN_LAG > 0 and side is not None and (direct_w or not want_w) and (direct_b or not want_b)
+    if not (deferred or direct_without_deferral):
+        direct_w = direct_b = False
+    for p in (_as_list(wp) if direct_w else []):
+        _claim_direct(p, "w")
+    for p in (_as_list(bp) if direct_b else []):
+        _claim_direct(p, "b")
+    sp = sparse_stamps and ops.STAMPS is not None and ops.STAMPS.get("sparse")
+    if sp:
+        _SP_SEQ[0] += 1
+        ops.stamp(f"dg{_SP_SEQ[0]}e")            # main stream: the data gradient of layer (backward order) is behind us
+    with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+        if sp:
+            ops.stamp(f"wg{_SP_SEQ[0]}s")        # side stream: its weight gradient starts
+        elif not sparse_stamps and ops.STAMPS is not None:
+            _STAMP_SEQ[0] += 1
+            ops.stamp(f"d2w{_STAMP_SEQ[0]}")
+        if want_w:
+            dw = wgrad(direct_w, _WGRAD_JOBS if (direct_w and deferred) else None)
+        if want_b:
+            db = bsum(direct_b, _COLSUM_JOBS if (direct_b and deferred) else None)
+        if flush and deferred and WGRAD_FLUSH_BYTES > 0 \
+                and sum(j.workspace.numel() for j in _WGRAD_JOBS) >= WGRAD_FLUSH_BYTES:
+            # the slabs collected so far are summed NOW, on this (side) stream, in the middle of the backward pass: one
+            # reduction of every layer at the very end read ~170 MB of 128-channel tiles on the step's critical tail
+            ops.wgrad_reduce_batched(_WGRAD_JOBS)
+            _WGRAD_KEEP.extend(_WGRAD_JOBS)      # (buffers stay referenced until the step's join)
+            del _WGRAD_JOBS[:]
+        if deferred:
+            ev = torch.cuda.Event()
+            ev.record(side)
+    if deferred:
+        _PENDING.append((ev, keep))              # inputs stay alive until the lagged join
+        if len(_PENDING) > WGRAD_JOIN_LAG:
+            cur.wait_event(_PENDING[-1 - WGRAD_JOIN_LAG][0])
+            del _PENDING[:len(_PENDING) - WGRAD_JOIN_LAG]
+    elif side is not None:
+        cur.wait_stream(side)                    # join: dW / dbias are consumed on the current stream
+        for t in _as_list(dw) + _as_list(db):
+            if t is not None:
+                t.record_stream(cur)
+    return dx, dw, db
 
 
 def _to_bf16_padded(x, c_pad):
@@ -112,7 +204,7 @@ def _to_bf16_padded(x, c_pad):
     return x.contiguous()
 
 
-def _window_wgrad(c):
+def window_wgrad(c):
     """The "subm_window_wgrad" option admits the window weight gradient for c channels (bit 0 = 64, bit 1 = 32, bit 2 = 16)."""
     from .. import _lib as L
     return bool(L.get_option("subm_window_wgrad") & {64: 1, 32: 2, 16: 4}.get(int(c), 0))
@@ -193,22 +285,12 @@ class SparseConvFunction(Function):
         if dy is None:                               # only the identity branch received a gradient
             return (d_ident, None, None, None, None, None, None, None, None, None)
         dy16 = _to_bf16_padded(dy, ctx.cout)
-        dx = dw = db = None
-        # dgrad and wgrad only share their inputs: at B = 4 neither fills the chip (1-4 waves per SIMD), so the
-        # weight gradient (+ bias column sum) runs on a second HIP stream concurrently with the data gradient
-        # and is joined before returning (fork/join is captured as such in hipGraph mode).
-        side = None
-        cur = torch.cuda.current_stream()
-        # The data gradient is issued FIRST and the weight gradient forks from an event recorded before it: in a
-        # captured graph the first successor of a node stays on its hardware queue, and the main chain
-        # (BatchNorm backward -> dgrad -> BatchNorm backward ...) should be the one that never changes queues --
-        # a cross-queue dependency costs several microseconds, a same-queue one ~1.5.
-        ready = None
-        if OVERLAP_WGRAD and ctx.needs_input_grad[0] and (ctx.needs_input_grad[1] or
-                                                         (ctx.has_bias and ctx.needs_input_grad[2])):
-            ready = torch.cuda.Event()
-            ready.record(cur)
-        if ctx.needs_input_grad[0]:
+        need_dx, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        weight_p, bias_p = ctx.weight_param, ctx.bias_param
+        keep = [x, dy16]                             # what the side-stream kernels read (scheduled_backward)
+
+        def dgrad():
             if ctx.cin_pad % 16 != 0:
                 raise RuntimeError("dgrad needs >= 16 input channels (the 5-channel input layer never "
                                    "requires an input gradient)")
@@ -245,74 +327,36 @@ class SparseConvFunction(Function):
             dx = dxp if ctx.cin_pad == ctx.in_cols else dxp[:, :ctx.in_cols].contiguous()
             if d_ident is not None and add is None:
                 dx = dx + d_ident.to(dx.dtype)
-        want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
-        if OVERLAP_WGRAD and want_w and ctx.needs_input_grad[0]:
-            side = _side_stream(dy16.device)
-            side.wait_event(ready)                   # dy16 is complete (recorded BEFORE the dgrad was issued)
-        bias_p = ctx.bias_param
-        weight_p = ctx.weight_param
-        direct_w = DIRECT_GRAD and weight_p is not None and weight_p.grad is not None \
-            and weight_p.grad.dtype == torch.float32 and weight_p.grad.is_contiguous()
-        direct_b = DIRECT_GRAD and bias_p is not None and bias_p.grad is not None \
-            and bias_p.grad.dtype == torch.float32 and bias_p.grad.is_contiguous()
-        if direct_w and ctx.needs_input_grad[1]:
-            _claim_direct(weight_p, "w")
-        if direct_b and ctx.has_bias and ctx.needs_input_grad[2]:
-            _claim_direct(bias_p, "b")
-        keep_partial = None
-        deferred = (WGRAD_JOIN_LAG > 0 and side is not None and (direct_w or not ctx.needs_input_grad[1])
-                    and (direct_b or not (ctx.has_bias and ctx.needs_input_grad[2])))
-        if ops.STAMPS is not None and ops.STAMPS.get("sparse"):
-            _SP_SEQ[0] += 1
-            ops.stamp(f"dg{_SP_SEQ[0]}e")                 # main stream: the data gradient of layer (backward order) is behind us
-        with torch.cuda.stream(side) if side is not None else _NullCtx():
-            if ops.STAMPS is not None and ops.STAMPS.get("sparse"):
-                ops.stamp(f"wg{_SP_SEQ[0]}s")             # side stream: its weight gradient starts
-            if ctx.needs_input_grad[1]:
-                if ctx.window and rb.subm and ctx.cin <= ctx.cout == x.shape[1] and _window_wgrad(ctx.cout):
-                    dwk = ops.subm_window_wgrad(x, dy16, rb, out=weight_p.grad if direct_w else None,
-                                                defer=_WGRAD_JOBS if (deferred and direct_w) else None, cin=ctx.cin)
-                else:
-                    dwk = ops.wgrad(x, ctx.cin, dy16, None, None, rb.kvol,
-                                    out=weight_p.grad if direct_w else None,                 # [Cout, K, Cin] f32
-                                    defer=_WGRAD_JOBS if (deferred and direct_w) else None, rb=rb)
-                dw = None if direct_w else dwk.view(weight.shape).to(weight.dtype)
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                cl = ctx.colsum_link.result if ctx.colsum_link is not None else None
-                if cl is not None and cl[0].data_ptr() == dy16.data_ptr() and cl[0].shape == dy16.shape:
-                    # the BatchNorm backward that produced dy already summed its columns per workgroup
-                    if deferred and direct_b:
-                        _COLSUM_JOBS.append((cl[1], cl[2], bias_p.grad))     # finished in join_deferred_wgrad()
-                        db = bias_p.grad
-                    else:
-                        db = ops.col_sum_finalize(cl[1], cl[2], out=bias_p.grad if direct_b else None)
-                    keep_partial = cl[1]
-                else:
-                    db = ops.col_sum(dy16, n_dev=rb.n_out_dev, out=bias_p.grad if direct_b else None)
-                if ctx.colsum_link is not None:
-                    ctx.colsum_link.result = None
-                if direct_b:
+            return dx
+
+        def wgrad(direct, jobs):
+            out = weight_p.grad if direct else None                                          # [Cout, K, Cin] f32
+            if ctx.window and rb.subm and ctx.cin <= ctx.cout == x.shape[1] and window_wgrad(ctx.cout):
+                dwk = ops.subm_window_wgrad(x, dy16, rb, out=out, defer=jobs, cin=ctx.cin)
+            else:
+                dwk = ops.wgrad(x, ctx.cin, dy16, None, None, rb.kvol, out=out, defer=jobs, rb=rb)
+            return None if direct else dwk.view(weight.shape).to(weight.dtype)
+
+        def bsum(direct, jobs):
+            out = bias_p.grad if direct else None
+            cl = ctx.colsum_link.result if ctx.colsum_link is not None else None
+            if cl is not None and cl[0].data_ptr() == dy16.data_ptr() and cl[0].shape == dy16.shape:
+                # the BatchNorm backward that produced dy already summed its columns per workgroup
+                if jobs is not None:
+                    jobs.append((cl[1], cl[2], out))             # finished in join_deferred_wgrad()
                     db = None
-            if deferred and WGRAD_FLUSH_BYTES > 0 and sum(j.workspace.numel() for j in _WGRAD_JOBS) >= WGRAD_FLUSH_BYTES:
-                # the slabs collected so far are summed NOW, on this (side) stream, in the middle of the backward pass: one
-                # reduction of every layer at the very end read ~170 MB of 128-channel tiles on the step's critical tail
-                ops.wgrad_reduce_batched(_WGRAD_JOBS)
-                _WGRAD_KEEP.extend(_WGRAD_JOBS)          # (buffers stay referenced until the step's join)
-                del _WGRAD_JOBS[:]
-            if deferred:
-                ev = torch.cuda.Event()
-                ev.record(side)
-        if deferred:
-            _PENDING.append((ev, x, dy16, keep_partial))   # inputs stay alive until the lagged join below
-            side = None
-        if deferred and len(_PENDING) > WGRAD_JOIN_LAG:
-            cur.wait_event(_PENDING[-1 - WGRAD_JOIN_LAG][0])
-            del _PENDING[:len(_PENDING) - WGRAD_JOIN_LAG]
-        if side is not None:
-            cur.wait_stream(side)                    # join: dW / dbias are consumed on the current stream
-            for t in (dw, db):
-                if t is not None:
-                    t.record_stream(cur)
+                else:
+                    db = ops.col_sum_finalize(cl[1], cl[2], out=out)
+                keep.append(cl[1])                   # the partial it consumed lives until the join
+            else:
+                db = ops.col_sum(dy16, n_dev=rb.n_out_dev, out=out)
+            if ctx.colsum_link is not None:
+                ctx.colsum_link.result = None
+            return None if direct else db
+
+        # the sparse convs write into .grad whenever it is usable, deferred or not, and flush piled-up slab reductions
+        dx, dw, db = scheduled_backward(need_dx, want_w, want_b, weight_p, bias_p, dgrad, wgrad, bsum, keep,
+                                        direct_without_deferral=True, flush=True, sparse_stamps=True)
         if dx is None and d_ident is not None:
             dx = d_ident
         return dx, dw, db, None, None, None, None, None, None, None
