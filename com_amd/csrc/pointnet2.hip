@@ -427,7 +427,7 @@ struct FpsWaveBest {
 // barrier 16 lanes of every wave reduce the 16 wave results (double-buffered by the parity of the sample).
 __global__ __launch_bounds__(1024) void fps_bucket_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ xyz_cnt,
                                                           int32_t *__restrict__ idxs, const int32_t *__restrict__ num_sampled,
-                                                          FpsBucketWs W, int dbg) {
+                                                          FpsBucketWs W) {
     extern __shared__ __attribute__((aligned(16))) char fpsb_lds[];
     float4 *bmin = (float4 *)fpsb_lds;                                 // (mnx, mny, mnz, maxd)
     float4 *bmax = bmin + FPS_NB;                                      // (mxx, mxy, mxz, tie word of the farthest point)
@@ -508,7 +508,7 @@ __global__ __launch_bounds__(1024) void fps_bucket_kernel(const float *__restric
                     pk[i][u] = 0;
                     if (u < nu && qs[i] >= 0) {                 // (wave-uniform: no instruction for pieces the bucket does not have)
                         const int p = lane + 64 * u;
-                        if (p < cn && !(dbg & 1)) {
+                        if (p < cn) {
                             pp[i][u] = sp[s0 + p];
                             pk[i][u] = sk[s0 + p];
                         }
@@ -528,7 +528,7 @@ __global__ __launch_bounds__(1024) void fps_bucket_kernel(const float *__restric
                         const float px = pp[i][u].x, py = pp[i][u].y, pz = pp[i][u].z;
                         const float d = (px - x1) * (px - x1) + (py - y1) * (py - y1) + (pz - z1) * (pz - z1);
                         const float d2 = fminf(d, pp[i][u].w);
-                        if (d2 != pp[i][u].w && !(dbg & 2)) sp[s0 + p].w = d2;
+                        if (d2 != pp[i][u].w) sp[s0 + p].w = d2;
                         const unsigned t = fps_tie(pk[i][u]);
                         if (d2 > bd || (d2 == bd && t > bt)) {
                             bd = d2; bt = t; bxv = px; byv = py; bzv = pz;
@@ -537,7 +537,7 @@ __global__ __launch_bounds__(1024) void fps_bucket_kernel(const float *__restric
                 }
                 float dmax;
                 unsigned tmax;
-                if (!(dbg & 4) && fps_wave_best(bd, bt, dmax, tmax)) {          // the one lane that holds the bucket's farthest point
+                if (fps_wave_best(bd, bt, dmax, tmax)) {          // the one lane that holds the bucket's farthest point
                     bmin[slot(q)].w = dmax;
                     bmax[slot(q)].w = __uint_as_float(tmax);
                     bpt[slot(q)] = make_float4(bxv, byv, bzv, 0.0f);
@@ -1002,8 +1002,7 @@ extern "C" int pcd_stack_farthest_point_sampling_buckets(int B, const float *xyz
         hipFuncSetAttribute((const void *)fps_bucket_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FPS_LDS_BYTES) != hipSuccess)
         return PCD_ERR_LAUNCH;
     fps_bin_kernel<<<B, 1024, bin_lds, st>>>(xyz, xyz_batch_cnt, W);
-    const int dbg = pcd_opt(PCD_OPT_FPS_G) >= 1000 ? pcd_opt(PCD_OPT_FPS_G) - 1000 : 0;     // (ablation bits of tools/exp_fps.py; 0 in production)
-    fps_bucket_kernel<<<B, 1024, FPS_LDS_BYTES, st>>>(xyz, xyz_batch_cnt, idxs, num_sampled_points, W, dbg);
+    fps_bucket_kernel<<<B, 1024, FPS_LDS_BYTES, st>>>(xyz, xyz_batch_cnt, idxs, num_sampled_points, W);
     PN2_CHECK_LAUNCH();
 }
 

@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256 * WN, gg_waves(NB / WN, MI, G)) void gather_gem
     const unsigned short *__restrict__ x, int c_in, int cshift, const uint4 *__restrict__ wp,
     const float *__restrict__ bias, const int32_t *__restrict__ nbr, int nbr_stride, int K, int flip,
     int n_out_cap, const int32_t *__restrict__ n_out_dev, void *__restrict__ yv, int nsteps,
-    unsigned x_bytes, int dbg, const void *__restrict__ addend, BnRed bn) {
+    unsigned x_bytes, const void *__restrict__ addend, BnRed bn) {
     __builtin_amdgcn_s_setprio(PCD_MAIN_PRIO);   // main-chain kernel: issue ahead of the weight-gradient waves sharing the SIMD
     constexpr int ROWS = 4 * MI * 16;
     constexpr int THREADS = 256 * WN;
@@ -494,8 +494,7 @@ __global__ __launch_bounds__(256 * WN, gg_waves(NB / WN, MI, G)) void gather_gem
             valid[gg] = false;
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
-                int i = nbr_s[k * ROWS + tile_row + mi * 16];
-                if (dbg & 1) i = (i >= 0) ? (tile_row & 63) : i;  // ablation: gathers hit a few hot rows
+                const int i = nbr_s[k * ROWS + tile_row + mi * 16];
                 a[gg][mi] = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, ((unsigned)i << row_shift) + c0b, 0, 0);
                 valid[gg] |= (i >= 0);
             }
@@ -510,7 +509,7 @@ __global__ __launch_bounds__(256 * WN, gg_waves(NB / WN, MI, G)) void gather_gem
                     bool(&vn)[G]) {
         constexpr bool FIRST = decltype(first_tag)::value, LAST = decltype(last_tag)::value;
         const int s0 = grp * G;
-        if (STAGED && FIRST && !(dbg & 2)) {
+        if (STAGED && FIRST) {
             const unsigned base = (unsigned)(s0 / (STAGED ? SG : 1) + 1) * VEC;  // next stage (OOB -> zeros)
 #pragma unroll
             for (int j = 0; j < WPT; ++j)
@@ -522,7 +521,7 @@ __global__ __launch_bounds__(256 * WN, gg_waves(NB / WN, MI, G)) void gather_gem
                                    : wbuf + (size_t)s0 * NB * 64;
 #pragma unroll
         for (int gg = 0; gg < G; ++gg) {
-            if (__any(vc[gg]) && !(dbg & 4)) {
+            if (__any(vc[gg])) {
 #pragma unroll
                 for (int nb = 0; nb < NBW; ++nb) {
                     bf16x8 b = as_bf16x8(wcur[(gg * NB + wn * NBW + nb) * 64 + lane]);
@@ -546,7 +545,7 @@ __global__ __launch_bounds__(256 * WN, gg_waves(NB / WN, MI, G)) void gather_gem
 
     gather_group(0, a0, v0);
     const int ngroups = (nsteps + G - 1) / G;
-    const int npairs = (dbg & 8) ? 0 : (ngroups + 1) / 2;  // groups are processed in ping-pong pairs
+    const int npairs = (ngroups + 1) / 2;  // groups are processed in ping-pong pairs
     for (int pr = 0; pr < npairs; ++pr) {
         if (GPS == 2) {  // one stage = this pair
             body(2 * pr, T_{}, F_{}, a0, v0, a1, v1);
@@ -585,7 +584,6 @@ static int launch_gg(const void *x, int c_in, int cshift, const void *wp, const 
     size_t wbytes = SG > 0 ? (size_t)2 * SG * NB * 64 * sizeof(uint4) : (size_t)nsteps * NB * 64 * sizeof(uint4);
     size_t lds = wbytes + (size_t)(K + 1) * ROWS * sizeof(int) + (bn.mode ? (size_t)8 * NB * 16 * sizeof(float) : 0);
     if (lds > 160 * 1024) return PCD_ERR_UNSUPPORTED;
-    const int dbg = pcd_opt(PCD_OPT_GG_DBG);   // ablation switches (0 in production)
     auto kb = gather_gemm_kernel<NB, MI, G, SG, true, WN>;
     auto kf = gather_gemm_kernel<NB, MI, G, SG, false, WN>;
     if (lds > 64 * 1024) {
@@ -602,10 +600,10 @@ static int launch_gg(const void *x, int c_in, int cshift, const void *wp, const 
     }
     if (y_dtype == PCD_BF16)
         kb<<<grid, 256 * WN, lds, st>>>((const unsigned short *)x, c_in, cshift, (const uint4 *)wp, bias, nbr,
-                                   nbr_stride, K, flip, n_out, n_out_dev, y, nsteps, x_bytes, dbg, addend, bn);
+                                   nbr_stride, K, flip, n_out, n_out_dev, y, nsteps, x_bytes, addend, bn);
     else
         kf<<<grid, 256 * WN, lds, st>>>((const unsigned short *)x, c_in, cshift, (const uint4 *)wp, bias, nbr,
-                                   nbr_stride, K, flip, n_out, n_out_dev, y, nsteps, x_bytes, dbg, addend, bn);
+                                   nbr_stride, K, flip, n_out, n_out_dev, y, nsteps, x_bytes, addend, bn);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }
@@ -646,7 +644,7 @@ __global__ __launch_bounds__(256 * (1 + CW), 1) void ggw_kernel(
     const unsigned short *__restrict__ x, const uint4 *__restrict__ wp, const float *__restrict__ bias,
     const int32_t *__restrict__ nbr, int nbr_stride, int K, int flip, int n_out_cap,
     const int32_t *__restrict__ n_out_dev, void *__restrict__ yv, unsigned x_bytes, unsigned w_bytes,
-    const void *__restrict__ addend, BnRed bn, int dbg) {
+    const void *__restrict__ addend, BnRed bn) {
     __builtin_amdgcn_s_setprio(PCD_MAIN_PRIO);   // main-chain kernel: issue ahead of the weight-gradient waves sharing the SIMD
     // 8 waves: waves 0-3 are CONSUMERS (MI x 16 output rows each: LDS operand reads + MFMAs, nothing else), waves
     // 4-7 are LOADERS (wave 4 + w feeds consumer w: neighbour indices -> DMA offsets, all LDS-DMA instructions).
@@ -702,7 +700,7 @@ __global__ __launch_bounds__(256 * (1 + CW), 1) void ggw_kernel(
                 const int row = r0wg + r;
                 const int krow = flip ? (K - 1 - k) : k;
                 const bool ok = idx < total && row < n_out;
-                const unsigned off = (ok && !(dbg & 16)) ? ((unsigned)krow * (unsigned)nbr_stride + (unsigned)row) * 4u : 0xFFFFFFF0u;
+                const unsigned off = ok ? ((unsigned)krow * (unsigned)nbr_stride + (unsigned)row) * 4u : 0xFFFFFFF0u;
                 v[u] = __builtin_amdgcn_raw_buffer_load_b32(nrsrc, off, 0, 0);
                 if (!ok) v[u] = -1;
             }
@@ -719,7 +717,7 @@ __global__ __launch_bounds__(256 * (1 + CW), 1) void ggw_kernel(
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void *)wp, 0, (int)w_bytes, 0x00020000);
     char *const awave = aring + wave * (R * A_STAGE);
     const int wrow0 = wave * (MI * 16);
-    const int T = (dbg & 8) ? 0 : K * SOFF;                // stages (ablation 8: prologue + epilogue only)
+    const int T = K * SOFF;                                // stages
     const int NIT = (T + R - 1) / R * R;                   // iterations (both roles run the same number of barriers)
 
     using S0 = std::integral_constant<int, 0>;
@@ -735,13 +733,12 @@ __global__ __launch_bounds__(256 * (1 + CW), 1) void ggw_kernel(
     if (loader) {
         // ------------------------------------------------------------------------------------------- loader
         // the loader's few instructions go ahead of the consumer's MFMA stream on the shared SIMD
-        if (!(dbg & 64)) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
         const int gl_row = lane >> 3;                      // row slot of DMA instruction j: 8 j + (lane >> 3)
         // source piece = (l & 7) ^ ((row_slot >> 1) & 7) = (l & 7) ^ ((4 j + (l >> 4)) & 7)
         const unsigned gl_p0 = (unsigned)(lane & 7), gl_p1 = (unsigned)(lane >> 4);
         auto fire = [&](int stage, auto slot_tag) {
             constexpr int SLOT = decltype(slot_tag)::value;
-            if (dbg & 32) return;                              // ablation: no DMA instructions at all
             const unsigned h = SOFF == 2 ? (unsigned)(stage & 1) * 128u : 0u;
             const int *irow = nbr_s + stage_k(stage) * ROWS + wrow0 + gl_row;
             int idx[GI];
@@ -750,14 +747,13 @@ __global__ __launch_bounds__(256 * (1 + CW), 1) void ggw_kernel(
 #pragma unroll
             for (int j = 0; j < GI; ++j) {
                 const unsigned piece = gl_p0 ^ ((4u * j + gl_p1) & 7u);
-                unsigned off = (unsigned)idx[j] * (unsigned)ROWB + h + piece * 16u;   // idx = -1 -> beyond num_records
-                if (dbg & 1) off = 0xFFFFFF00u;                                     // ablation: no gather traffic
+                const unsigned off = (unsigned)idx[j] * (unsigned)ROWB + h + piece * 16u;   // idx = -1 -> beyond num_records
                 glds16(xrsrc, awave + SLOT * A_STAGE + j * 1024, off);
             }
 #pragma unroll
             for (int f = 0; f < WPW; ++f) {
                 const int frag = wave + 4 * f;
-                const unsigned off = (stage < T && !(dbg & 2))
+                const unsigned off = stage < T
                                          ? (unsigned)stage * (unsigned)W_STAGE + (unsigned)lane * 16u + (unsigned)frag * 1024u
                                          : 0xFFFFFFF0u;
                 glds16(wrsrc, wring + SLOT * W_STAGE + frag * 1024, off);
@@ -815,7 +811,7 @@ __global__ __launch_bounds__(256 * (1 + CW), 1) void ggw_kernel(
     };
     auto compute = [&](auto slot_tag, bool valid) {
         constexpr int SLOT = decltype(slot_tag)::value;
-        if (!valid || (dbg & 4)) return;
+        if (!valid) return;
         const char *ab = awave + SLOT * A_STAGE;
         const char *wb = wring + SLOT * W_STAGE;
         // all operand fragments of the stage (2 contraction steps) are requested up front, then consumed in order:
@@ -888,7 +884,6 @@ static int launch_ggw(const void *x, const void *wp, const float *bias, const in
     const size_t lds = (size_t)R * (2 * NB * 1024) + (size_t)4 * R * (MI * 2048) + (size_t)(K + 1) * ROWS * sizeof(int) +
                        (bn.mode ? (size_t)8 * NB * 16 * sizeof(float) : 0);
     if (lds > 160 * 1024) return PCD_ERR_UNSUPPORTED;
-    const int dbg = pcd_opt(PCD_OPT_GGW_DBG);   // ablation switches (0 in production)
     auto kb = ggw_kernel<NB, SOFF, MI, R, true, CW>;
     auto kf = ggw_kernel<NB, SOFF, MI, R, false, CW>;
     if (lds > 64 * 1024) {
@@ -903,10 +898,10 @@ static int launch_ggw(const void *x, const void *wp, const float *bias, const in
     }
     if (y_dtype == PCD_BF16)
         kb<<<grid, 256 * (1 + CW), lds, st>>>((const unsigned short *)x, (const uint4 *)wp, bias, nbr, nbr_stride, K, flip, n_out,
-                                              n_out_dev, y, x_bytes, w_bytes, addend, bn, dbg);
+                                              n_out_dev, y, x_bytes, w_bytes, addend, bn);
     else
         kf<<<grid, 256 * (1 + CW), lds, st>>>((const unsigned short *)x, (const uint4 *)wp, bias, nbr, nbr_stride, K, flip, n_out,
-                                              n_out_dev, y, x_bytes, w_bytes, addend, bn, dbg);
+                                              n_out_dev, y, x_bytes, w_bytes, addend, bn);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }
@@ -942,26 +937,16 @@ __global__ __launch_bounds__(256, gg_waves(NB, MI, 1)) void gather_gemm_cls_kern
     // neighbourhood) in one L2.  The BatchNorm partial row of a workgroup is its block index (any bijection onto the grid works).
     const int tile = blockIdx.x;
     int v0 = -1, cls_v = 0;
-    if (compact & 2) {                                     // (ablation, option "gg_dbg" bit 8: contiguous runs of tiles per XCD)
-        const int t = xcd_tile(vstart[T.ncls], ROWS);
-        if (t * ROWS < vstart[T.ncls]) {
-            v0 = t * ROWS;
-            for (int q = 1; q < T.ncls; ++q)
-                if (vstart[q] <= v0) cls_v = q;
+    const int xcd = blockIdx.x & 7;
+    for (int q = 0, left = blockIdx.x >> 3; q < T.ncls; ++q) {
+        const int t0 = vstart[q] / ROWS, tc = vstart[q + 1] / ROWS - t0;     // (class starts are multiples of the class tile >= ROWS)
+        const int lo = (xcd * tc) >> 3, hi = ((xcd + 1) * tc) >> 3;
+        if (left < hi - lo) {
+            v0 = (t0 + lo + left) * ROWS;
+            cls_v = q;
+            break;
         }
-    } else {
-        const int xcd = blockIdx.x & 7;
-        int j = blockIdx.x >> 3;
-        for (int q = 0; q < T.ncls; ++q) {
-            const int t0 = vstart[q] / ROWS, tc = vstart[q + 1] / ROWS - t0;     // (class starts are multiples of the class tile >= ROWS)
-            const int lo = (xcd * tc) >> 3, hi = ((xcd + 1) * tc) >> 3;
-            if (j < hi - lo) {
-                v0 = (t0 + lo + j) * ROWS;
-                cls_v = q;
-                break;
-            }
-            j -= hi - lo;
-        }
+        left -= hi - lo;
     }
     if (v0 < 0) {
         if (bn.mode) bnred_zero_row(bn, tile, c_out);
@@ -994,7 +979,7 @@ __global__ __launch_bounds__(256, gg_waves(NB, MI, 1)) void gather_gemm_cls_kern
         const int j = e / ROWS, r = e - j * ROWS;
         const int i = row_s[r];
         // (compact: the class-compact table nbr_cls [8][nbr_stride], indexed by permutation slot -- coalesced, no gather)
-        nbr_s[e] = (j < nk && i >= 0) ? ((compact & 1) ? nbr[(size_t)j * nbr_stride + v0 + r] : nbr[(size_t)kk_s[j] * nbr_stride + i]) : -1;
+        nbr_s[e] = (j < nk && i >= 0) ? (compact ? nbr[(size_t)j * nbr_stride + v0 + r] : nbr[(size_t)kk_s[j] * nbr_stride + i]) : -1;
     }
     u32x4 wreg[WPT];
     auto load_w = [&](int s) {
@@ -1937,7 +1922,7 @@ static int gg_dispatch(const void *x, int n_rows_in, int c_in, const void *packe
         const unsigned w_bytes = (unsigned)wbytes;
         int mi = n_rows_out <= 256 * 192 * 5 / 4 ? 3 : 2;   /* (capacities are 1.25 x the row counts) */
         // Few rows (one round of 128-row tiles fits the chip): the FORWARD conv takes 128-row tiles -- 36-38 us isolated against
-        // 42-44 at 21-32 k rows (tools/exp_ggw.py) and nothing runs beside levels 3-4 of the forward pass; the data gradient
+        // 42-44 at 21-32 k rows and nothing runs beside levels 3-4 of the forward pass; the data gradient
         // keeps 192 rows: its workgroups leave ~45 % of the CUs to the weight-gradient kernel running beside it, and with
         // 128-row tiles everywhere the training step was 7 % SLOWER (3.35 against 3.12 ms).
         if (mi == 3 && !is_dgrad && n_rows_out <= 256 * 128 * 5 / 4) mi = 2;
@@ -2047,9 +2032,8 @@ extern "C" int pcd_sparse_conv_dgrad_classes_v2(const void *dy, int n_dy_rows, i
     // flight) hide its prologue better than the generic kernel's row-count rule
     const int mi = cls_mi(n_rows_in);
     int *tiles_only = nullptr;
-    const int compact = (nbr_compact ? 1 : 0) | ((pcd_opt(PCD_OPT_GG_DBG) & 256) ? 2 : 0);
-#define CLS_ARGS dy, c_dy, cshift, packed_w, nbr_in, nbr_stride, K, perm, vstart_dev, T, vcap, dx, dx_dtype, nsteps, x_bytes, st, addend, bn_reduce, tiles_only, compact
-#define CLS_MI(NBV) (mi == 4 ? launch_gg_cls<NBV, 4>(CLS_ARGS) : mi == 2 ? launch_gg_cls<NBV, 2>(CLS_ARGS) : launch_gg_cls<NBV, 1>(CLS_ARGS))
+#define CLS_ARGS dy, c_dy, cshift, packed_w, nbr_in, nbr_stride, K, perm, vstart_dev, T, vcap, dx, dx_dtype, nsteps, x_bytes, st, addend, bn_reduce, tiles_only, nbr_compact
+#define CLS_MI(NBV) (mi == 2 ? launch_gg_cls<NBV, 2>(CLS_ARGS) : launch_gg_cls<NBV, 1>(CLS_ARGS))
     switch (c_in / 16) {
         case 1: return CLS_MI(1);
         case 2: return CLS_MI(2);

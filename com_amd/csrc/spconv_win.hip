@@ -133,8 +133,8 @@ struct WinCfg {
         return r * 32 + (((ei >> 3) ^ ((r >> 2) & 3)) << 3) + (ei & 7);
     }
     static constexpr bool DIRECT = NOQ == 1 && NCB == 1; // a wave owns whole rows: no cross-wave sums, the epilogue runs from registers
-    // what a further pass over a tile costs, in quarters of a tile's time (measured per workgroup, tools/exp_subm_win.py
-    // WIN_BALANCE: 2.84 / 1.32 / 0.94 tiles at 16 / 32 / 64 channels)
+    // what a further pass over a tile costs, in quarters of a tile's time (measured per workgroup with the entry / exit
+    // times the kernel wrote then: 2.84 / 1.32 / 0.94 tiles at 16 / 32 / 64 channels)
     static constexpr int PASS_COST = CIN <= 16 ? 11 : CIN <= 32 ? 5 : 4;
     static constexpr int SPR = (R / RPI + NW - 1) / NW;  // window DMA instructions per run and wave
     static constexpr int NSLOT = 3 * SPR + TSL;          // prefetch instructions per wave and tile
@@ -485,7 +485,6 @@ __global__ __launch_bounds__(256) void win_pack_batched_kernel(const long long *
 }
 
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-unsigned long long *g_win_trace = nullptr;     // profiling aid, NULL in production (pcd_subm_window_set_trace)
 
 // ---- the kernel ------------------------------------------------------------------------------------------------------
 struct WinPlan {                 // scalars only (an array member sent the struct to scratch memory)
@@ -501,7 +500,10 @@ __global__ __launch_bounds__(C::THREADS, C::NW == 8 ? 1 : 2) void subm_win_kerne
     const int4 *__restrict__ plan_g, unsigned short *__restrict__ y, unsigned x_bytes,
     const unsigned short *__restrict__ addend, BnRed bn, int dbg, unsigned long long *trace, float *__restrict__ y_f32) {
     __builtin_amdgcn_s_setprio(3);       // main-chain kernel (see spconv.hip: PCD_MAIN_PRIO)
-    // profiling aid (pcd_subm_window_set_trace): shader-clock stamps of workgroup 0 / wave 0 at the phase boundaries of its tiles
+    // `dbg` (ablation bits) and `trace` (profiling aid) are DORMANT: no option or entry point sets them any more, launch_win passes
+    // 0 / NULL.  They stay in this one kernel because taking them out changed its register allocation for the worse (16 channels:
+    // 239 / 240 -> 253 VGPRs with 20 bytes of scratch per lane; 32 channels: 230 / 234 -> 251 / 255) although every branch on
+    // them is dead -- the kernel sits at the register limit.  trace: shader-clock stamps of workgroup 0 / wave 0 at the phase boundaries of its tiles
     int trace_at = 0;
     auto stamp = [&]() {
         if (trace && blockIdx.x == 0 && threadIdx.x == 0 && trace_at < 256) trace[trace_at++] = __builtin_readcyclecounter();
@@ -603,7 +605,7 @@ __global__ __launch_bounds__(C::THREADS, C::NW == 8 ? 1 : 2) void subm_win_kerne
     // The prefetch of a tile is NSLOT VMEM instructions per wave, issued one at a time BETWEEN the MFMA steps of the previous
     // tile (a 1-KiB instruction occupies the CU's texture-address unit for ~34 clk and the in-order wave behind it: issued as one
     // burst after the barrier, the 40-80 instructions of a tile cost every wave 1.8 k clk before its first MFMA and skewed the
-    // waves by another 3 k clk -- measured with pcd_subm_window_set_trace).
+    // waves by another 3 k clk -- measured with the stamps below).
     //   slots 0 .. 3 SPR - 1: window pieces -- run g = s / SPR, 1-KiB instruction wave8 + 8 (s % SPR) of the run
     //   slots 3 SPR ..      : 1-KiB piece wave8 + 8 (s - 3 SPR) of the tile's table (NTABI pieces)
     constexpr int NSLOT = C::NSLOT, SPR = C::SPR;
@@ -791,7 +793,7 @@ __global__ __launch_bounds__(C::THREADS, C::NW == 8 ? 1 : 2) void subm_win_kerne
             // (window + table of tile t were published by the barriers of tile t - 1; B1 = "buffer buf ^ 1 is free" sits inside
             //  compute(), in front of the first prefetch slot)
             if (dbg & 64) {
-                // COSTING ABLATION (option "win_dbg" bit 6; results are wrong with it): what a BatchNorm applied ON READ would
+                // COSTING ABLATION (dbg bit 6; results are wrong with it): what a BatchNorm applied ON READ would
                 // cost this launch -- one in-LDS pass relu(scale * x + shift) over the tile's three landed runs (scale / shift per
                 // channel out of LDS, one bf16 rounding) + the barrier that publishes it, before the MFMA loop
                 const float *aff = (const float *)(smem + C::COLS);            // [2 COUT] floats: stands in for scale | shift
@@ -1037,7 +1039,7 @@ static int launch_win(const void *x, int n_rows, const void *wp, const float *bi
     k<<<grid, C::THREADS, C::LDS_BYTES, st>>>((const unsigned short *)x, (const uint4 *)wp, bias, nbr, nbr_stride,
                                                     n_rows, n_dev, (const int4 *)plan, (unsigned short *)y,
                                                     (unsigned)((size_t)n_rows * C::ROWB), (const unsigned short *)addend, bn,
-                                                    pcd_opt(PCD_OPT_WIN_DBG), g_win_trace, y_f32);
+                                                    0, nullptr, y_f32);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }
@@ -1089,14 +1091,8 @@ template <class C, int G>
 __device__ __forceinline__ void wgrad_win_body(const unsigned short *__restrict__ x, const unsigned short *__restrict__ dy,
                                                const int32_t *__restrict__ nbr, int nbr_stride, int n_cap, int n,
                                                const char *__restrict__ plan_g, float *__restrict__ slab, unsigned x_bytes,
-                                               unsigned dy_bytes, int share, char *smem, unsigned long long *trace) {
+                                               unsigned dy_bytes, int share, char *smem) {
     using W = WgCfg<C>;
-    int trace_at = 0;
-    auto stamp = [&]() {
-        if (trace && blockIdx.x == 0 && threadIdx.x == 0 && trace_at < 256) trace[trace_at++] = __builtin_readcyclecounter();
-    };
-    stamp();
-    const unsigned long long t_entry = trace ? __builtin_amdgcn_s_memrealtime() : 0ull;     // (100 MHz, the same clock on every CU)
     constexpr int T = C::T, R = C::R, ROWB = C::ROWB, S = C::S, CIN = C::CIN, NB = W::NB, NO = W::NO;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1273,13 +1269,10 @@ __device__ __forceinline__ void wgrad_win_body(const unsigned short *__restrict_
             const Run p = run_of(plan_s[(t - chunk0) * 2], plan_s[(t - chunk0) * 2 + 1]);
             // tile t + 2 into the stage tile t - 1 left (every wave passed the barrier behind its compute)
             int c_new = 0;
-            stamp();
             const bool pf = t + 2 < chunk1;
             const int tp = pf ? t + 2 : t;
             const Run pn = run_of(plan_s[(tp - chunk0) * 2], plan_s[(tp - chunk0) * 2 + 1]);
-            stamp();
             compute(buf, pf, pn, t + 2, buf == 0 ? 2 : buf - 1, &c_new);
-            stamp();
             for (int pass = 1; pass * R < p.cnt; ++pass) {
                 // the run is longer than the window (rare): its next R rows into the same stage, the nine table columns of
                 // the run rebuilt from the rulebook for that part
@@ -1307,14 +1300,12 @@ __device__ __forceinline__ void wgrad_win_body(const unsigned short *__restrict_
                 c_new = 0;                   // (everything has been waited for)
             }
             wait_vm(c_new);                  // tile t + 1 has landed (this wave's part): only tile t + 2's may be in flight
-            stamp();
             WIN_BARRIER();                   // ... everybody's, and everybody is done with stage buf
             buf = buf == 2 ? 0 : buf + 1;
         }
     }
 
     // the waves of a group that split the row steps: summed in wave order through LDS
-    stamp();
     __syncthreads();
     if (W::RS > 1) {
         float4 *red = (float4 *)smem;
@@ -1354,27 +1345,22 @@ __device__ __forceinline__ void wgrad_win_body(const unsigned short *__restrict_
             }
         }
     }
-    stamp();
-    if (trace && threadIdx.x == 0 && blockIdx.x < 256) {         // per-workgroup entry / exit times (trace[256 + b], trace[512 + b])
-        trace[256 + blockIdx.x] = t_entry;
-        trace[512 + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
-    }
 }
 
 template <class C>
 __global__ __launch_bounds__(C::THREADS, C::NW == 8 ? 1 : 2) void subm_wgrad_win_kernel(
     const unsigned short *__restrict__ x, const unsigned short *__restrict__ dy, const int32_t *__restrict__ nbr, int nbr_stride,
     int n_cap, const int32_t *__restrict__ n_dev, const char *__restrict__ plan_g, float *__restrict__ slab, unsigned x_bytes,
-    unsigned dy_bytes, unsigned long long *trace) {
+    unsigned dy_bytes) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
     if (j >= 3 * (C::WG_SHARES / 8)) return;
     const int share = xcd * (C::WG_SHARES / 8) + j / 3;
     const int n = eff_rows(n_dev, n_cap);
     switch (j % 3) {
-        case 0: wgrad_win_body<C, 0>(x, dy, nbr, nbr_stride, n_cap, n, plan_g, slab, x_bytes, dy_bytes, share, smem, trace); break;
-        case 1: wgrad_win_body<C, 1>(x, dy, nbr, nbr_stride, n_cap, n, plan_g, slab, x_bytes, dy_bytes, share, smem, trace); break;
-        default: wgrad_win_body<C, 2>(x, dy, nbr, nbr_stride, n_cap, n, plan_g, slab, x_bytes, dy_bytes, share, smem, trace); break;
+        case 0: wgrad_win_body<C, 0>(x, dy, nbr, nbr_stride, n_cap, n, plan_g, slab, x_bytes, dy_bytes, share, smem); break;
+        case 1: wgrad_win_body<C, 1>(x, dy, nbr, nbr_stride, n_cap, n, plan_g, slab, x_bytes, dy_bytes, share, smem); break;
+        default: wgrad_win_body<C, 2>(x, dy, nbr, nbr_stride, n_cap, n, plan_g, slab, x_bytes, dy_bytes, share, smem); break;
     }
 }
 
@@ -1388,7 +1374,7 @@ static int launch_wgrad_win(const void *x, const void *dy, int n_rows, const int
         return PCD_ERR_LAUNCH;
     const unsigned bytes = (unsigned)((size_t)n_rows * C::ROWB);
     k<<<WIN_GRID * (8 / C::NW), C::THREADS, W::LDS_BYTES, st>>>((const unsigned short *)x, (const unsigned short *)dy, nbr, nbr_stride, n_rows,
-                                                   n_dev, (const char *)plan, slab, bytes, bytes, g_win_trace);
+                                                   n_dev, (const char *)plan, slab, bytes, bytes);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }
@@ -1407,11 +1393,6 @@ extern "C" int pcd_subm_window_tile_rows(int c_in, int c_out) {
 // rows of PcdBnReduce.partial a forward / data-gradient launch of these widths writes (one per workgroup)
 extern "C" int pcd_subm_window_partial_rows(int c_in, int c_out) {
     return win_dispatch(c_in, c_out, [](auto c) { return win_grid<decltype(c)>(); }, 0);
-}
-
-extern "C" int pcd_subm_window_set_trace(void *buf256_u64) {
-    g_win_trace = (unsigned long long *)buf256_u64;
-    return PCD_OK;
 }
 
 extern "C" size_t pcd_subm_window_plan_bytes(int n_cap, int c_in, int c_out) {

@@ -12,8 +12,7 @@
  *     device memory and keeps no pointer after returning; all work is enqueued on `stream`
  *     (a hipStream_t, may be NULL for the default stream) and NOT synchronised;
  *   - functions keep no state between calls and may be called from several host threads; the ONLY process-wide state is the
- *     tuning-option table (pcd_set_option: set before the first launch, read unsynchronised at launch time) and the two
- *     profiling pointers that are NULL unless a tool sets them (pcd_subm_window_set_trace);
+ *     tuning-option table (pcd_set_option: set before the first launch, read unsynchronised at launch time);
  *   - index tensors are int32, coordinates are (batch, z, y, x) rows of 4 int32.
  *
  * Device-side row counts: wherever a function takes a row count `n` together with a `const int32_t *n_dev`
@@ -75,7 +74,7 @@ void pcd_set_last_hip_error(int code);    /* internal use */
 int pcd_stream_capture_id(void *stream, unsigned long long *id_out);
 
 /* ---- tuning options --------------------------------------------------------------------------
- * Integer knobs of the kernel dispatch (tile shapes, kernel variants, ablation switches).  They select between
+ * Integer knobs of the kernel dispatch (tile shapes, kernel variants).  They select between
  * implementations that produce the same results; the defaults are the measured optima and nothing in the product sets them.
  * Explicit and inspectable (no environment reads anywhere in the library): pcd_set_option returns PCD_ERR_INVALID_ARG for an
  * unknown key.  Process-wide, not synchronised: set them before the first call that uses them.  (No reference counterpart.)
@@ -95,7 +94,6 @@ int pcd_stream_capture_id(void *stream, unsigned long long *id_out);
  *   "wg_rows" 6144        row-range split of the generic weight-gradient kernel
  *   "conv2d_wg_blocks" 128 workgroups of the dense 3x3 weight-gradient kernel
  *   "fps_g" 0             workgroups per frame of the cooperative farthest point sampling (0: from the device's CU count)
- *   "gg_dbg" 0, "ggw_dbg" 0, "win_dbg" 0   ablation bit masks of the gather-GEMM kernels (profiling only)
  *   "subm_window_half" 0  4-wave window configurations (256 threads, <= 80 KB of LDS: two workgroups per CU): bit 1 = 32 channels,
  *                         bit 2 = 16 channels.  Set it before the first plan is built: plans, packs and launches of a width must agree
  *   "subm_window_grid" 256   workgroups of a window launch (a multiple of 8, <= 256); fewer leave CUs to other streams --
@@ -1289,10 +1287,6 @@ int pcd_debug_spin_shape(int blocks, int threads, int lds_bytes, int vgprs, unsi
  * ============================================================================================ */
 int pcd_subm_window_tile_rows(int c_in, int c_out);
 int pcd_subm_window_partial_rows(int c_in, int c_out);
-/* profiling aid: a device buffer of 1024 x u64 whose first 256 entries receive shader-clock stamps of workgroup 0 at the phase boundaries of its
- * tiles (7 per tile: barrier, prefetch issued, MFMA loop done, prefetch landed, barrier, partial sums written + barrier,
- * epilogue done); NULL (the default) = off.  Process-wide; tools/exp_subm_win.py */
-int pcd_subm_window_set_trace(void *buf256_u64);
 size_t pcd_subm_window_plan_bytes(int n_cap, int c_in, int c_out);
 int pcd_subm_window_plan(const int32_t *nbr, int nbr_stride, int n_cap, const int32_t *n_dev, int c_in, int c_out,
                          void *plan, void *stream);

@@ -111,14 +111,14 @@ def test_retired_kernels_are_out_of_the_library():
                "pcd_conv2d_wgrad_planes_splits", "pcd_conv2d_wgrad_planes_nhwc",
                "pcd_adam_flat_step", "pcd_adam_flat_step_v2", "pcd_adam_flat_step_v3", "pcd_sparse_conv_wgrad",
                "pcd_sparse_conv_dgrad_classes", "pcd_bn_forward", "pcd_bn_backward", "pcd_conv2d_3x3_nhwc",
-               "pcd_conv2d_3x3_nhwc_ld", "pcd_sparse_conv_gather_gemm_tiles"]
+               "pcd_conv2d_3x3_nhwc_ld", "pcd_sparse_conv_gather_gemm_tiles", "pcd_subm_window_set_trace"]
     for name in retired:
         assert not hasattr(default, name), f"{name} was retired: it must not be in the library"
     assert not set(retired) & set(_declared_symbols()) and not set(retired) & set(_lib.PROTOTYPES)
     lib = _lib.lib()
     assert lib.pcd_subm_window_tile_rows(128, 128) == 0 and lib.pcd_subm_window_tile_rows(64, 64) > 0
     value = ctypes.c_int()
-    for key in (b"ggwin", b"conv2d_wgp_blocks"):
+    for key in (b"ggwin", b"conv2d_wgp_blocks", b"gg_dbg", b"ggw_dbg", b"win_dbg"):
         assert lib.pcd_get_option(key, ctypes.byref(value)) != 0, key
         assert lib.pcd_set_option(key, 1) != 0, key
     with pytest.raises(_lib.PcdError):

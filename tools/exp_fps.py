@@ -6,7 +6,7 @@ sys.path.insert(0, '.')
 from com_amd import _lib as L, pointnet2_stack as P
 sys.path.insert(0, 'tools')
 import env_switches
-env_switches.apply()          # PCD_OPT_FPS_G=1000 + ablation bits (1: no loads, 2: no stores, 4: no bucket reduction)
+env_switches.apply()
 from com_amd.utils import synth
 import numpy as np
 B = 4
