@@ -6,8 +6,8 @@ from functools import partial
 import torch
 from torch import nn
 
-from .. import spconv
-from ..spconv import SparseConvTensor
+from .. import ops, spconv
+from ..spconv import SparseConvTensor, window
 from ..spconv import functional as Fsp
 
 
@@ -94,7 +94,10 @@ class _RulebookPrefetcher:
                 t.indice_dict.pop("__subm_hint__", None)
                 if rb.ready_event is None:
                     built.append(rb)
-                    self._window_plan(conv, rb)
+                    # the window kernel's tile plan too (ops.subm_window_plan caches it on the rulebook), here on the rulebook
+                    # stream: built by the first conv that uses it, it sat on the main chain (~30 us per level)
+                    if window.forward_on_tiles(conv, rb.order):
+                        ops.subm_window_plan(rb, conv.out_channels, conv.out_channels)
                 if not conv.subm:
                     t = SparseConvTensor(t.features, out_idx, out_shape, t.batch_size, indice_dict=t.indice_dict,
                                          num_rows=rb.n_out_dev)
@@ -104,7 +107,6 @@ class _RulebookPrefetcher:
                 ev.record(side)
                 for rb in built:
                     rb.ready_event = ev
-            from .. import ops
             if ops.STAMPS is not None:
                 ops.stamp(f"rb_unit{self.next - 1}")
             if self.next >= len(self.units) and self.after_units is not None:
@@ -137,30 +139,18 @@ class _RulebookPrefetcher:
     def _subm_hint(conv, unit, t):
         """(window width or None, neighbour table needed) for the SubM rulebook `conv` is about to build: all SubM convs of the
         unit with its kernel share that rulebook (SparseConvolution._rulebook), so the table is only needed if one of them
-        runs outside the window kernels -- forward / data gradient (window_capable) or, when autograd will run, the weight
-        gradient (option "subm_window_wgrad")."""
+        runs outside the window kernels -- forward / data gradient or, when autograd will run, the weight gradient.  (For
+        z-fastest rows: _rulebook takes the hint over no others.)"""
         group = [c for c in unit if c.subm and tuple(c.kernel_size) == tuple(conv.kernel_size)
                  and tuple(c.dilation) == tuple(conv.dilation)]
         widths = {c.out_channels for c in group if c.window_capable()}
         if len(widths) != 1:
             return None, True
-        w = widths.pop()
-        bf16 = t.features.dtype == torch.bfloat16
-        tables = not bf16 or any(not c.window_capable() or getattr(c, "fp8_train", None) is not None
-                                 or (c._needs_backward(t) and not Fsp.window_wgrad(c.out_channels)) for c in group)
-        return w, tables
-
-    @staticmethod
-    def _window_plan(conv, rb):
-        """The window kernel's tile plan of a freshly built SubM rulebook (ops.subm_window_plan caches it on the rulebook),
-        here on the rulebook stream: built by the first conv that uses it, it sat on the main chain (~30 us per level)."""
-        from .. import ops, _lib as L
-        if not (conv.subm and tuple(conv.kernel_size) == (3, 3, 3) and rb.order == ops.ROWS_YXZ):
-            return
-        c = conv.out_channels
-        bit = {64: 1, 32: 2, 16: 4, 128: 8}.get(c, 0)
-        if bit and (L.get_option("subm_window") & bit) and ops.subm_window_tile_rows(c, c) > 0:
-            ops.subm_window_plan(rb, c, c)
+        # (a layer with an fp8 training form keeps the table whether or not this forward takes that form)
+        tables = not all(window.forward_on_tiles(c, ops.ROWS_YXZ, t.features.dtype) and getattr(c, "fp8_train", None) is None
+                         and (not c._needs_backward(t) or window.wgrad_on_tiles(True, c.in_channels, c.out_channels))
+                         for c in group)
+        return widths.pop(), tables
 
 
 class _BackboneBase(nn.Module):
@@ -204,6 +194,7 @@ class _BackboneBase(nn.Module):
     after_rulebooks_at = None
     # rulebook units issued before the first conv; each unit's first consumer issues one more
     prefetch_depth = 2
+    _packed_ahead = None       # the `weight._version`s pack_after_update() packed, until the next forward takes its packs
 
     def _prefetch_rulebooks(self, x0):
         """All 9 rulebooks depend only on the voxel coordinates, not on features: they are built on a second HIP
@@ -241,12 +232,11 @@ class _BackboneBase(nn.Module):
         depth -= 1
         for _ in range(depth):
             pf.advance()
-        if getattr(self, "_packed_ahead", False):              # pack_after_update() ran since the last update
-            self._packed_ahead = False
-            # ... and no weight changed behind torch's back since (load_state_dict / broadcast / manual edits bump
-            # `_version`; the flat Adam kernel does not, and it is the update pack_after_update() follows)
-            if self._packed_versions == [c.weight._version for c in self._conv_list]:
-                return
+        ahead, self._packed_ahead = self._packed_ahead, None
+        # pack_after_update() ran since the last update, and no weight changed behind torch's back since (load_state_dict /
+        # broadcast / manual edits bump `_version`; the flat Adam kernel does not, and it is the update pack_after_update() follows)
+        if ahead is not None and ahead == [c.weight._version for c in self._conv_list]:
+            return
         pack_side = Fsp.side_stream(dev)                      # the wgrad stream is idle during the forward
         pack_side.wait_stream(cur)
         with torch.cuda.stream(pack_side):
@@ -261,19 +251,16 @@ class _BackboneBase(nn.Module):
         if not hasattr(self, "_conv_list"):
             return                                             # no forward yet: the first one packs by itself
         self._pack_all()
-        self._packed_ahead = True
-        self._packed_versions = [c.weight._version for c in self._conv_list]
+        self._packed_ahead = [c.weight._version for c in self._conv_list]
+
+    def forget_packs_ahead(self):
+        """The next forward packs from the live parameters, whatever pack_after_update() made."""
+        self._packed_ahead = None
 
     def _pack_all(self):
-        """All forward (+ dgrad) weight packs of the backbone in one launch."""
-        from .. import ops
-        todo = []
-        for conv in self._conv_list:
-            todo.append((conv, 0))
-            if self.training and conv.in_channels >= 16:
-                todo.append((conv, 1))
-        # (layers that run through the window kernel -- decided by their last forward -- get that kernel's layout: modes 2 / 3)
-        wm = [(c.weight.detach(), m + (2 if c.use_window else 0)) for c, m in todo]
+        """All forward (+ dgrad) weight packs of the backbone in one launch (two with window layers: theirs are in that layout)."""
+        modes = [conv.pack_modes(dgrad=self.training) for conv in self._conv_list]
+        wm = [(conv.weight.detach(), m) for conv, ms in zip(self._conv_list, modes) for m in ms]
         if not all(w.dtype == torch.float32 and w.is_contiguous() for w, _ in wm):
             for conv in self._conv_list:
                 conv.prepack(dgrad=self.training)
@@ -281,16 +268,12 @@ class _BackboneBase(nn.Module):
         plan = getattr(self, "_pack_plan", None)
         if plan is None or not plan.valid_for(wm):
             plan = self._pack_plan = ops.PackPlan(wm)
-        packed = plan.run()
-        got = {}
-        for (conv, mode), buf in zip(todo, packed):
-            got.setdefault(conv, [None, None])[mode] = buf
-        for conv, (f, d) in got.items():
-            conv.adopt_packs(f, d)        # (stamped with the conv's current use_window: a later change of mind repacks)
+        packed = iter(plan.run())
+        for conv, ms in zip(self._conv_list, modes):
+            conv.adopt_packs(*(next(packed) for _ in ms))     # (a later change of mind about the layout repacks)
 
     def _run(self, batch_dict):
         self._bump_bn_counters()
-        from .. import ops
         x0 = self._input_tensor(batch_dict)
         ops.stamp("fwd_begin")
         if ops.STAMPS is not None:

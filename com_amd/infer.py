@@ -80,8 +80,8 @@ class CapturedInference:
         """Weight packs a training step made ahead (backbone pack_after_update, Conv3x3Packs.run) are used by the next
         forward instead of packing: drop them, so that the forward -- and the graph -- packs from the live parameters."""
         for m in self.model.modules():
-            if getattr(m, "_packed_ahead", False):
-                m._packed_ahead = False
+            if hasattr(m, "forget_packs_ahead"):
+                m.forget_packs_ahead()
             if getattr(m, "_packs_ahead", None) is not None:
                 m._packs_ahead = None
 

@@ -12,6 +12,7 @@ from torch.nn import init
 
 from .. import ops
 from . import functional as Fsp
+from . import window
 from .core import SparseConvTensor
 from .modules import SparseModule
 
@@ -21,6 +22,56 @@ def _triple(v):
         assert len(v) == 3
         return [int(x) for x in v]
     return [int(v)] * 3
+
+
+class _PackCache:
+    """The packed (MFMA fragment order) copies of a layer's weight: slot 0 for the forward, slot 1 for the data gradient, in the
+    window kernel's layout while `window` is set.  `weight._version` is NOT a reliable change marker: fused optimizers
+    (torch.optim.Adam(fused=True), torch._fused_adam_) update parameters without bumping it.  So in training mode a pack is
+    used exactly once: put_ahead() (start of the step) or the access packs it, the access consumes it; in eval mode a slot
+    is cached per (version, pointer, device, layout), and train() / eval() switches drop the keys.  A repack writes into the
+    slot's buffer (`out=`): a captured step has recorded its address."""
+
+    def __init__(self):
+        self.window = False
+        self.buf = [None, None]
+        self.key = [None, None]
+        self.fresh = [False, False]
+
+    def _key(self, conv):
+        w = conv.weight
+        return (w._version, w.data_ptr(), w.device, self.window)
+
+    def _stale(self, conv, slot):
+        return self.buf[slot] is None or self.key[slot] != self._key(conv)
+
+    def _fill(self, conv, slot):
+        pack = ops.pack_weight_window if self.window else ops.pack_weight
+        self.buf[slot] = pack(conv.weight, slot, out=self.buf[slot])
+        self.key[slot] = self._key(conv)
+
+    def get(self, conv, slot):
+        if self._stale(conv, slot) or (conv.training and not self.fresh[slot]):
+            self._fill(conv, slot)
+        self.fresh[slot] = False
+        return self.buf[slot]
+
+    def put_ahead(self, conv, slot, buf=None):
+        """Fill a slot ahead of its use (`buf`: packed elsewhere, just now) and mark it fresh: the next access takes it as it is."""
+        if buf is not None:
+            self.buf[slot] = buf
+            self.key[slot] = self._key(conv)
+        elif conv.training or self._stale(conv, slot):
+            self._fill(conv, slot)
+        self.fresh[slot] = True
+
+    def dgrad_for(self, conv, window):
+        """The dgrad pack in the layout the FORWARD that asks for it decided on (`window`): the cached pack follows the
+        module's CURRENT decision, which another forward may have changed before this one's backward runs (an eval pass in
+        fp32, another row order, the fp8 toggle) -- then pack afresh in the layout the saved context needs."""
+        if bool(window) == self.window:
+            return self.get(conv, 1)
+        return ops.pack_weight_window(conv.weight, 1) if window else ops.pack_weight(conv.weight, 1)
 
 
 class SparseConvolution(SparseModule):
@@ -45,35 +96,22 @@ class SparseConvolution(SparseModule):
         else:
             self.register_parameter("bias", None)
         self.reset_parameters()
-        self._packed = None
-        self._packed_version = None
-        self._packed_d = None
-        self._packed_d_version = None
-        self._fresh_f = self._fresh_d = False
-        # window gather-GEMM (spconv_win.hip): SubM 3x3x3 layers whose widths have a window kernel take it when the chain's
-        # rows are numbered z-fastest (ops.ROWS_YXZ; decided per forward from the rulebook) -- their packs are then in that
-        # kernel's layout
-        self.use_window = False
+        self._packs = _PackCache()
 
     def window_capable(self):
-        """A window kernel exists for this layer (and the "subm_window" option admits it: bit 0 = 64 channels, bit 1 = 32, bit 2 = 16, bit 3 = 128)."""
-        if not (self.subm and tuple(self.kernel_size) == (3, 3, 3) and tuple(self.dilation) == (1, 1, 1)
-                and self.in_channels <= self.out_channels):
-            return False
-        from .. import _lib as L
-        opt = L.get_option("subm_window")
-        bit = {64: 1, 32: 2, 16: 4, 128: 8}.get(self.out_channels, 0)
-        if self.in_channels < self.out_channels and not (opt & 16):
-            return False         # (bit 4: fewer input channels than output channels -> rows zero-padded to the kernel's width;
-            #                       forward and weight gradient only: SparseConvolution.forward checks that no data gradient is due)
-        return bool(opt & bit) and ops.subm_window_tile_rows(self.out_channels, self.out_channels) > 0
+        return window.capable(self)
+
+    @property
+    def use_window(self):
+        """The last forward ran on the window tiles (spconv.window decides, per forward): the packs are in that kernel's layout."""
+        return self._packs.window
 
     def set_window(self, on):
-        on = bool(on)
-        if on != self.use_window:                  # the packs are in the other kernel's layout: drop them
-            self.use_window = on
-            self._packed_version = self._packed_d_version = None
-            self._fresh_f = self._fresh_d = False
+        p = self._packs
+        if bool(on) != p.window:                   # the packs are in the other kernel's layout: drop them (not their buffers)
+            p.window = bool(on)
+            p.key = [None, None]
+            p.fresh = [False, False]
 
     def reset_parameters(self):
         # spconv 2.x default init: kaiming_uniform_(a=sqrt(5)), bias ~ U(+-1/sqrt(fan_in))  (SURVEY.md A.5)
@@ -91,62 +129,29 @@ class SparseConvolution(SparseModule):
         return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, "
                 f"padding={self.padding}, subm={self.subm}, inverse={self.inverse}, key={self.indice_key}")
 
-    # Packed (MFMA fragment order) copies of the weight.  `weight._version` is NOT a reliable change marker:
-    # fused optimizers (torch.optim.Adam(fused=True), torch._fused_adam_) update parameters without bumping
-    # it.  So in training mode a pack is used exactly once: prepack() (start of the step) or the forward packs
-    # it, the forward / backward consumes it; in eval mode the pack is cached per (version, pointer) and
-    # train()/eval() switches drop the cache.
-    def _key(self):
-        return (self.weight._version, self.weight.data_ptr(), self.weight.device, self.use_window)
+    def _slots_ahead(self, dgrad):
+        return (0, 1) if dgrad and self.in_channels >= 16 else (0,)
 
-    def _pack(self, mode, out):
-        if self.use_window:
-            return ops.pack_weight_window(self.weight, mode, out=out)
-        return ops.pack_weight(self.weight, mode, out=out)
-
-    def _packed_fwd(self):
-        if self._packed is None or self._packed_version != self._key() or (self.training and not self._fresh_f):
-            self._packed = self._pack(0, self._packed)
-            self._packed_version = self._key()
-        self._fresh_f = False
-        return self._packed
-
-    def _packed_dgrad(self):
-        if self._packed_d is None or self._packed_d_version != self._key() or (self.training and not self._fresh_d):
-            self._packed_d = self._pack(1, self._packed_d)
-            self._packed_d_version = self._key()
-        self._fresh_d = False
-        return self._packed_d
-
-    def _packed_dgrad_for(self, window):
-        """The dgrad pack in the layout the FORWARD that asks for it decided on (`window`): the cached pack follows the
-        module's CURRENT decision, which another forward may have changed before this one's backward runs (an eval pass in
-        fp32, another row order, the fp8 toggle) -- then pack afresh in the layout the saved context needs."""
-        if bool(window) == self.use_window:
-            return self._packed_dgrad()
-        return ops.pack_weight_window(self.weight, 1) if window else ops.pack_weight(self.weight, 1)
+    def pack_modes(self, dgrad=True):
+        """The ops.PackPlan modes of the packs to make ahead (data gradient: from 16 input channels), in adopt_packs()'s order."""
+        return [slot + (2 if self._packs.window else 0) for slot in self._slots_ahead(dgrad)]
 
     def prepack(self, dgrad=True):
         """Pack the weights for forward (and dgrad) now -- e.g. on a side stream at the start of a step, so the
         ~40 small pack kernels of a backbone leave the critical path; the next forward / backward consumes
         these packs instead of packing again."""
-        self._fresh_f = False
-        self._packed_fwd()
-        self._fresh_f = True
-        if dgrad and self.in_channels >= 16:
-            self._fresh_d = False
-            self._packed_dgrad()
-            self._fresh_d = True
+        for slot in self._slots_ahead(dgrad):
+            self._packs.put_ahead(self, slot)
 
     def adopt_packs(self, fwd, dgrad=None):
         """Take freshly packed copies made elsewhere (ops.PackPlan: one launch for a whole backbone)."""
-        self._packed, self._packed_version, self._fresh_f = fwd, self._key(), True
+        self._packs.put_ahead(self, 0, fwd)
         if dgrad is not None:
-            self._packed_d, self._packed_d_version, self._fresh_d = dgrad, self._key(), True
+            self._packs.put_ahead(self, 1, dgrad)
 
     def train(self, mode=True):
         if mode != self.training:
-            self._packed_version = self._packed_d_version = None
+            self._packs.key = [None, None]
         return super().train(mode)
 
     def _rulebook(self, x):
@@ -174,23 +179,20 @@ class SparseConvolution(SparseModule):
             else:
                 # rows created by a strided conv of this chain are its bitmap ranks: no hash table needed
                 rank = x.indice_dict.get(("__rank__", x.indices.data_ptr()), None)
+                order = x.indice_dict.get("__row_order__", ops.ROWS_ZYX)
                 # 16-channel layers run their weight gradient through nbr_out (ops.WGRAD_OS): their rulebook is built
-                # without indice_pairs (derived on demand if some other consumer asks for them)
-                lazy = ops.WGRAD_OS and self.out_channels == 16 and self.in_channels <= 16 \
-                    and tuple(self.kernel_size) == (3, 3, 3)
-                # ... and so are the layers whose weight gradient runs over the window kernel's tiles
-                if not lazy and self.window_capable() and x.indice_dict.get("__row_order__", ops.ROWS_ZYX) == ops.ROWS_YXZ:
-                    from .functional import window_wgrad
-                    lazy = window_wgrad(self.out_channels)
-                # z-fastest rows with a column map: the window plan comes out of the same pass as the rulebook; a caller that
-                # knows ALL consumers of this rulebook (the backbones' prefetcher: indice_dict["__subm_hint__"] = (width,
-                # tables needed)) can drop the neighbour table altogether -- alone, a layer keeps it for the others
+                # without indice_pairs (derived on demand if some other consumer asks for them), and so are the layers whose
+                # weight gradient runs over the window kernel's tiles
+                lazy = (ops.WGRAD_OS and self.out_channels == 16 and self.in_channels <= 16
+                        and tuple(self.kernel_size) == (3, 3, 3)) \
+                    or window.wgrad_on_tiles(window.forward_on_tiles(self, order), self.in_channels, self.out_channels)
+                # with a column map the window plan comes out of the same pass as the rulebook; a caller that knows ALL
+                # consumers of this rulebook (the backbones' prefetcher: indice_dict["__subm_hint__"] = (width, tables needed))
+                # can drop the neighbour table altogether -- alone, a layer keeps it for the others
                 hint = x.indice_dict.pop("__subm_hint__", None)
-                win_c, tables = (self.out_channels if self.window_capable() else None), True
-                if hint is not None:
+                win_c, tables = (self.out_channels if window.forward_on_tiles(self, order) else None), True
+                if hint is not None and order == ops.ROWS_YXZ:
                     win_c, tables = hint
-                if x.indice_dict.get("__row_order__", ops.ROWS_ZYX) != ops.ROWS_YXZ:
-                    win_c, tables = None, True
                 rb = ops.rulebook_subm(x.indices, x.batch_size, x.spatial_shape, self.kernel_size,
                                        self.dilation, n_dev=x.num_rows, rank=rank,
                                        want_pairs=self._needs_backward(x) and not lazy,   # (inference never needs them)
@@ -245,27 +247,22 @@ class SparseConvolution(SparseModule):
             cur.wait_event(ev)                      # built on the prefetch stream: order this stream after it ONCE
             rb.joined_stream = cur.cuda_stream
             first_use = True
-        from .. import ops as _ops
-        dbg = _ops.STAMPS is not None and _ops.STAMPS.get("conv_seq", 99) < 3
+        dbg = ops.STAMPS is not None and ops.STAMPS.get("conv_seq", 99) < 3
         if dbg:
-            _ops.stamp(f"cv{_ops.STAMPS['conv_seq']}_a")
+            ops.stamp(f"cv{ops.STAMPS['conv_seq']}_a")
         fp8 = getattr(self, "fp8_train", None)
         if fp8 is not None and not (self.training and torch.is_grad_enabled()):
             fp8 = None                                  # (the fp8-forward training form; inference has Fp8Backbone)
-        # window kernel: SubM rulebook over z-fastest rows, bf16 features (decided here -- the packs follow the decision)
-        padded = self.in_channels < self.out_channels        # (conv_input: 5 -> 16 on rows zero-padded to 16 channels)
-        win = (fp8 is None and rb.subm and rb.order == ops.ROWS_YXZ and input.features.is_cuda
-               and input.features.dtype == torch.bfloat16
-               and (input.features.shape[1] == self.in_channels or
-                    (padded and input.features.shape[1] in (ops.pow2_ge8(self.in_channels), self.out_channels)))
-               and not (padded and input.features.requires_grad and torch.is_grad_enabled())
-               and self.window_capable())
+        # window kernel or not: decided here, per forward -- the packs follow the decision
+        x = input.features
+        win = fp8 is None and window.forward_on_tiles(self, rb.order, x.dtype, x.shape[1],
+                                                      x.requires_grad and torch.is_grad_enabled())
         self.set_window(win)
-        feats = Fsp.sparse_conv(input.features, self.weight, self.bias, rb, self._packed_fwd(),
-                                lambda w=win: self._packed_dgrad_for(w), passthrough, **({"fp8": fp8} if fp8 is not None else {}), window=win)
+        feats = Fsp.sparse_conv(x, self.weight, self.bias, rb, self._packs.get(self, 0),
+                                lambda w=win: self._packs.dgrad_for(self, w), passthrough, **({"fp8": fp8} if fp8 is not None else {}), window=win)
         if dbg:
-            _ops.stamp(f"cv{_ops.STAMPS['conv_seq']}_b")
-            _ops.STAMPS["conv_seq"] += 1
+            ops.stamp(f"cv{ops.STAMPS['conv_seq']}_b")
+            ops.STAMPS["conv_seq"] += 1
         ident = None
         if passthrough:
             feats, ident = feats

@@ -6,6 +6,7 @@ import torch
 from torch.autograd import Function
 
 from .. import ops
+from .window import wgrad_on_tiles
 
 
 OVERLAP_WGRAD = True
@@ -204,12 +205,6 @@ def _to_bf16_padded(x, c_pad):
     return x.contiguous()
 
 
-def window_wgrad(c):
-    """The "subm_window_wgrad" option admits the window weight gradient for c channels (bit 0 = 64, bit 1 = 32, bit 2 = 16)."""
-    from .. import _lib as L
-    return bool(L.get_option("subm_window_wgrad") & {64: 1, 32: 2, 16: 4}.get(int(c), 0))
-
-
 class SparseConvFunction(Function):
     """y = indice_conv(features, weight, rulebook) with bf16 MFMA, fp32 accumulate.
 
@@ -294,7 +289,7 @@ class SparseConvFunction(Function):
             if ctx.cin_pad % 16 != 0:
                 raise RuntimeError("dgrad needs >= 16 input channels (the 5-channel input layer never "
                                    "requires an input gradient)")
-            # (the pack's layout is bound to THIS forward's window decision: conv._packed_dgrad_for)
+            # (the pack's layout is bound to THIS forward's window decision: conv._PackCache.dgrad_for)
             if ctx.packed_dgrad is not None:
                 packed_d = ctx.packed_dgrad()
             else:
@@ -331,7 +326,7 @@ class SparseConvFunction(Function):
 
         def wgrad(direct, jobs):
             out = weight_p.grad if direct else None                                          # [Cout, K, Cin] f32
-            if ctx.window and rb.subm and ctx.cin <= ctx.cout == x.shape[1] and window_wgrad(ctx.cout):
+            if wgrad_on_tiles(ctx.window, ctx.cin, ctx.cout, x.shape[1]):
                 dwk = ops.subm_window_wgrad(x, dy16, rb, out=out, defer=jobs, cin=ctx.cin)
             else:
                 dwk = ops.wgrad(x, ctx.cin, dy16, None, None, rb.kvol, out=out, defer=jobs, rb=rb)

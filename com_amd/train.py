@@ -32,7 +32,7 @@ import torch
 
 from . import dist as cdist
 from . import hotpath, ops
-from .spconv import functional as Fsp
+from .spconv import SparseConvolution, functional as Fsp, window
 
 
 class VoxelizeConfig:
@@ -100,8 +100,8 @@ def feature_stride(model, voxelize):
     """The voxeliser emits the MeanVFE rows as the bf16 operand of the first conv: zero-padded to that conv's OUTPUT width
     when it runs on the window tiles (conv_input 5 -> 16 over z-fastest rows), to the next power of two >= 8 otherwise (None)."""
     backbone = getattr(model, "backbone_3d", None)
-    first = next((m for m in backbone.modules() if hasattr(m, "window_capable")), None) if backbone is not None else None
-    if first is not None and voxelize.row_order == "yxz" and first.in_channels < first.out_channels and first.window_capable():
+    first = next((m for m in backbone.modules() if isinstance(m, SparseConvolution)), None) if backbone is not None else None
+    if first is not None and first.in_channels < first.out_channels and window.forward_on_tiles(first, ops.ROW_ORDERS[voxelize.row_order]):
         return first.out_channels
     return None
 

@@ -2,12 +2,16 @@
 wait_event / wait_stream, in order -- and every parameter gradient, bit for bit, equal what the commit before
 functional.scheduled_backward issued and computed (tests/golden/backward_schedule_trace.json, written there by
 tests/golden/make_backward_schedule_trace.py with the logging code of tests/schedule_trace.py).  None of the weight-gradient
-kernels of these layers sums with fp32 atomics (the record was taken twice and agreed), so the gradients compare by sha256."""
+kernels of these layers sums with fp32 atomics (the record was taken twice and agreed), so the gradients compare by sha256.
+
+And the weight-pack launches of a whole backbone over four steps equal what the commit before SparseConvolution's pack cache
+issued (tests/golden/backbone_pack_trace.json, tests/golden/make_pack_window_traces.py, tests/pack_window_trace.py)."""
 import json
 import os
 
 import pytest
 
+import pack_window_trace as P
 import schedule_trace as T
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +19,11 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def golden_trace():
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "backward_schedule_trace.json")) as f:
+    return _golden("backward_schedule_trace.json")
+
+
+def _golden(name):
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name)) as f:
         return json.load(f)
 
 
@@ -28,3 +36,14 @@ def test_launch_sequence_and_gradients_are_the_recorded_ones(case, setting, gold
         assert a == b, (i, a, b, got["log"][max(0, i - 5):i + 3], want["log"][max(0, i - 5):i + 3])
     assert len(got["log"]) == len(want["log"])
     assert got["grads"] == want["grads"]
+
+
+def test_backbone_packs_once_per_step_and_ahead_of_the_forward_when_told(monkeypatch):
+    """VoxelBackBone8x, training, z-fastest bf16 rows: pack_after_update() packs every layer in two batched launches (generic +
+    window layers) on the current stream; the step behind it packs nothing; a step without it packs on the side stream, in
+    front of the first conv; and so does a step whose weights were edited behind pack_after_update()'s back."""
+    want = _golden("backbone_pack_trace.json")
+    batched = ["pcd_pack_weights_batched", "pcd_subm_window_pack_weights_batched"]
+    assert want["pack_after_update"] == [[n, "main"] for n in batched] and want["step 2"] == []      # the record itself
+    assert want["edit, step 3"] == [[n, "side"] for n in batched]
+    assert P.backbone_pack_trace(monkeypatch) == want

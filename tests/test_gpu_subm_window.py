@@ -225,7 +225,7 @@ def test_submconv3d_module_takes_the_window_kernel_on_yxz_rows_and_matches_the_g
 def test_backward_keeps_the_pack_layout_of_its_own_forward_when_the_module_changes_its_mind(pcd_option):
     """Forward A through the window kernel, then forward B of the SAME module with the window option off (the module drops its
     window packs), then A's backward: its data gradient must still come out of the window kernel with a window-layout pack
-    (conv._packed_dgrad_for binds the layout to the forward) -- equal to the undisturbed run bit for bit."""
+    (the layer's pack cache binds the layout to the forward: dgrad_for) -- equal to the undisturbed run bit for bit."""
     from com_amd import spconv
     idx, rank, shape = _level(1, 3)
     n, ch = idx.shape[0], 64
