@@ -17,51 +17,14 @@
 // -ffp-contract=off (Makefile): labels depend on `==` and `>=` of fp32 values evaluated in the reference's order.
 #include "anchorhead_common.h"
 
-#define ANC_CHUNK 256
-#define ANC_BOXF 6      // prepared box: x1, y1, x2, y2, area, class slot (int bits)
-
 namespace {
 
-
-struct Anchor {
-    float xa, ya, za, dxa, dya, dza, ra, diag;
-    float x1, y1, x2, y2, area;
-    int slot;
-};
-
+// anchor n of a frame in the single head's order: (y, x, kind) = (n / (W * A), n / A % W, n % A)
 __device__ __forceinline__ Anchor make_anchor(const float *s_kind, const float *shifts, int n, int A, int W, int H,
                                               int n_classes) {
-    Anchor a;
     const int cell = n / A, k = n - cell * A;
     const int y = cell / W, x = cell - y * W;
-    const float *kd = s_kind + k * ANC_KIND_F;
-    a.slot = min(max((int)kd[K_SLOT], 0), n_classes - 1);            // (a table row can never index outside the shifts)
-    const float *sh = shifts + (size_t)a.slot * (W + H);
-    a.xa = sh[x];
-    a.ya = sh[W + y];
-    a.dxa = kd[K_DX];
-    a.dya = kd[K_DY];
-    a.dza = kd[K_DZ];
-    a.ra = kd[K_ROT];
-    a.za = kd[K_ZC];
-    a.diag = kd[K_DIAG];
-    // box_utils.py:322-324 with the host's choice of the (dx, dy) | (dy, dx) halves
-    a.x1 = a.xa - kd[K_HX];
-    a.y1 = a.ya - kd[K_HY];
-    a.x2 = a.xa + kd[K_HX];
-    a.y2 = a.ya + kd[K_HY];
-    a.area = (a.x2 - a.x1) * (a.y2 - a.y1);
-    return a;
-}
-
-// box_utils.py:301-310 for one pair (0 / x == 0 for the pairs that do not intersect: no division for them)
-__device__ __forceinline__ float pair_iou(const Anchor &a, const float *bx) {
-    const float x_min = fmaxf(a.x1, bx[0]), x_max = fminf(a.x2, bx[2]);
-    const float y_min = fmaxf(a.y1, bx[1]), y_max = fminf(a.y2, bx[3]);
-    const float x_len = fmaxf(x_max - x_min, 0.f), y_len = fmaxf(y_max - y_min, 0.f);
-    const float inter = x_len * y_len;
-    if (!(inter > 0.f)) return 0.f;
-    return __fdiv_rn(inter, fmaxf(a.area + bx[4] - inter, 1e-6f));
+    return anchor_of_kind(s_kind + k * ANC_KIND_F, shifts, x, y, W, H, n_classes);
 }
 
 // ---- launch 1: boxes -> aligned BEV boxes, class slots; clears the per-box maxima and the positive counts

@@ -1,7 +1,8 @@
-// What the anchor-head loss kernels share (anchorhead.hip: AnchorHeadSingle; anchorhead_cur.hip: the COM curriculum
-// form): table layout, the prediction-map descriptor, ONE loss core with a compile-time curriculum variant, the ordered
-// second pass and the host-side argument checks; the focal element and the ordered pass also serve the point head
-// (roiaware.hip).  Include inside the translation unit (everything is file-local).
+// What the anchor-head kernels share (anchorhead.hip: AnchorHeadSingle; anchorhead_cur.hip: the COM curriculum form;
+// anchorhead_multi.hip: AnchorHeadMulti): table layout, the described anchor and the nearest-BEV pair IoU, the
+// prediction-map descriptor, ONE loss core with a compile-time curriculum variant, the ordered second pass and the
+// host-side argument checks; the focal element and the ordered pass also serve the point head (roiaware.hip).  Include
+// inside the translation unit (everything is file-local).
 #pragma once
 #include "common.h"
 
@@ -21,6 +22,50 @@ enum { K_DX = 0, K_DY, K_DZ, K_ROT, K_ZC, K_SLOT, K_HX, K_HY, K_DIAG };
 __device__ __forceinline__ void stage_kinds(float *s_kind, const float *kinds, int n_kinds) {
     for (int i = threadIdx.x; i < n_kinds * ANC_KIND_F; i += blockDim.x) s_kind[i] = kinds[i];
     __syncthreads();
+}
+
+// ---- the described anchor and the nearest-BEV pair IoU (anchorhead.hip and anchorhead_multi.hip order the anchors
+// differently; what an anchor IS, given its kind row and its cell, is the same)
+#define ANC_CHUNK 256
+#define ANC_BOXF 6      // prepared box: x1, y1, x2, y2, area, class slot (int bits)
+
+struct Anchor {
+    float xa, ya, za, dxa, dya, dza, ra, diag;
+    float x1, y1, x2, y2, area;
+    int slot;
+};
+
+// the anchor of kind row `kd` (ANC_KIND_F leading floats) at cell (x, y)
+__device__ __forceinline__ Anchor anchor_of_kind(const float *kd, const float *shifts, int x, int y, int W, int H,
+                                                 int n_classes) {
+    Anchor a;
+    a.slot = min(max((int)kd[K_SLOT], 0), n_classes - 1);            // (a table row can never index outside the shifts)
+    const float *sh = shifts + (size_t)a.slot * (W + H);
+    a.xa = sh[x];
+    a.ya = sh[W + y];
+    a.dxa = kd[K_DX];
+    a.dya = kd[K_DY];
+    a.dza = kd[K_DZ];
+    a.ra = kd[K_ROT];
+    a.za = kd[K_ZC];
+    a.diag = kd[K_DIAG];
+    // box_utils.py:322-324 with the host's choice of the (dx, dy) | (dy, dx) halves
+    a.x1 = a.xa - kd[K_HX];
+    a.y1 = a.ya - kd[K_HY];
+    a.x2 = a.xa + kd[K_HX];
+    a.y2 = a.ya + kd[K_HY];
+    a.area = (a.x2 - a.x1) * (a.y2 - a.y1);
+    return a;
+}
+
+// box_utils.py:301-310 for one pair (0 / x == 0 for the pairs that do not intersect: no division for them)
+__device__ __forceinline__ float pair_iou(const Anchor &a, const float *bx) {
+    const float x_min = fmaxf(a.x1, bx[0]), x_max = fminf(a.x2, bx[2]);
+    const float y_min = fmaxf(a.y1, bx[1]), y_max = fminf(a.y2, bx[3]);
+    const float x_len = fmaxf(x_max - x_min, 0.f), y_len = fmaxf(y_max - y_min, 0.f);
+    const float inter = x_len * y_len;
+    if (!(inter > 0.f)) return 0.f;
+    return __fdiv_rn(inter, fmaxf(a.area + bx[4] - inter, 1e-6f));
 }
 
 struct AncMaps {            // the three prediction maps (and their gradients): element strides {batch, channel, y, x}

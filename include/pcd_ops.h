@@ -751,6 +751,75 @@ int pcd_anchor_decode(const void *cls_preds, const void *box_preds, const void *
                       float dir_limit_offset, float *batch_box_preds, float *batch_cls_preds, void *stream);
 
 /* ============================================================================================
+ * (f3m) AnchorHeadMulti on the device (the dense head of tools/cfgs/nuscenes_models/cbgs_{second,pp}_multihead.yaml,
+ *       lyft_models/cbgs_second{,-nores}_multihead.yaml, kitti_models/second_multihead.yaml; USE_MULTIHEAD +
+ *       SEPARATE_MULTIHEAD) -- com_amd/csrc/anchorhead_multi.hip.  The assignment rule, the focal / smooth-L1 / direction
+ *       arithmetic and the ordered sums are those of (f3); what differs is the anchor order, per-head prediction maps,
+ *       ResidualCoder in full (any code size, sin/cos heading), WeightedL1Loss and pos_cls_weight / neg_cls_weight.
+ *       Every entry point takes a stream, allocates nothing, reads nothing back and launches a fixed number of kernels
+ *       (3 / 2 / 1 / 1); one launch covers all heads.
+ *
+ *   Anchor order (axis_aligned_target_assigner.py:69, anchor_head_template.py:244): every class's anchors permuted to
+ *   (size, rotation, z, y, x), classes concatenated: anchor n = (g * H + y) * W + x with g the GLOBAL kind (class in
+ *   ANCHOR_GENERATOR_CONFIG order, then size, then rotation); N = n_kinds * H * W.  Head h owns the kinds
+ *   [kind0, kind0 + n_kinds) and the classes [class0, class0 + num_class); the heads tile both ranges in order.
+ *     kinds   device f32 [n_kinds][PCD_ANCHOR_MULTI_KIND_FLOATS]: the PCD_ANCHOR_KIND_FLOATS of (f3), then cos and sin of
+ *             the heading as torch computes them on the host (so that the sin/cos codes use the reference's anchor values)
+ *     classes, shifts: as in (f3)
+ *   Prediction maps: one PcdAnchorMultiHead per head (host array, passed by value to the kernels): cls / box / dir map
+ *   pointers (dir NULL in every head: no direction classifier), their gradients, element strides {batch, channel, y, x};
+ *   one dtype for all maps.  Channel of (local anchor a, item j) = a * items + j with items = num_class of the head, `code`
+ *   or the number of bins -- the reference's view(-1, A_h, items, H, W) (anchor_head_multi.py:124-137).  For a head with
+ *   SEPARATE_REG_CONFIG the box map is the channel concatenation of its branches in REG_LIST order; the same formula then
+ *   cuts across the branches when A_h > 1, as the reference's view does.
+ *
+ *   pcd_anchor_multi_assign_targets  gt_boxes [B][M][code_gt + 1] (code_gt 7 | 9; the 1-based class id last; zero rows =
+ *     padding, anywhere).  box_reg_targets f32 [B][N][code], code = code_gt + sincos: six position / size codes, then
+ *     rg - ra | (cos rg - cos ra, sin rg - sin ra), then the extra columns (box_coder_utils.py:13-43).  The other outputs
+ *     as pcd_anchor_assign_targets; num_pos counts the positives of all heads.
+ *   pcd_anchor_multi_loss_forward / _backward  anchor_head_multi.py:245-373.  Focal weight of an anchor = (pos_cls_weight |
+ *     neg_cls_weight) / max(num_pos[b], 1); a head's one-hot target is its class slice of the global one-hot; num_class == 1
+ *     (all heads together): class-agnostic.  reg_l1 == 0: WeightedSmoothL1Loss (beta 1/9), 1: WeightedL1Loss; with
+ *     direction maps the sin-difference substitution on code 6 and the direction cross entropy.  code_weights device
+ *     f32 [code].  out device f32[4] = rpn_loss, _cls, _loc, _dir over all heads, weighted; per-workgroup partials + one
+ *     ordered pass.  The backward writes every element of every head's gradient maps.
+ *   pcd_anchor_multi_decode  batch_box_preds f32 [B][N][code - sincos] (decode_torch: atan2(sint + sin ra, cost + cos ra)
+ *     when sincos; + the direction-bin correction with direction maps); cls_out_host[h]: device f32 [B][N_h][num_class_h],
+ *     the logits of head h (N_h = n_kinds_h * H * W).
+ * ============================================================================================ */
+#define PCD_ANCHOR_MULTI_KIND_FLOATS 12
+#define PCD_ANCHOR_MULTI_MAX_HEADS 8
+#define PCD_ANCHOR_MULTI_MAX_CODE 10
+typedef struct PcdAnchorMultiHead {
+    const void *map[3];                       /* cls, box, dir (or NULL) */
+    void *grad[3];                            /* their gradients (backward only) */
+    long long strides[3][4];                  /* element strides {batch, channel, y, x} of each map */
+    int kind0, n_kinds, class0, num_class;
+} PcdAnchorMultiHead;
+size_t pcd_anchor_multi_assign_workspace_bytes(int batch, int n_boxes);
+int pcd_anchor_multi_assign_targets(const float *gt_boxes, int batch, int n_boxes, int code_gt, int sincos,
+                                    const float *kinds, int n_kinds, const float *classes, int n_classes,
+                                    const float *shifts, int height, int width, int *box_cls_labels, float *box_reg_targets,
+                                    float *reg_weights, int *gt_index, int *num_pos, void *workspace, size_t workspace_bytes,
+                                    void *stream);
+size_t pcd_anchor_multi_loss_workspace_bytes(int batch, int height, int width, int n_kinds);
+int pcd_anchor_multi_loss_forward(const PcdAnchorMultiHead *heads, int n_heads, int dtype, const int *box_cls_labels,
+                                  const float *box_reg_targets, const int *num_pos, int batch, int height, int width,
+                                  int n_kinds, int num_class, int code, int reg_l1, int num_dir_bins, const float *kinds,
+                                  const float *code_weights, float pos_cls_weight, float neg_cls_weight, float cls_weight,
+                                  float loc_weight, float dir_weight, float dir_offset, float *out /*device [4]*/,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int pcd_anchor_multi_loss_backward(const PcdAnchorMultiHead *heads, int n_heads, int dtype, const int *box_cls_labels,
+                                   const float *box_reg_targets, const int *num_pos, int batch, int height, int width,
+                                   int n_kinds, int num_class, int code, int reg_l1, int num_dir_bins, const float *kinds,
+                                   const float *code_weights, float pos_cls_weight, float neg_cls_weight, float cls_weight,
+                                   float loc_weight, float dir_weight, float dir_offset, const float *grad_out, void *stream);
+int pcd_anchor_multi_decode(const PcdAnchorMultiHead *heads, int n_heads, int dtype, int batch, int height, int width,
+                            int n_kinds, int n_classes, int code, int sincos, int num_dir_bins, const float *kinds,
+                            const float *shifts, float dir_offset, float dir_limit_offset, float *batch_box_preds,
+                            float *const *cls_out_host, void *stream);
+
+/* ============================================================================================
  * (f3b) The COM curriculum on the anchor head: CurriculumAnchorHeadSingle and its head_zoo variants (_x1, _car, _car_x2)
  *       over AnchorHeadCurriculum / CurriculumAxisAlignedTargetAssigner / CurriculumSigmoidFocalClassificationLoss --
  *       com_amd/csrc/anchorhead_cur.hip.  Tables, maps and labels as in (f3); every entry point takes a stream, allocates

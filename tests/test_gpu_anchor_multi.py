@@ -1,0 +1,232 @@
+"""GPU: the multi-head anchor head's kernels (com_amd/csrc/anchorhead_multi.hip) and module against fixtures g38-g42 = the
+reference's own AnchorHeadMulti run on the CPU (tests/golden/make_golden_anchor_multi.py).  The map is 24 x 20, so a block
+of 256 anchors straddles kinds and heads.  Labels, the positives' box index and num_pos: exactly equal, every anchor.
+Regression targets and decoded boxes: rtol 1e-6, atol 1e-6 (the bar of tests/test_gpu_anchor_head.py).  Losses: 1e-4
+relative to fp64 arithmetic on the same (rounded) inputs, gradients relative to the largest magnitude of the tensor."""
+import numpy as np
+import pytest
+import torch
+
+from com_amd import _lib as L
+from com_amd.hotpath import anchor_head_multi as AM
+from tests import anchor_multi_ref as AR
+
+pytestmark = pytest.mark.gpu
+CASES = ["N", "K"]
+
+
+def _head(case, **kw):
+    names = AR.CASES[case]["names"]
+    return AM.AnchorHeadMulti(AR.model_cfg(case), AR.IN_CHANNELS, len(names), names, np.array(AR.GRID), AR.RANGE, **kw).cuda()
+
+
+def _check_targets(ret, g, case):
+    ref_labels = g[f"{case}_labels"].astype(np.int32)
+    labels = ret["box_cls_labels"].cpu().numpy()
+    assert ret["box_cls_labels"].dtype == torch.int32
+    print(f"[assign {case}] label mismatches {(labels != ref_labels).sum()} of {labels.size}")
+    np.testing.assert_array_equal(labels, ref_labels)                       # every anchor of every frame
+    np.testing.assert_array_equal(ret["box_gt_index"].cpu().numpy(), g[f"{case}_gt_index"])
+    np.testing.assert_array_equal(ret["num_pos"].cpu().numpy(), g[f"{case}_num_pos"])
+    np.testing.assert_array_equal(ret["reg_weights"].cpu().numpy(), (ref_labels > 0).astype(np.float32))
+    return ref_labels
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_target_assignment_matches_reference_fixture(golden, case):
+    g = golden("g38_anchor_multi_targets")
+    head = _head(case)
+    ret = head.assign_targets(torch.from_numpy(g[f"{case}_gt_boxes"]).cuda())
+    ref_labels = _check_targets(ret, g, case)
+    assert (ref_labels[0] > 0).sum() > 10 and (ref_labels[2] == 0).all()
+    targets, ref_t = ret["box_reg_targets"].cpu().numpy(), g[f"{case}_targets"]
+    assert targets.shape == ref_t.shape and targets.shape[2] == (10 if case == "N" else 7)
+    print(f"[assign {case}] max |target - reference| {np.abs(targets - ref_t).max():.3e}")
+    assert (targets[ref_labels <= 0] == 0).all()
+    np.testing.assert_allclose(targets, ref_t, rtol=1e-6, atol=1e-6)
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_assignment_has_no_cap_on_the_number_of_boxes(golden, case):
+    """600 boxes per frame (three LDS chunks): the first rows are the fixture's, the rest padding and far-away boxes --
+    same labels, same box indices."""
+    g = golden("g38_anchor_multi_targets")
+    gt0 = g[f"{case}_gt_boxes"]
+    gt = np.zeros((gt0.shape[0], 600, gt0.shape[2]), np.float32)
+    gt[:, :gt0.shape[1]] = gt0
+    gt[:, 300:560, :7] = [500.0, 500.0, 0.0, 4.0, 2.0, 1.5, 0.3]
+    gt[:, 300:560, -1] = 1
+    _check_targets(_head(case).assign_targets(torch.from_numpy(gt).cuda()), g, case)
+
+
+def _fixture_maps(g, case, dtype):
+    n = len(AR.head_layout(case))
+    return [[torch.from_numpy(g[f"{case}_{name}{h}"]).to(dtype) for h in range(n)] if f"{case}_{name}0" in g else None
+            for name in ("cls", "box", "dir")]
+
+
+def _fp64(case, maps, labels, targets, anchors):
+    """tests/anchor_multi_ref.py in fp64 on `maps` (== the reference's fp64: test_anchor_multi_cpu)"""
+    cfg = AR.model_cfg(case)
+    lw = cfg["LOSS_CONFIG"]["LOSS_WEIGHTS"]
+    t = [[m.double().requires_grad_(True) for m in group] if group is not None else None for group in maps]
+    r = AR.get_loss(t[0], t[1], t[2], torch.from_numpy(labels.astype(np.int64)), torch.from_numpy(targets),
+                    torch.from_numpy(anchors[:, 6]), AR.head_layout(case), len(AR.CASES[case]["names"]),
+                    cfg["LOSS_CONFIG"].get("REG_LOSS_TYPE") == "WeightedL1Loss", lw.get("pos_cls_weight", 1.0),
+                    lw.get("neg_cls_weight", 1.0), (lw["cls_weight"], lw["loc_weight"], lw["dir_weight"]),
+                    code_weights=torch.tensor(lw["code_weights"]))
+    r[0].backward()
+    return np.array([float(v.detach()) for v in r]), [[x.grad.numpy() for x in group] if group is not None else None for group in t]
+
+
+@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_loss_and_gradients_against_fp64(golden, case, dtype):
+    g38, g = golden("g38_anchor_multi_targets"), golden(f"g39_anchor_multi_loss_{case}")
+    head = _head(case)
+    tab = head.tables("cuda")
+    tg = head.assign_targets(torch.from_numpy(g38[f"{case}_gt_boxes"]).cuda())
+    np.testing.assert_array_equal(tg["box_cls_labels"].cpu().numpy(), g38[f"{case}_labels"].astype(np.int32))
+    host = _fixture_maps(g, case, dtype)
+    dev = [[m.cuda().requires_grad_(True) for m in group] if group is not None else None for group in host]
+    loss, out = AM.multi_loss(dev[0], dev[1], dev[2], tg, tab, head.code_weights, head._loss)
+    loss.backward()
+    s64, grads64 = _fp64(case, host, g38[f"{case}_labels"], g38[f"{case}_targets"], g38[f"{case}_anchors"])
+    if dtype == torch.float32:
+        np.testing.assert_allclose(s64, g[f"{case}_f64_scalars"], rtol=1e-6)
+    ulp = 0.0 if dtype == torch.float32 else 2.0 ** -8       # the gradient is STORED in bf16: one bf16 ulp of the element
+    got = out.cpu().numpy().astype(np.float64)
+    print(f"[loss {case} {dtype}] device {got} fp64 {s64} rel {np.abs(got - s64) / np.maximum(np.abs(s64), 1e-30)}")
+    assert float(loss) == got[0]
+    np.testing.assert_allclose(got, s64, rtol=1e-4)
+    for name, group, refs in zip(("cls", "box", "dir"), dev, grads64):
+        for h, (t, ref) in enumerate(zip(group or [], refs or [])):
+            err = np.abs(t.grad.float().cpu().numpy() - ref)
+            print(f"[loss {case} {dtype}] d{name}{h}: max err / max |grad| = {err.max() / np.abs(ref).max():.3e}")
+            assert np.abs(ref).max() > 0
+            assert (err <= 1e-4 * np.abs(ref).max() + ulp * np.abs(ref)).all(), (name, h)
+    # every element of every gradient map is written (NaN-filled buffers), and a second run gives the same bits
+    maps = [[t.detach() for t in group] if group is not None else None for group in dev]
+    grads = [[torch.full_like(t, float("nan")) for t in group] if group is not None else [] for group in maps]
+    heads, code, B = AM._head_structs(tab, maps[0], maps[1], maps[2], grads)
+    one = torch.ones(1, device="cuda")
+    L.check(L.lib().pcd_anchor_multi_loss_backward(
+        heads, len(tab.heads), code, L.ptr(tg["box_cls_labels"]), L.ptr(tg["box_reg_targets"]), L.ptr(tg["num_pos"]), B, tab.H,
+        tab.W, tab.G, head._loss.num_class, tab.code, head._loss.reg_l1, tab.num_dir_bins, L.ptr(tab.kinds),
+        L.ptr(head.code_weights), *head._loss.weights, tab.dir_offset, L.ptr(one), L.stream_ptr()), "backward")
+    for group, again in zip(dev, grads):
+        for t, d in zip(group or [], again):
+            assert not torch.isnan(d.float()).any() and torch.equal(d, t.grad)
+    loss2, out2 = AM.multi_loss([t.detach() for t in dev[0]], [t.detach() for t in dev[1]],
+                                [t.detach() for t in dev[2]] if dev[2] is not None else None, tg, tab, head.code_weights,
+                                head._loss)
+    assert torch.equal(out, out2)
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_decoding_matches_reference_fixture(golden, case):
+    """Heading of case N: atan2(sint + sin ra, cost + cos ra), compared as a wrapped difference at 1e-6 (the fixture keeps
+    the argument at least 0.5 away from the origin)."""
+    g = golden(f"g40_anchor_multi_decode_{case}")
+    head = _head(case)
+    maps = [[m.cuda() for m in group] if group is not None else None for group in _fixture_maps(g, case, torch.float32)]
+    logits, boxes = head.generate_predicted_boxes(maps[0][0].shape[0], maps[0], maps[1], maps[2])
+    ref, got = g[f"{case}_batch_box_preds"], boxes.cpu().numpy()
+    assert got.shape == ref.shape and got.shape[2] == (9 if case == "N" else 7)
+    d = got[..., 6] - ref[..., 6]
+    d = d - np.round(d / (2 * np.pi)) * 2 * np.pi
+    print(f"[decode {case}] max abs err (no heading) {np.abs(np.delete(got - ref, 6, axis=2)).max():.3e}, heading {np.abs(d).max():.3e}")
+    np.testing.assert_allclose(np.delete(got, 6, axis=2), np.delete(ref, 6, axis=2), rtol=1e-6, atol=1e-6)
+    assert (np.abs(d) <= 1e-6 + 1e-6 * np.abs(ref[..., 6])).all()
+    for h, t in enumerate(logits):                                          # per-head logits == the inputs as fp32
+        np.testing.assert_array_equal(t.cpu().numpy(), g[f"{case}_batch_cls_preds{h}"])
+    # bf16 maps decode the rounded values
+    bf = [[m.bfloat16() for m in group] if group is not None else None for group in maps]
+    l2, b2 = head.generate_predicted_boxes(maps[0][0].shape[0], bf[0], bf[1], bf[2])
+    l3, b3 = head.generate_predicted_boxes(maps[0][0].shape[0], *[[m.float() for m in group] if group is not None else None
+                                                                  for group in bf])
+    assert torch.equal(b2, b3) and all(torch.equal(a, b) for a, b in zip(l2, l3))
+
+
+def _loaded(golden, case):
+    g = golden("g42_anchor_multi_module")
+    head = _head(case).train()
+    head.load_state_dict({str(k): torch.from_numpy(g[f"{case}_state_{k}"]) for k in g[f"{case}_keys"]}, strict=True)
+    g38 = golden("g38_anchor_multi_targets")
+    return g, head, torch.from_numpy(g[f"{case}_input"]).cuda(), torch.from_numpy(g38[f"{case}_gt_boxes"]).cuda()
+
+
+def _step(head, x, gt):
+    """-> loss, tb_dict, parameter gradients, data_dict, gradients of every head's prediction maps"""
+    dd = head(dict(spatial_features_2d=x, gt_boxes=gt, batch_size=x.shape[0]))
+    loss, tb = head.get_loss()
+    f = head.forward_ret_dict
+    maps = f["cls_preds"] + f["box_preds"] + f.get("dir_cls_preds", [])
+    params = [p for p in head.parameters() if p.requires_grad]
+    grads = torch.autograd.grad(loss, params + maps, allow_unused=True)
+    return loss.detach(), tb, [q for q in grads[:len(params)] if q is not None], dd, list(grads[len(params):])
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_module_reproduces_the_references_loss(golden, case):
+    """the reference's weights, input and boxes (training mode, fp32 compute): its rpn_loss within 1e-3 relative"""
+    g, head, x, gt = _loaded(golden, case)
+    loss, tb, grads, dd, _ = _step(head, x, gt)
+    ref = g[f"{case}_rpn_loss"]
+    got = np.array([float(tb["rpn_loss"]), float(tb["rpn_loss_cls"]), float(tb["rpn_loss_loc"]),
+                    float(tb.get("rpn_loss_dir", torch.zeros(())))])
+    print(f"[module {case}] device {got} reference {ref}")
+    assert float(loss) == got[0] and all(v.is_cuda for v in tb.values())
+    assert set(tb) == {"rpn_loss", "rpn_loss_cls", "rpn_loss_loc"} | ({"rpn_loss_dir"} if case == "K" else set())
+    np.testing.assert_allclose(got, ref, rtol=1e-3)
+    assert all(torch.isfinite(q).all() for q in grads) and len(grads) > 4
+    assert dd["cls_preds_normalized"] is False and isinstance(dd["batch_cls_preds"], list)
+    assert [m.tolist() for m in dd["multihead_label_mapping"]] == [hd.head_label_indices.tolist() for hd in head.rpn_heads]
+    boxes, ref_boxes = dd["batch_box_preds"].cpu().numpy(), g[f"{case}_batch_box_preds"]
+    assert boxes.shape == ref_boxes.shape
+    # (the heading is left out: these weights are untrained, so atan2's argument comes near the origin in case N and a
+    #  direction bin may flip on near-equal logits in case K; test_decoding_matches_reference_fixture pins the heading)
+    np.testing.assert_allclose(np.delete(boxes, 6, axis=2), np.delete(ref_boxes, 6, axis=2), rtol=1e-3, atol=1e-3)
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_training_step_is_capturable(golden, case):
+    """forward (with box decoding) + get_loss + backward in ONE graph, replayed twice: the eager run's loss bits and the
+    bits of the gradients of every head's maps (what pcd_anchor_multi_* compute); the parameter gradients behind them come
+    from torch's own fp32 convolutions, whose weight gradients are not bit-reproducible from run to run: close."""
+    g, head, x, gt = _loaded(golden, case)
+    eager = _step(head, x, gt)
+    head.forward_ret_dict = {}               # no autograd graph of an eager step may be alive during capture
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = _step(head, x, gt)
+    for _ in range(2):
+        out[0].zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out[0], eager[0])
+        assert len(out[4]) == len(eager[4]) >= 6
+        for p, q in zip(out[4], eager[4]):
+            assert torch.equal(p, q)
+        for p, q in zip(out[2], eager[2]):
+            assert float((p - q).abs().max()) <= 1e-4 * float(q.abs().max()) + 1e-12
+
+
+def test_post_processing_matches_reference_fixture(golden):
+    """MULTI_CLASSES_NMS: the same boxes in the same order as the reference's post_processing, scores within 1e-6"""
+    g = golden("g41_anchor_multi_postproc")
+    n = len(AR.head_layout("N"))
+    head = _head("N")
+    bd = {"batch_size": g["N_batch_box_preds"].shape[0], "batch_box_preds": torch.from_numpy(g["N_batch_box_preds"]).cuda(),
+          "batch_cls_preds": [torch.from_numpy(g[f"N_batch_cls_preds{h}"]).cuda() for h in range(n)],
+          "multihead_label_mapping": [hd.head_label_indices for hd in head.rpn_heads], "cls_preds_normalized": False}
+    preds = head.post_processing(bd, AR.POST_PROCESSING)
+    assert len(preds) == bd["batch_size"]
+    for b, p in enumerate(preds):
+        labels = g[f"N_pred_labels{b}"]
+        assert labels.size > 0 and 3 not in labels                         # (class 3 has nothing above the score threshold)
+        np.testing.assert_array_equal(p["pred_labels"].cpu().numpy(), labels)
+        np.testing.assert_array_equal(p["pred_boxes"].cpu().numpy(), g[f"N_pred_boxes{b}"])
+        np.testing.assert_allclose(p["pred_scores"].cpu().numpy(), g[f"N_pred_scores{b}"], rtol=0, atol=1e-6)
+        assert p["pred_labels"].dtype == torch.int64
