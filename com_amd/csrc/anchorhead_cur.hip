@@ -9,7 +9,9 @@
 //   pcd_anchor_cur_loss_backward  (CurriculumSigmoidFocalClassificationLoss: update_score, groups_confidence, forward)
 //
 // The forward is four launches: a statistics pass over the anchor groups (only grouped positives load a prediction), a
-// one-block state update, the loss pass (anchorhead_common.h, curriculum variant) and the ordered finish.  Statistics
+// one-block state update, the loss pass (the anchor heads' core in anchorhead_common.h under its cell-major layout,
+// curriculum variant) and the ordered finish.  This file holds what only the curriculum has: the cluster, groups,
+// statistics and state kernels, and the entry points.  Statistics
 // are accumulated as 64-bit fixed point (2^-40) with integer atomics (in LDS per block, then one flush per block that
 // holds a grouped positive): exact, hence independent of the order of the adds, hence bit-identical between runs.  No [B, N, C, 97] tensor exists.  Compiled with -ffp-contract=off.
 #include "anchorhead_common.h"
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(256) void anc_cur_groups_kernel(const int *__restri
 // ---- statistics pass (update_score :150-198 sums; groups_confidence :200-214)
 __device__ __forceinline__ u64t fixed40(double v) { return (u64t)__double2ll_rn(v * 1099511627776.0); }
 
-__global__ __launch_bounds__(256) void anc_cur_stats_kernel(AncMaps m, int H, int W, int A, int num_class,
+__global__ __launch_bounds__(256) void anc_cur_stats_kernel(CellMajor lay, int dtype, int H, int W, int A,
                                                             const int *__restrict__ groups, u64t *__restrict__ accum) {
     __shared__ u64t s_acc[CUR_ACCUM];
     const int N = H * W * A;
@@ -106,11 +108,11 @@ __global__ __launch_bounds__(256) void anc_cur_stats_kernel(AncMaps m, int H, in
     if (threadIdx.x < CUR_ACCUM) s_acc[threadIdx.x] = 0;
     if (!__syncthreads_or(g > 0)) return;                                // (block-uniform: most blocks hold no grouped positive)
     if (g > 0) {
-        const int cell = n / A, k = n - cell * A;
-        const int y = cell / W, x = cell - y * W;
-        const long long off = (long long)b * m.s[0][0] + (long long)y * m.s[0][2] + (long long)x * m.s[0][3] +
-                              (long long)(k * num_class) * m.s[0][1];
-        const float p = 1.f / (1.f + expf(-load_el(m.p[0], m.dtype, off)));
+        const AncGeom q = CellMajor::geom(n, H, W, A);
+        const AncHead &m = lay.h;
+        const long long off = (long long)b * m.strides[0][0] + (long long)q.y * m.strides[0][2] +
+                              (long long)q.x * m.strides[0][3] + (long long)(q.g * m.num_class) * m.strides[0][1];
+        const float p = 1.f / (1.f + expf(-load_el(m.map[0], dtype, off)));
         const u64t fp = fixed40((double)p);
         atomicAdd(s_acc + 0, fp);                                        // integer sums: exact in any order
         atomicAdd(s_acc + 1, fixed40((double)p * (double)p));
@@ -223,8 +225,7 @@ extern "C" int pcd_anchor_cur_groups(const int *box_cls_labels, const int *gt_in
 }
 
 extern "C" size_t pcd_anchor_cur_loss_workspace_bytes(int batch, int height, int width, int n_kinds) {
-    if (!shape_ok(batch, height, width, n_kinds)) return 0;
-    return ws_piece((size_t)batch * pcd_div_up(height * width * n_kinds, 256) * 3, sizeof(float));
+    return loss_workspace_bytes(batch, height, width, n_kinds);
 }
 
 extern "C" int pcd_anchor_cur_loss_forward(const void *cls_preds, const void *box_preds, const void *dir_preds, int dtype,
@@ -237,28 +238,27 @@ extern "C" int pcd_anchor_cur_loss_forward(const void *cls_preds, const void *bo
                                            float *conf_num, float *epoch_conf, float *epoch_num, float *saved, float *out,
                                            void *workspace, size_t workspace_bytes, void *stream) {
     PCD_ENTER();
-    AncMaps m;
+    CellMajor m;
     AncLossCfg c;
     AncCurArgs a;
     AncCurState s;
-    if (!fill_maps(m, cls_preds, box_preds, dir_preds, nullptr, nullptr, nullptr, dtype, strides_host) || !box_cls_labels ||
-        !box_reg_targets || !num_pos || !kinds || !code_weights || !out || !cur_args(a, &s, cur, groups, saved) || !epoch_table ||
-        !state || !accum || !conf_sum || !conf_num || !epoch_conf || !epoch_num)
+    if (!fill_maps(m, cls_preds, box_preds, dir_preds, nullptr, nullptr, nullptr, dtype, strides_host, n_kinds, num_class) ||
+        !box_cls_labels || !box_reg_targets || !num_pos || !kinds || !code_weights || !out ||
+        !cur_args(a, &s, cur, groups, saved) || !epoch_table || !state || !accum || !conf_sum || !conf_num || !epoch_conf ||
+        !epoch_num)
         return PCD_ERR_INVALID_ARG;
     if (num_class != 1) return PCD_ERR_UNSUPPORTED;          // the reference's get_loss cannot run with more (pcd_ops.h)
-    if (!loss_cfg(c, batch, height, width, n_kinds, num_class, num_dir_bins, dir_preds != nullptr, cls_weight, loc_weight,
-                  dir_weight, dir_offset))
+    if (!loss_cfg(c, dtype, batch, height, width, n_kinds, num_class, 7, 0, num_dir_bins, dir_preds != nullptr, true, 1.f, 1.f,
+                  cls_weight, loc_weight, dir_weight, dir_offset))
         return PCD_ERR_UNSUPPORTED;
     WsCarver ws(workspace, workspace_bytes);
     dim3 grid(pcd_div_up(height * width * n_kinds, 256), batch);
     float *partials = ws.take<float>((size_t)grid.x * grid.y * 3);
     if (!ws.ok) return PCD_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    anc_cur_stats_kernel<<<grid, 256, 0, st>>>(m, height, width, n_kinds, num_class, groups, accum);
+    anc_cur_stats_kernel<<<grid, 256, 0, st>>>(m, dtype, height, width, n_kinds, groups, accum);
     anc_cur_state_kernel<<<1, 256, 0, st>>>(accum, s, epoch_table, state, conf_sum, conf_num, epoch_conf, epoch_num, saved);
-    anc_loss_kernel<false, AncCurArgs><<<grid, 256, 0, st>>>(m, c, box_cls_labels, box_reg_targets, num_pos, kinds, code_weights,
-                                                             nullptr, partials, a);
-    anc_loss_finish_kernel<<<1, 256, 0, st>>>(partials, (int)(grid.x * grid.y), c, out);
+    launch_loss_forward(m, c, grid, box_cls_labels, box_reg_targets, num_pos, kinds, code_weights, partials, out, a, st);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }
@@ -272,20 +272,20 @@ extern "C" int pcd_anchor_cur_loss_backward(const void *cls_preds, const void *b
                                             const PcdAnchorCurriculum *cur, const float *saved, const float *grad_out,
                                             void *stream) {
     PCD_ENTER();
-    AncMaps m;
+    CellMajor m;
     AncLossCfg c;
     AncCurArgs a;
-    if (!fill_maps(m, cls_preds, box_preds, dir_preds, d_cls, d_box, d_dir, dtype, strides_host) || !d_cls || !d_box ||
-        (dir_preds && !d_dir) || !box_cls_labels || !box_reg_targets || !num_pos || !kinds || !code_weights || !grad_out ||
-        !cur_args(a, nullptr, cur, groups, saved))
+    if (!fill_maps(m, cls_preds, box_preds, dir_preds, d_cls, d_box, d_dir, dtype, strides_host, n_kinds, num_class) || !d_cls ||
+        !d_box || (dir_preds && !d_dir) || !box_cls_labels || !box_reg_targets || !num_pos || !kinds || !code_weights ||
+        !grad_out || !cur_args(a, nullptr, cur, groups, saved))
         return PCD_ERR_INVALID_ARG;
     if (num_class != 1) return PCD_ERR_UNSUPPORTED;
-    if (!loss_cfg(c, batch, height, width, n_kinds, num_class, num_dir_bins, dir_preds != nullptr, cls_weight, loc_weight,
-                  dir_weight, dir_offset))
+    if (!loss_cfg(c, dtype, batch, height, width, n_kinds, num_class, 7, 0, num_dir_bins, dir_preds != nullptr, true, 1.f, 1.f,
+                  cls_weight, loc_weight, dir_weight, dir_offset))
         return PCD_ERR_UNSUPPORTED;
     dim3 grid(pcd_div_up(height * width * n_kinds, 256), batch);
-    anc_loss_kernel<true, AncCurArgs><<<grid, 256, 0, (hipStream_t)stream>>>(m, c, box_cls_labels, box_reg_targets, num_pos, kinds,
-                                                                            code_weights, grad_out, nullptr, a);
+    anc_loss_kernel<true, CellMajor, AncCurArgs><<<grid, 256, 0, (hipStream_t)stream>>>(
+        m, c, box_cls_labels, box_reg_targets, num_pos, kinds, code_weights, grad_out, nullptr, a);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }

@@ -392,13 +392,11 @@ extern "C" int pcd_point_head_loss_forward(const void *logits, int dtype, long l
     const int blocks = pcd_div_up(num_points, 256);
     float *partials = ws.take<float>((size_t)(blocks + 1) * 3);
     if (!ws.ok) return PCD_ERR_WORKSPACE;
-    AncLossCfg c = {};                                 // the anchor heads' ordered finish: sum * 1 * cls_w, no other terms
-    c.inv_batch = 1.f;
-    c.cls_w = cls_weight;
     hipStream_t st = (hipStream_t)stream;
     ph_loss_kernel<false><<<blocks, 256, 0, st>>>(logits, nullptr, dtype, row_stride, point_cls_labels, num_pos, num_points,
                                                   num_class, cls_weight, nullptr, partials);
-    anc_loss_finish_kernel<<<1, 256, 0, st>>>(partials, blocks, c, out);
+    // the anchor heads' ordered finish: sum * 1 * cls_w, no other terms
+    anc_loss_finish_kernel<<<1, 256, 0, st>>>(partials, blocks, cls_weight, 0.f, 0.f, 1.f, out);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }

@@ -165,6 +165,37 @@ class AnchorTables:
                             self.num_class, self.num_dir_bins, self.dir_offset, self.dir_limit_offset)
 
 
+def refuse_common(no, ta, loss_cfg, reg_losses):
+    """the refusals every anchor head shares; `no(key, why)` raises the head's PcdError"""
+    if _get(ta, 'NAME') != 'AxisAlignedTargetAssigner':
+        no('TARGET_ASSIGNER_CONFIG.NAME', f"= {_get(ta, 'NAME')!r}")
+    if _get(ta, 'MATCH_HEIGHT', False):
+        no('MATCH_HEIGHT', '= True')
+    if _get(ta, 'POS_FRACTION', -1.0) >= 0:
+        no('POS_FRACTION', '>= 0 (random sampling)')
+    if _get(ta, 'NORM_BY_NUM_EXAMPLES', False):
+        no('NORM_BY_NUM_EXAMPLES', '= True')
+    if _get(ta, 'BOX_CODER', 'ResidualCoder') != 'ResidualCoder':
+        no('BOX_CODER', f"= {_get(ta, 'BOX_CODER')!r}")
+    if _get(loss_cfg, 'REG_LOSS_TYPE', None) not in (None,) + tuple(reg_losses):
+        no('REG_LOSS_TYPE', f"= {_get(loss_cfg, 'REG_LOSS_TYPE')!r}")
+
+
+def cached_tables(head, device):
+    """`head._tables_host` on `device`, moved there once (the `tables` method of the anchor heads)"""
+    key = str(device)
+    if key not in head._tables:
+        head._tables[key] = head._tables_host.to(device)
+    return head._tables[key]
+
+
+def target_buffers(B, N, code, dev):
+    """(box_cls_labels, box_reg_targets, reg_weights, box_gt_index, num_pos) for the assignment kernels to fill"""
+    return (torch.empty((B, N), dtype=torch.int32, device=dev), torch.empty((B, N, code), dtype=torch.float32, device=dev),
+            torch.empty((B, N), dtype=torch.float32, device=dev), torch.empty((B, N), dtype=torch.int32, device=dev),
+            torch.empty((B,), dtype=torch.int32, device=dev))
+
+
 def assign_targets(tab, gt_boxes):
     """pcd_anchor_assign_targets: the reference's `all_targets_dict` (box_cls_labels int32 [B, N], box_reg_targets
     [B, N, 7], reg_weights [B, N]) + num_pos int32 [B] and box_gt_index int32 [B, N] (the box of each positive)."""
@@ -177,11 +208,7 @@ def assign_targets(tab, gt_boxes):
     N = tab.H * tab.W * tab.A
     dev = gt.device
     lib = L.lib()
-    labels = torch.empty((B, N), dtype=torch.int32, device=dev)
-    targets = torch.empty((B, N, 7), dtype=torch.float32, device=dev)
-    weights = torch.empty((B, N), dtype=torch.float32, device=dev)
-    gt_index = torch.empty((B, N), dtype=torch.int32, device=dev)
-    num_pos = torch.empty((B,), dtype=torch.int32, device=dev)
+    labels, targets, weights, gt_index, num_pos = target_buffers(B, N, 7, dev)
     ws = L.workspace(lib.pcd_anchor_assign_workspace_bytes(B, M), dev)
     L.check(lib.pcd_anchor_assign_targets(L.ptr(gt) if M else None, B, M, L.ptr(tab.kinds), tab.A, L.ptr(tab.classes), tab.C,
                                           L.ptr(tab.shifts), tab.H, tab.W, L.ptr(labels), L.ptr(targets), L.ptr(weights),
@@ -340,20 +367,9 @@ class AnchorHeadSingle(nn.Module):
             raise L.PcdError(f"AnchorHeadSingle: {key} {why} is not supported by the HIP anchor head")
         if _get(model_cfg, 'USE_MULTIHEAD', False):
             no('USE_MULTIHEAD', '= True')
-        if _get(ta, 'NAME') != 'AxisAlignedTargetAssigner':
-            no('TARGET_ASSIGNER_CONFIG.NAME', f"= {_get(ta, 'NAME')!r}")
-        if _get(ta, 'MATCH_HEIGHT', False):
-            no('MATCH_HEIGHT', '= True')
-        if _get(ta, 'POS_FRACTION', -1.0) >= 0:
-            no('POS_FRACTION', '>= 0 (random sampling)')
-        if _get(ta, 'NORM_BY_NUM_EXAMPLES', False):
-            no('NORM_BY_NUM_EXAMPLES', '= True')
-        if _get(ta, 'BOX_CODER', 'ResidualCoder') != 'ResidualCoder':
-            no('BOX_CODER', f"= {_get(ta, 'BOX_CODER')!r}")
+        refuse_common(no, ta, loss_cfg, ('WeightedSmoothL1Loss',))
         if (_get(ta, 'BOX_CODER_CONFIG', None) or {}).get('encode_angle_by_sincos', False):
             no('encode_angle_by_sincos', '= True')
-        if _get(loss_cfg, 'REG_LOSS_TYPE', None) not in (None, 'WeightedSmoothL1Loss'):
-            no('REG_LOSS_TYPE', f"= {_get(loss_cfg, 'REG_LOSS_TYPE')!r}")
 
     def init_weights(self):
         """anchor_head_single.py:36-39"""
@@ -361,11 +377,7 @@ class AnchorHeadSingle(nn.Module):
         nn.init.constant_(self.conv_cls.bias, -np.log((1 - pi) / pi))
         nn.init.normal_(self.conv_box.weight, mean=0, std=0.001)
 
-    def tables(self, device):
-        key = str(device)
-        if key not in self._tables:
-            self._tables[key] = self._tables_host.to(device)
-        return self._tables[key]
+    tables = cached_tables
 
     def assign_targets(self, gt_boxes):
         """anchor_head_template.py:89-100 -> axis_aligned_target_assigner.py:36-210, three launches for the batch."""

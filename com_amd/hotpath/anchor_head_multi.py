@@ -25,7 +25,7 @@ import torch.nn as nn
 from .. import _lib as L
 from .. import iou3d_nms
 from ._maps import dtype_code as _dt, like as _like
-from .anchor_head import AnchorGenerator, anchor_tables
+from .anchor_head import AnchorGenerator, anchor_tables, cached_tables, refuse_common, target_buffers
 from .dense2d import BaseBEVBackbone, BatchNormReLU2d, Conv3x3, _get
 
 KIND_FLOATS, MAX_HEADS, MAX_CODE = L.PCD_ANCHOR_MULTI_KIND_FLOATS, L.PCD_ANCHOR_MULTI_MAX_HEADS, L.PCD_ANCHOR_MULTI_MAX_CODE
@@ -125,11 +125,7 @@ def assign_targets(tab, gt_boxes):
     B, M = int(gt.shape[0]), int(gt.shape[1])
     dev = gt.device
     lib = L.lib()
-    labels = torch.empty((B, tab.N), dtype=torch.int32, device=dev)
-    targets = torch.empty((B, tab.N, tab.code), dtype=torch.float32, device=dev)
-    weights = torch.empty((B, tab.N), dtype=torch.float32, device=dev)
-    gt_index = torch.empty((B, tab.N), dtype=torch.int32, device=dev)
-    num_pos = torch.empty((B,), dtype=torch.int32, device=dev)
+    labels, targets, weights, gt_index, num_pos = target_buffers(B, tab.N, tab.code, dev)
     ws = L.workspace(lib.pcd_anchor_multi_assign_workspace_bytes(B, M), dev)
     L.check(lib.pcd_anchor_multi_assign_targets(
         L.ptr(gt) if M else None, B, M, tab.code_gt, tab.sincos, L.ptr(tab.kinds), tab.G, L.ptr(tab.classes), tab.C,
@@ -425,23 +421,12 @@ class AnchorHeadMulti(nn.Module):
             no('USE_MULTIHEAD', '= False')
         if not _get(model_cfg, 'SEPARATE_MULTIHEAD', False):
             no('SEPARATE_MULTIHEAD', '= False')
-        if _get(ta, 'NAME') != 'AxisAlignedTargetAssigner':
-            no('TARGET_ASSIGNER_CONFIG.NAME', f"= {_get(ta, 'NAME')!r}")
-        if _get(ta, 'MATCH_HEIGHT', False):
-            no('MATCH_HEIGHT', '= True')
-        if _get(ta, 'POS_FRACTION', -1.0) >= 0:
-            no('POS_FRACTION', '>= 0 (random sampling)')
-        if _get(ta, 'NORM_BY_NUM_EXAMPLES', False):
-            no('NORM_BY_NUM_EXAMPLES', '= True')
-        if _get(ta, 'BOX_CODER', 'ResidualCoder') != 'ResidualCoder':
-            no('BOX_CODER', f"= {_get(ta, 'BOX_CODER')!r}")
+        refuse_common(no, ta, loss_cfg, ('WeightedSmoothL1Loss', 'WeightedL1Loss'))
         coder = _get(ta, 'BOX_CODER_CONFIG', None) or {}
         if int(coder.get('code_size', 7)) not in (7, 9):
             no('BOX_CODER_CONFIG.code_size', f"= {coder.get('code_size')}")
         if coder.get('encode_angle_by_sincos', False) and use_dir:
             no('encode_angle_by_sincos', 'together with USE_DIRECTION_CLASSIFIER')
-        if _get(loss_cfg, 'REG_LOSS_TYPE', None) not in (None, 'WeightedSmoothL1Loss', 'WeightedL1Loss'):
-            no('REG_LOSS_TYPE', f"= {_get(loss_cfg, 'REG_LOSS_TYPE')!r}")
         if len({int(c['feature_map_stride']) for c in ag_cfg}) != 1:
             no('feature_map_stride', 'differing between anchor classes')
         if any(len(c['anchor_bottom_heights']) != 1 for c in ag_cfg):
@@ -472,11 +457,7 @@ class AnchorHeadMulti(nn.Module):
                                     separate_reg_config=_get(self.model_cfg, 'SEPARATE_REG_CONFIG', None)))
         self.rpn_heads = nn.ModuleList(heads)
 
-    def tables(self, device):
-        key = str(device)
-        if key not in self._tables:
-            self._tables[key] = self._tables_host.to(device)
-        return self._tables[key]
+    tables = cached_tables
 
     def assign_targets(self, gt_boxes):
         """anchor_head_template.py:89-100 -> axis_aligned_target_assigner.py:36-210, three launches for the batch."""
