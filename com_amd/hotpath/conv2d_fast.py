@@ -1,11 +1,11 @@
-"""nn.Conv2d(k = 3, stride 1, padding 1) on channels-last bf16 maps through the hand-written implicit-GEMM kernel
-(com_amd/csrc/conv2d.hip) instead of MIOpen: forward and data gradient are the same MFMA kernel (weights packed
-forward / transposed + rotated), the weight gradient is the sparse path's pair-wise X^T dY kernel (spconv.hip) run over
-the DENSE pair lists of the 9 taps -- built once per map shape.  `Conv3x3` is a drop-in nn.Conv2d subclass (same
-parameters and state-dict keys, base_bev_backbone.py:37-51 / center_head.py:17-24 construct it with the same arguments);
-anything the kernel does not cover (other kernel sizes / strides, CPU tensors, fp32 maps outside a bf16 autocast
-region, cin % 32 != 0) takes
-nn.Conv2d's own path."""
+"""The four dense convs of the BEV stack -- ops.DENSE_KINDS: nn.Conv2d(3, stride 1, padding 1), nn.Conv2d(3, stride 2,
+padding 1) and nn.ConvTranspose2d(k = stride in {1, 2}) -- on channels-last bf16 maps through the hand-written kernels of
+com_amd/csrc/conv2d.hip instead of MIOpen: forward and data gradient are the same MFMA kernel family (weights packed with the
+kind's forward mode / the next odd one), the weight gradient is the dense 3x3 kernel or the sparse path's pair-wise X^T dY
+kernel (spconv.hip) run over the DENSE pair lists of the kind's taps -- built once per map shape.  `Conv3x3`, `Conv3x3S2` and
+`UpConvT` are drop-in subclasses (same parameters and state-dict keys, base_bev_backbone.py:37-62 / center_head.py:17-24
+construct them with the same arguments); anything the kernels do not cover (`_covered`: other kernel sizes / strides,
+cin % 32 != 0, ...; `_fast`: CPU tensors, fp32 maps outside a bf16 autocast region) takes torch's own path."""
 import torch
 import torch.nn as nn
 
@@ -17,87 +17,133 @@ ENABLED = True
 # whenever spconv.functional.FUSE_BN_REDUCTIONS holds.  Measured in the full step (2 x 80 replays): off 7.84, forward
 # 7.79 ms.  The backward reductions on the data-gradient launch (mode 2) were retired: they re-read the BatchNorm's input
 # and output tile in that epilogue and lost, 7.89 ms alone and 7.86 with the forward form.
+BATCH_BN_COUNTERS = True
 _PAIRS = {}
 
 
-def _dense_pairs(B, H, W, device):
-    """indice_pairs of a dense 3x3 / stride 1 / padding 1 conv over [B, H, W] pixels (row = (b * H + y) * W + x):
-    pairs [9, 2, n] (input row, output row; ascending), pair_num [9]."""
-    key = (B, H, W, str(device))
+def pair_lists(mode, B, H, W, device):
+    """indice_pairs for the WEIGHT gradient of the dense kind `mode` on a [B, H, W] input map, in the (gathered row,
+    accumulated row) convention of the sparse pair kernels, built once per map shape: the pairs of the ordinary convolution
+    (k, s, p) from the kind's fine map [fh, fw] to its coarse one -- tap t = ty * k + tx pairs the fine pixel
+    (s oy + ty - p, s ox + tx - p) with the coarse pixel (oy, ox); row = (b * height + y) * width + x.  For a conv the fine
+    map is x and dW comes out as [cout, K, cin]; for a transposed conv it is dy, the kernel runs with the roles of x / dy
+    swapped and dW comes out as [cin, K, cout], the parameter's own layout.  Returns pairs [K, 2, n] (valid ones first,
+    ascending; -1 behind) and pair_num [K]."""
+    key = (mode, B, H, W, str(device))
     hit = _PAIRS.get(key)
     if hit is not None:
         return hit
-    n = B * H * W
-    p = torch.arange(n, device=device, dtype=torch.int64)
-    y, x = (p // W) % H, p % W
-    pairs = torch.full((9, 2, n), -1, dtype=torch.int32, device=device)
-    num = torch.zeros((9,), dtype=torch.int32, device=device)
-    for k in range(9):
-        dy, dx = k // 3 - 1, k % 3 - 1
-        ok = (y + dy >= 0) & (y + dy < H) & (x + dx >= 0) & (x + dx < W)
-        out_rows = p[ok]
-        m = out_rows.numel()
-        pairs[k, 0, :m] = (out_rows + dy * W + dx).int()
-        pairs[k, 1, :m] = out_rows.int()
-        num[k] = m
+    kind = ops.DENSE_KINDS[mode]
+    k, s, p = kind.k, kind.stride, kind.pad
+    fh, fw = kind.fine_hw(H, W)
+    ch, cw = (fh + 2 * p - k) // s + 1, (fw + 2 * p - k) // s + 1
+    n = B * ch * cw
+    o = torch.arange(n, device=device, dtype=torch.int64)
+    b, oy, ox = o // (ch * cw), (o // cw) % ch, o % cw
+    pairs = torch.full((k * k, 2, n), -1, dtype=torch.int32, device=device)
+    num = torch.zeros((k * k,), dtype=torch.int32, device=device)
+    for t in range(k * k):
+        fy, fx = s * oy + t // k - p, s * ox + t % k - p
+        ok = (fy >= 0) & (fy < fh) & (fx >= 0) & (fx < fw)
+        m = int(ok.sum())
+        pairs[t, 0, :m] = ((b * fh + fy) * fw + fx)[ok].int()
+        pairs[t, 1, :m] = o[ok].int()
+        num[t] = m
     _PAIRS[key] = (pairs, num)
     return pairs, num
+
+
+def _dense_pairs(B, H, W, device):
+    """The pair lists of the 3x3 / stride 1 / padding 1 conv (kind 0)."""
+    return pair_lists(0, B, H, W, device)
 
 
 def _pad32(c):
     return (c + 31) // 32 * 32
 
 
-BATCH_BN_COUNTERS = True
+def _bf16_region(x):
+    return x.is_cuda and (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled()
+                                                        and torch.get_autocast_dtype('cuda') == torch.bfloat16))
 
 
-def _plane_pairs(mode_f, B, hi, wi, device):
-    """Dense pair lists for the WEIGHT gradients of the plane operators (conv2d.hip, pack modes 2 / 4 / 6), in the
-    (gathered row, accumulated row) convention of the sparse pair kernels, built once per map shape:
-      mode 2  Conv2d(3, stride 2, padding 1): tap k = ky * 3 + kx pairs the fine INPUT pixel (2 oy + ky - 1, 2 ox + kx - 1)
-              with the coarse output pixel (oy, ox) -> dW [cout, 9, cin]
-      mode 4  ConvTranspose2d(2, stride 2): tap k = a * 2 + b pairs the fine OUTPUT pixel (2 y + a, 2 x + b) with the coarse
-              input pixel (y, x); the kernel runs with the roles of x / dy swapped so that dW comes out as [cin, 4, cout],
-              i.e. in the parameter's own [cin, cout, 2, 2] layout after the conv2d_layout reduction
-      mode 6  ConvTranspose2d(1, stride 1): identity pairs.
-    (hi, wi) = size of the layer's INPUT map.  Returns pairs [K, 2, n], pair_num [K]."""
-    key = ("planes", mode_f, B, hi, wi, str(device))
-    hit = _PAIRS.get(key)
-    if hit is not None:
-        return hit
-    if mode_f == 2:
-        ho, wo = (hi - 1) // 2 + 1, (wi - 1) // 2 + 1
-        n = B * ho * wo
-        p = torch.arange(n, device=device, dtype=torch.int64)
-        b, oy, ox = p // (ho * wo), (p // wo) % ho, p % wo
-        pairs = torch.full((9, 2, n), -1, dtype=torch.int32, device=device)
-        num = torch.zeros((9,), dtype=torch.int32, device=device)
-        for k in range(9):
-            fy, fx = 2 * oy + k // 3 - 1, 2 * ox + k % 3 - 1
-            ok = (fy >= 0) & (fy < hi) & (fx >= 0) & (fx < wi)
-            m = int(ok.sum())
-            pairs[k, 0, :m] = ((b * hi + fy) * wi + fx)[ok].int()
-            pairs[k, 1, :m] = p[ok].int()
-            num[k] = m
-    elif mode_f == 4:
-        n = B * hi * wi
-        p = torch.arange(n, device=device, dtype=torch.int64)
-        b, y, x = p // (hi * wi), (p // wi) % hi, p % wi
-        pairs = torch.empty((4, 2, n), dtype=torch.int32, device=device)
-        for k in range(4):
-            pairs[k, 0] = ((b * 2 * hi + 2 * y + k // 2) * (2 * wi) + 2 * x + k % 2).int()
-            pairs[k, 1] = p.int()
-        num = torch.full((4,), n, dtype=torch.int32, device=device)
-    else:
-        n = B * hi * wi
-        p = torch.arange(n, device=device, dtype=torch.int32)
-        pairs = torch.stack([p, p]).reshape(1, 2, n).contiguous()
-        num = torch.full((1,), n, dtype=torch.int32, device=device)
-    _PAIRS[key] = (pairs, num)
-    return pairs, num
+def dense_input(x):
+    """x as the kernels read it -- bf16, channels-last storage -- or None for a map they do not take: off the device, or
+    fp32 outside a bf16 autocast region."""
+    if not _bf16_region(x):
+        return None
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        x = x.contiguous(memory_format=torch.channels_last)
+    return x
 
 
-class _PacksAhead:
+def _grad_nhwc(dy, cp):
+    """dy [B, cout, H, W] as the backward kernels read it: [B, H, W, cp] bf16 contiguous, zero-padded to cp channels."""
+    dyn = dy.permute(0, 2, 3, 1)
+    if dyn.dtype != torch.bfloat16:
+        dyn = dyn.to(torch.bfloat16)
+    if cp != dyn.shape[3]:
+        dyn = torch.nn.functional.pad(dyn, (0, cp - dyn.shape[3]))
+    return dyn.contiguous()
+
+
+def _wgrad_3x3(x, dyp, weight, wp, direct, jobs, x_block=False):
+    """dW of ONE 3x3 / stride 1 conv: x [B, H, W, cin] bf16 (x_block: a channel block of a wider map), dyp [B, H, W, cp] its
+    output gradient with zero-padded channels.  direct: into wp.grad (slab reduction deferred to `jobs`; only the real rows
+    of the slabs are reduced), returns None; otherwise returns a tensor in the parameter's layout and dtype."""
+    B, H, W, cin = x.shape
+    cout, cp = weight.shape[0], dyp.shape[3]
+    if ops.conv2d_wgrad_splits(B, H, W, cin, cp) > 0:              # the dense kernel (no pair lists)
+        if direct:
+            ops.conv2d_wgrad(x, dyp, cout, out=wp.grad, defer=jobs)
+            return None
+        return ops.conv2d_wgrad(x, dyp, cout).to(weight.dtype)
+    pairs, num = _dense_pairs(B, H, W, x.device)
+    rows = x.view(-1, cin)                                          # (a channel block stays one: row stride of the wide map)
+    if direct:
+        ops.wgrad(rows, cin, dyp.reshape(-1, cp), pairs, num, 9, out=wp.grad, defer=jobs, conv2d_layout=True,
+                  cout_write=cout if cp != cout else 0, x_block=x_block)
+        return None
+    dwk = ops.wgrad(rows, cin, dyp.reshape(-1, cp), pairs, num, 9, x_block=x_block)      # [cp, 9, cin] f32
+    return dwk[:cout].permute(0, 2, 1).reshape(cout, cin, 3, 3).to(weight.dtype)
+
+
+def _bias_grad(dyp, cout, bp, direct):
+    """Column sums of dyp [B, H, W, cp] (fp32, fixed order), the first cout of them: into bp.grad (direct) or returned."""
+    cp = dyp.shape[3]
+    if direct and cp == cout:
+        ops.col_sum(dyp.reshape(-1, cp), out=bp.grad)
+        return None
+    cs = ops.col_sum(dyp.reshape(-1, cp))[:cout]
+    if direct:
+        bp.grad.copy_(cs)
+        return None
+    return cs
+
+
+class _DenseConv:
+    """What Conv3x3, Conv3x3S2 and UpConvT share: the covering predicate and the packs made ahead."""
+    KINDS = ()           # forward pack modes of the kinds the class can stand for
+
+    def _covered(self):
+        """The forward pack mode of the dense kind whose kernels cover this module, or None -- by the module alone: what
+        `_fast` asks of it and what Conv3x3Packs plans by."""
+        for mode in self.KINDS:
+            kind = ops.DENSE_KINDS[mode]
+            if (self.kernel_size == (kind.k, kind.k) and self.stride == (kind.stride, kind.stride)
+                    and self.padding == (kind.pad, kind.pad) and self.output_padding == (0, 0) and self.dilation == (1, 1)
+                    and self.groups == 1 and self.padding_mode == 'zeros' and (kind.bias or self.bias is None)
+                    and self.in_channels % 32 == 0 and (kind.any_cout or self.out_channels % 32 == 0)):
+                return mode
+        return None
+
+    def _fast(self, x):
+        return (ENABLED and _bf16_region(x) and x.dim() == 4 and (mode := self._covered()) is not None
+                and x.shape[0] * x.shape[2] * x.shape[3] * ops.DENSE_KINDS[mode].span
+                * max(self.in_channels, _pad32(self.out_channels)) * 2 < 2 ** 32 - 4096)
+
     def _take_packs(self):
         """(pack_f, pack_d) made ahead by Conv3x3Packs.run() since the last weight update, or (None, None)."""
         pf = pd = None
@@ -143,90 +189,34 @@ class _Conv3x3Function(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         xn, weight, pack_d = ctx.saved_tensors
-        B, H, W, cin = xn.shape
-        cout, cp = ctx.cout, _pad32(ctx.cout)
-        dyn = dy.permute(0, 2, 3, 1)
-        if dyn.dtype != torch.bfloat16:
-            dyn = dyn.to(torch.bfloat16)
-        if cp != cout:
-            dyn = torch.nn.functional.pad(dyn, (0, cp - cout))
-        dyn = dyn.contiguous()
-        want_w = ctx.needs_input_grad[1]
-        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        cin, cout = xn.shape[3], ctx.cout
+        dyn = _grad_nhwc(dy, _pad32(cout))
         wp, bp = ctx.weight_param, ctx.bias_param
 
         def dgrad():
             pd = pack_d if pack_d is not None else ops.conv2d_pack_weight(weight, 1)
             return ops.conv2d_3x3_nhwc(dyn, pd, cin).permute(0, 3, 1, 2)
 
-        def wgrad(direct, jobs):
-            if ops.conv2d_wgrad_splits(B, H, W, cin, cp) > 0:      # the dense kernel (no pair lists)
-                if direct:
-                    ops.conv2d_wgrad(xn, dyn, cout, out=wp.grad, defer=jobs)
-                    return None
-                return ops.conv2d_wgrad(xn, dyn, cout).to(weight.dtype)
-            pairs, num = _dense_pairs(B, H, W, xn.device)
-            if direct:   # (zero-padded output channels: only the real rows of the slabs are reduced into .grad)
-                ops.wgrad(xn.reshape(-1, cin), cin, dyn.reshape(-1, cp), pairs, num, 9, out=wp.grad,
-                          defer=jobs, conv2d_layout=True, cout_write=cout if cp != cout else 0)
-                return None
-            dwk = ops.wgrad(xn.reshape(-1, cin), cin, dyn.reshape(-1, cp), pairs, num, 9)  # [cp, 9, cin] f32
-            return dwk[:cout].permute(0, 2, 1).reshape(cout, cin, 3, 3).to(weight.dtype)
-
-        def bsum(direct, jobs):
-            if direct and cp == cout:
-                ops.col_sum(dyn.reshape(-1, cp), out=bp.grad)
-                return None
-            if direct:
-                bp.grad.copy_(ops.col_sum(dyn.reshape(-1, cp))[:cout])
-                return None
-            return ops.col_sum(dyn.reshape(-1, cp))[:cout]   # fp32 column sums in a fixed order
-
-        dx, dw, db = Fsp.scheduled_backward(ctx.needs_input_grad[0], want_w, want_b, wp, bp, dgrad, wgrad, bsum,
-                                            [xn, dyn])
+        dx, dw, db = Fsp.scheduled_backward(
+            ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2], wp, bp, dgrad,
+            lambda direct, jobs: _wgrad_3x3(xn, dyn, weight, wp, direct, jobs),
+            lambda direct, jobs: _bias_grad(dyn, cout, bp, direct), [xn, dyn])
         return dx, dw, db, None, None, None
 
-
-class Conv3x3(_PacksAhead, nn.Conv2d):
-    """nn.Conv2d whose forward takes the HIP kernel when it applies (see the module docstring)."""
-
-    def _fast(self, x):
-        bf16 = x.dtype == torch.bfloat16 or (torch.is_autocast_enabled()
-                                             and torch.get_autocast_dtype('cuda') == torch.bfloat16)
-        return (ENABLED and bf16 and x.is_cuda and x.dim() == 4 and self.kernel_size == (3, 3) and self.stride == (1, 1)
-                and self.padding == (1, 1) and self.dilation == (1, 1) and self.groups == 1
-                and self.padding_mode == 'zeros' and self.in_channels % 32 == 0
-                and x.shape[0] * x.shape[2] * x.shape[3] * max(self.in_channels, _pad32(self.out_channels)) * 2
-                < 2 ** 32 - 4096)
-
-    bn_follows = False   # set by the owner when a BatchNormReLU2d consumes the output (dense2d.py)
-
-    def forward(self, x):
-        if not self._fast(x):
-            return super().forward(x)
-        if x.dtype != torch.bfloat16:
-            x = x.to(torch.bfloat16)
-        if not x.is_contiguous(memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
-        pf, pd = self._take_packs()
-        follows = bool(self.bn_follows and self.training and torch.is_grad_enabled())
-        return _Conv3x3Function.apply(x, self.weight, self.bias, pf, pd, follows)
 
 class _ConvPlanesFunction(torch.autograd.Function):
     """The stride-2 3x3 conv (mode 2) and the k = stride transposed convs (modes 4, 6) of BaseBEVBackbone through the
     plane kernels of conv2d.hip; the data gradient is the same kernel family with the next odd pack mode, the weight
-    gradient the sparse pair kernels over dense pair lists (_plane_pairs).  No bias (base_bev_backbone.py:38,58,66)."""
+    gradient the sparse pair kernels over dense pair lists (pair_lists).  No bias (base_bev_backbone.py:38,58,66)."""
 
     @staticmethod
     def forward(ctx, x, weight, pack_f, pack_d, mode_f):
         xn = x.detach().permute(0, 2, 3, 1)
         assert xn.is_contiguous()
-        B, H, W, _ = xn.shape
-        _, cout = ops.conv2d_layer_channels(weight, mode_f)
-        out_hw = ((H - 1) // 2 + 1, (W - 1) // 2 + 1) if mode_f == 2 else ((2 * H, 2 * W) if mode_f == 4 else (H, W))
+        kind = ops.DENSE_KINDS[mode_f]
         if pack_f is None:
             pack_f = ops.conv2d_pack_weight(weight, mode_f)
-        y = ops.conv2d_planes_nhwc(mode_f, xn, pack_f, cout, out_hw)
+        y = ops.conv2d_planes_nhwc(mode_f, xn, pack_f, kind.channels(weight)[1], kind.out_hw(xn.shape[1], xn.shape[2]))
         ctx.save_for_backward(xn, weight, pack_d)
         ctx.mode_f = mode_f
         ctx.weight_param = weight if isinstance(weight, nn.Parameter) else None
@@ -236,88 +226,69 @@ class _ConvPlanesFunction(torch.autograd.Function):
     def backward(ctx, dy):
         xn, weight, pack_d = ctx.saved_tensors
         mode_f = ctx.mode_f
+        kind = ops.DENSE_KINDS[mode_f]
         B, H, W, cin = xn.shape
-        _, cout = ops.conv2d_layer_channels(weight, mode_f)
-        dyn = dy.permute(0, 2, 3, 1)
-        if dyn.dtype != torch.bfloat16:
-            dyn = dyn.to(torch.bfloat16)
-        dyn = dyn.contiguous()
+        cout = kind.channels(weight)[1]
+        dyn = _grad_nhwc(dy, cout)
         wp = ctx.weight_param
-        kk = {2: 9, 4: 4, 6: 1}[mode_f]
 
         def dgrad():
             pd = pack_d if pack_d is not None else ops.conv2d_pack_weight(weight, mode_f + 1)
             return ops.conv2d_planes_nhwc(mode_f + 1, dyn, pd, cin, (H, W)).permute(0, 3, 1, 2)
 
         def wgrad(direct, jobs):
-            pairs, num = _plane_pairs(mode_f, B, H, W, xn.device)
-            if mode_f == 2:       # gathered rows = x (contraction c = cin), accumulated rows = dy (o = cout)
-                a, ca, b_, cb = xn.reshape(-1, cin), cin, dyn.reshape(-1, cout), cout
-            else:                 # transposed convs: roles swapped -> dW [cin, K, cout] = the parameter's layout
-                a, ca, b_, cb = dyn.reshape(-1, cout), cout, xn.reshape(-1, cin), cin
+            pairs, num = pair_lists(mode_f, B, H, W, xn.device)
+            # gathered rows (contraction c) = the fine map, accumulated rows (o) = the coarse one: x and dy for a conv, swapped
+            # for a transposed conv -> dW [o, K, c] = the parameter's layout either way
+            a, ca, b_, cb = xn.reshape(-1, cin), cin, dyn.reshape(-1, cout), cout
+            if kind.transposed:
+                a, ca, b_, cb = b_, cb, a, ca
             if direct:
-                ops.wgrad(a, ca, b_, pairs, num, kk, out=wp.grad, defer=jobs, conv2d_layout=True)
+                ops.wgrad(a, ca, b_, pairs, num, kind.taps, out=wp.grad, defer=jobs, conv2d_layout=True)
                 return None
-            dwk = ops.wgrad(a, ca, b_, pairs, num, kk)                    # [cb, K, ca] f32
-            k = int(round(kk ** 0.5))
-            return dwk.permute(0, 2, 1).reshape(cb, ca, k, k).to(weight.dtype)
+            dwk = ops.wgrad(a, ca, b_, pairs, num, kind.taps)             # [cb, K, ca] f32
+            return dwk.permute(0, 2, 1).reshape(cb, ca, kind.k, kind.k).to(weight.dtype)
 
         dx, dw, _ = Fsp.scheduled_backward(ctx.needs_input_grad[0], ctx.needs_input_grad[1], False, wp, None, dgrad,
                                            wgrad, None, [xn, dyn])
         return dx, dw, None, None, None
 
 
-def _plane_input(x):
-    if x.dtype != torch.bfloat16:
-        x = x.to(torch.bfloat16)
-    if not x.is_contiguous(memory_format=torch.channels_last):
-        x = x.contiguous(memory_format=torch.channels_last)
-    return x
-
-
-def _bf16_region(x):
-    return x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16)
-
-
-class Conv3x3S2(_PacksAhead, nn.Conv2d):
-    """nn.Conv2d(k = 3, stride 2, padding 1, bias=False) -- the conv that opens a down-sampling block
-    (base_bev_backbone.py:36-41: ZeroPad2d(1) + Conv2d(padding=0), the same arithmetic) -- through the plane kernels."""
-    MODE_F = 2
-
-    def _fast(self, x):
-        return (ENABLED and _bf16_region(x) and x.is_cuda and x.dim() == 4 and self.kernel_size == (3, 3)
-                and self.stride == (2, 2) and self.padding == (1, 1) and self.dilation == (1, 1) and self.groups == 1
-                and self.padding_mode == 'zeros' and self.bias is None and self.in_channels % 32 == 0
-                and self.out_channels % 32 == 0
-                and x.shape[0] * x.shape[2] * x.shape[3] * max(self.in_channels, self.out_channels) * 2 < 2 ** 32 - 4096)
+class Conv3x3(_DenseConv, nn.Conv2d):
+    """nn.Conv2d whose forward takes the HIP kernel when it applies (see the module docstring)."""
+    KINDS = (0,)
+    bn_follows = False   # set by the owner when a BatchNormReLU2d consumes the output (dense2d.py)
 
     def forward(self, x):
         if not self._fast(x):
             return super().forward(x)
         pf, pd = self._take_packs()
-        return _ConvPlanesFunction.apply(_plane_input(x), self.weight, pf, pd, 2)
+        follows = bool(self.bn_follows and self.training and torch.is_grad_enabled())
+        return _Conv3x3Function.apply(dense_input(x), self.weight, self.bias, pf, pd, follows)
 
 
-class UpConvT(_PacksAhead, nn.ConvTranspose2d):
+class Conv3x3S2(_DenseConv, nn.Conv2d):
+    """nn.Conv2d(k = 3, stride 2, padding 1, bias=False) -- the conv that opens a down-sampling block
+    (base_bev_backbone.py:36-41: ZeroPad2d(1) + Conv2d(padding=0), the same arithmetic) -- through the plane kernels."""
+    KINDS = (2,)
+
+    def forward(self, x):
+        if not self._fast(x):
+            return super().forward(x)
+        pf, pd = self._take_packs()
+        return _ConvPlanesFunction.apply(dense_input(x), self.weight, pf, pd, self.KINDS[0])
+
+
+class UpConvT(_DenseConv, nn.ConvTranspose2d):
     """nn.ConvTranspose2d(k = stride in {1, 2}, bias=False) -- the deblocks (base_bev_backbone.py:55-62) -- through the
     plane kernels (k = 2: four 1-tap planes written with stride 2, no intermediate + pixel shuffle pass)."""
-
-    @property
-    def MODE_F(self):
-        return 4 if self.kernel_size == (2, 2) else 6
-
-    def _fast(self, x):
-        return (ENABLED and _bf16_region(x) and x.is_cuda and x.dim() == 4 and self.kernel_size in ((1, 1), (2, 2))
-                and self.stride == self.kernel_size and self.padding == (0, 0) and self.output_padding == (0, 0)
-                and self.dilation == (1, 1) and self.groups == 1 and self.bias is None
-                and self.in_channels % 32 == 0 and self.out_channels % 32 == 0
-                and x.shape[0] * x.shape[2] * x.shape[3] * 4 * max(self.in_channels, self.out_channels) * 2 < 2 ** 32 - 4096)
+    KINDS = (4, 6)
 
     def forward(self, x, output_size=None):
         if output_size is not None or not self._fast(x):
             return super().forward(x, output_size)
         pf, pd = self._take_packs()
-        return _ConvPlanesFunction.apply(_plane_input(x), self.weight, pf, pd, self.MODE_F)
+        return _ConvPlanesFunction.apply(dense_input(x), self.weight, pf, pd, self._covered())
 
 
 class _BranchConvsFunction(torch.autograd.Function):
@@ -379,46 +350,12 @@ class _BranchConvsFunction(torch.autograd.Function):
             return da.permute(0, 3, 1, 2)
 
         def wgrad(direct, jobs):
-            pairs, num = _dense_pairs(B, H, W, an.device)
-            a2 = an.reshape(-1, C)
-            res = []
-            for i in range(n):
-                if dys[i] is None or not ctx.needs_input_grad[3 + 2 * i]:
-                    res.append(None)
-                    continue
-                cout = ws[i].shape[0]
-                if ops.conv2d_wgrad_splits(B, H, W, width, cps[i]) > 0:
-                    xblk = an[..., width * i:width * (i + 1)]
-                    if direct:
-                        ops.conv2d_wgrad(xblk, dyp[i], cout, out=ctx.w_params[i].grad, defer=jobs)
-                        res.append(None)
-                    else:
-                        res.append(ops.conv2d_wgrad(xblk, dyp[i], cout).to(ws[i].dtype))
-                    continue
-                xb = a2[:, width * i:width * (i + 1)]
-                if direct:
-                    ops.wgrad(xb, width, dyp[i].reshape(-1, cps[i]), pairs, num, 9, out=ctx.w_params[i].grad,
-                              defer=jobs, conv2d_layout=True, cout_write=cout if cps[i] != cout else 0,
-                              x_block=True)
-                    res.append(None)
-                else:
-                    dwk = ops.wgrad(xb, width, dyp[i].reshape(-1, cps[i]), pairs, num, 9, x_block=True)
-                    res.append(dwk[:cout].permute(0, 2, 1).reshape(cout, width, 3, 3).to(ws[i].dtype))
-            return res
+            return [_wgrad_3x3(an[..., width * i:width * (i + 1)], dyp[i], ws[i], ctx.w_params[i], direct, jobs, x_block=True)
+                    if dys[i] is not None and ctx.needs_input_grad[3 + 2 * i] else None for i in range(n)]
 
         def bsum(direct, jobs):
-            res = []
-            for i in range(n):
-                if dys[i] is None or not (ctx.has_bias[i] and ctx.needs_input_grad[4 + 2 * i]):
-                    res.append(None)
-                    continue
-                cs = ops.col_sum(dyp[i].reshape(-1, cps[i]))[:ws[i].shape[0]]
-                if direct:
-                    ctx.b_params[i].grad.copy_(cs)
-                    res.append(None)
-                else:
-                    res.append(cs)
-            return res
+            return [_bias_grad(dyp[i], ws[i].shape[0], ctx.b_params[i], direct)
+                    if dys[i] is not None and ctx.has_bias[i] and ctx.needs_input_grad[4 + 2 * i] else None for i in range(n)]
 
         wps = [ctx.w_params[i] for i in live if ctx.needs_input_grad[3 + 2 * i]]
         bps = [ctx.b_params[i] for i in live if ctx.has_bias[i] and ctx.needs_input_grad[4 + 2 * i]]
@@ -432,9 +369,10 @@ class _BranchConvsFunction(torch.autograd.Function):
 
 
 class Conv3x3Packs:
-    """Forward + data-gradient packs of all Conv3x3 modules of a model in ONE launch (pcd_conv2d_pack_weights_batched)
-    into persistent buffers -- call `run()` right after every optimizer step (the weights do not change again before
-    the next forward; 2 x 22 small pack launches otherwise sit in front of the convs of the CenterPoint BEV stack).
+    """Forward + data-gradient packs of all Conv3x3 / Conv3x3S2 / UpConvT modules of a model that the kernels cover
+    (`_covered`) in ONE launch (pcd_conv2d_pack_weights_batched) into persistent buffers -- call `run()` right after every
+    optimizer step (the weights do not change again before the next forward; 2 x 22 small pack launches otherwise sit in
+    front of the convs of the CenterPoint BEV stack).
     A module uses the packs for exactly one forward / backward and packs by itself again afterwards, so a forgotten
     `run()` costs time, never correctness; packs made BEFORE a torch-visible in-place change of the weight
     (load_state_dict, checkpoint restore, dist.broadcast, manual edits: all bump `weight._version`) are dropped."""
@@ -448,17 +386,9 @@ class Conv3x3Packs:
             if callable(hook):
                 extra += list(hook())
         for m in list(model.modules()) + extra:
-            if not (hasattr(m, "weight") and m.weight is not None and m.weight.is_cuda and m.weight.dtype == torch.float32):
-                continue
-            if isinstance(m, Conv3x3) and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1) \
-                    and m.in_channels % 32 == 0:
-                self.convs.append(m), self.modes.append((0, 1))
-            elif isinstance(m, Conv3x3S2) and m.stride == (2, 2) and m.padding == (1, 1) and m.bias is None \
-                    and m.in_channels % 32 == 0 and m.out_channels % 32 == 0:
-                self.convs.append(m), self.modes.append((2, 3))
-            elif isinstance(m, UpConvT) and m.kernel_size in ((1, 1), (2, 2)) and m.stride == m.kernel_size \
-                    and m.bias is None and m.in_channels % 32 == 0 and m.out_channels % 32 == 0:
-                self.convs.append(m), self.modes.append((m.MODE_F, m.MODE_F + 1))
+            mode = m._covered() if isinstance(m, _DenseConv) else None
+            if mode is not None and m.weight.is_cuda and m.weight.dtype == torch.float32:
+                self.convs.append(m), self.modes.append((mode, mode + 1))
         rows, first, self.bufs = [], 0, []
         lib = L.lib()
         for m, modes in zip(self.convs, self.modes):

@@ -264,15 +264,13 @@ class SeparateHead(nn.Module):
         return [wm[0]] if wm is not None else []
 
     def forward(self, x):
-        wm = None
-        if x.is_cuda and (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled()
-                                                        and torch.get_autocast_dtype('cuda') == torch.bfloat16)):
-            wm = self._wide_modules()
+        xf = conv2d_fast.dense_input(x)
+        wm = self._wide_modules() if xf is not None else None
         if wm is None:
             return {name: self.__getattr__(name)(x) for name in self.sep_head_dict}
         names, seqs = self._branches()
         conv, bn = wm
-        a = bn(conv(x))                                        # [B, n C, H, W], all branches' first stage
+        a = bn(conv(xf))                                       # [B, n C, H, W], all branches' first stage
         metas, wb = [], []
         for q in seqs:
             metas.append(q[1]._take_packs())

@@ -1413,16 +1413,45 @@ class LinearFunctionalLoss(torch.autograd.Function):
         return gx, None
 
 
-PLANE_MODES = {  # pack mode -> (parameter layout, kernel size): see pcd_conv2d_planes_nhwc
-    2: ("conv", 3), 3: ("conv", 3), 4: ("convT", 2), 5: ("convT", 2), 6: ("convT", 1), 7: ("convT", 1)}
+class DenseKind(collections.namedtuple("DenseKind", "k stride pad transposed bias any_cout")):
+    """One operator of the dense BEV stack (conv2d.hip): kernel size, stride and padding of the nn.Conv2d / nn.ConvTranspose2d it
+    stands for, whether the kernels add a bias, and whether an output channel count that is no multiple of 32 runs (zero-padded)."""
+
+    @property
+    def taps(self):
+        return self.k * self.k
+
+    def channels(self, weight):
+        """(cin, cout) of the LAYER a weight belongs to (nn.Conv2d: [cout, cin, k, k]; nn.ConvTranspose2d: [cin, cout, k, k])."""
+        return (weight.shape[0], weight.shape[1]) if self.transposed else (weight.shape[1], weight.shape[0])
+
+    def out_hw(self, h, w):
+        if self.transposed:
+            return (h - 1) * self.stride - 2 * self.pad + self.k, (w - 1) * self.stride - 2 * self.pad + self.k
+        return (h + 2 * self.pad - self.k) // self.stride + 1, (w + 2 * self.pad - self.k) // self.stride + 1
+
+    def fine_hw(self, h, w):
+        """The finer of a layer's two maps ((h, w) = its input): the weight gradient's pair lists are those of the ordinary
+        convolution (k, stride, pad) from this map to the coarser one."""
+        return self.out_hw(h, w) if self.transposed else (h, w)
+
+    @property
+    def span(self):
+        """pixels of the larger map per pixel of the input, as the 32-bit offset bound counts them (4 for both transposed
+        kinds: the 1x1 one keeps the bound it always had)"""
+        return 4 if self.transposed else 1
 
 
-def conv2d_layer_channels(weight, mode):
-    """(cin, cout) of the LAYER a conv / transposed-conv weight belongs to (nn.Conv2d: [cout, cin, k, k];
-    nn.ConvTranspose2d: [cin, cout, k, k])."""
-    if mode >= 2 and PLANE_MODES[mode][0] == "convT":
-        return weight.shape[0], weight.shape[1]
-    return weight.shape[1], weight.shape[0]
+# forward pack mode -> kind; the data gradient packs with the next odd mode (pcd_conv2d_pack_weight, pcd_conv2d_planes_nhwc)
+DENSE_KINDS = {0: DenseKind(3, 1, 1, False, bias=True, any_cout=True),       # conv2d_3x3_nhwc
+               2: DenseKind(3, 2, 1, False, bias=False, any_cout=False),     # conv2d_planes_nhwc, as 4 and 6
+               4: DenseKind(2, 2, 0, True, bias=False, any_cout=False),
+               6: DenseKind(1, 1, 0, True, bias=False, any_cout=False)}
+
+
+def dense_kind(mode):
+    """The kind a pack mode (forward or data gradient) belongs to."""
+    return DENSE_KINDS[mode & ~1]
 
 
 def conv2d_pack_weight(weight, mode=0):
@@ -1431,9 +1460,9 @@ def conv2d_pack_weight(weight, mode=0):
     transposed convs of the plane kernels (conv2d_planes_nhwc)."""
     _require_cuda(weight)
     w = weight.detach().float().contiguous()
-    cin, cout = conv2d_layer_channels(w, mode)
-    k = PLANE_MODES[mode][1] if mode >= 2 else 3
-    assert tuple(w.shape[2:]) == (k, k)
+    kind = dense_kind(mode)
+    cin, cout = kind.channels(w)
+    assert tuple(w.shape[2:]) == (kind.k, kind.k)
     nbytes = L.lib().pcd_conv2d_packed_weight_bytes(cin, cout, mode)
     packed = torch.empty((nbytes // 2,), dtype=torch.bfloat16, device=w.device)
     L.check(L.lib().pcd_conv2d_pack_weight(L.ptr(w), cin, cout, mode, L.ptr(packed), L.stream_ptr()),
@@ -1522,7 +1551,7 @@ def conv2d_planes_nhwc(mode, x, packed_w, cout, out_hw, bias=None):
     ho, wo = out_hw
     y = torch.empty((B, ho, wo, cout), dtype=torch.bfloat16, device=x.device)
     b = bias.detach().float().contiguous() if bias is not None else None
-    taps = {2: 9, 3: 9, 4: 4, 5: 4, 6: 1, 7: 1}[mode]
+    taps = dense_kind(mode).taps
     coarse = B * min(hi, ho) * min(wi, wo)
     with _Timed(f"conv2d_planes_kernel<{mode}> {cin}->{cout} {hi}x{wi}",
                 lambda: dict(bytes=(x.numel() + y.numel()) * 2 + taps * cin * cout * 2, flops=2 * taps * coarse * cin * cout,

@@ -5,12 +5,17 @@ tests/golden/make_backward_schedule_trace.py with the logging code of tests/sche
 kernels of these layers sums with fp32 atomics (the record was taken twice and agreed), so the gradients compare by sha256.
 
 And the weight-pack launches of a whole backbone over four steps equal what the commit before SparseConvolution's pack cache
-issued (tests/golden/backbone_pack_trace.json, tests/golden/make_pack_window_traces.py, tests/pack_window_trace.py)."""
+issued (tests/golden/backbone_pack_trace.json, tests/golden/make_pack_window_traces.py, tests/pack_window_trace.py).
+
+And the table Conv3x3Packs plans for a small dense model, with the dense weight-pack launches of four steps, equal what the
+commit before the dense kinds' one table planned and issued (tests/golden/dense_pack_trace.json,
+tests/golden/make_dense_pack_trace.py, tests/dense_pack_trace.py)."""
 import json
 import os
 
 import pytest
 
+import dense_pack_trace as D
 import pack_window_trace as P
 import schedule_trace as T
 
@@ -47,3 +52,19 @@ def test_backbone_packs_once_per_step_and_ahead_of_the_forward_when_told(monkeyp
     assert want["pack_after_update"] == [[n, "main"] for n in batched] and want["step 2"] == []      # the record itself
     assert want["edit, step 3"] == [[n, "side"] for n in batched]
     assert P.backbone_pack_trace(monkeypatch) == want
+
+
+def test_dense_packs_are_planned_and_made_as_recorded(monkeypatch):
+    """BaseBEVBackbone + CenterHeadTowers with the batched head path, training: the plan lists every conv the kernels cover (the
+    un-registered first conv of all branches last) with two rows each; run() is ONE launch on the current stream; the step
+    behind it packs nothing; a step without it packs per call, forward and data gradient (none for the first conv: no dx);
+    and after run() plus an in-place edit of five weights exactly the convs that read them pack per call again (for a branch's
+    first-stage weight that is the batched first conv, whose weight aliases it)."""
+    want = _golden("dense_pack_trace.json")
+    one = ["pcd_conv2d_pack_weight", "main"]
+    assert want["run"] == [["pcd_conv2d_pack_weights_batched", "main"]] and want["step 2"] == []      # the record itself
+    assert want["step 3, without run"] == [one] * 25 and want["run, edit, step 4"] == want["run"] + [one] * 9
+    assert [r[4] for r in want["table"]] == [0, 1, 0, 1, 2, 3, 0, 1, 6, 7, 4, 5] + [0, 1] * 12
+    got = D.dense_pack_trace(monkeypatch)
+    assert got["table"] == want["table"]
+    assert got == want
