@@ -14,3 +14,4 @@ from .anchor_curriculum_head import (CurriculumAnchorHeadSingle, CurriculumAncho
 from .anchor_head_multi import AnchorHeadMulti, SingleHead  # noqa: F401
 from .point_head import PointHeadSimple  # noqa: F401
 from .roi_head import ProposalTargetLayer, PVRCNNHead, RoIHeadTemplate, VoxelRCNNHead  # noqa: F401
+from .second_head import SECONDHead  # noqa: F401

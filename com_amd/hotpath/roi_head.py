@@ -250,7 +250,13 @@ class RoIHeadTemplate(nn.Module):
     """roi_head_template.py:11-261: what the reference's RoI heads share -- proposal_layer, assign_targets (with the
     `uniforms` / `sampled_inds` hooks, and `roi_targets_dict` in the heads' forward), the loss, generate_predicted_boxes and
     the sampler's status check -- over the kernels of com_amd/csrc/roihead.hip.  A head sets HEAD_NAME and adds its own
-    refusals in `_refuse`."""
+    refusals in `_refuse`.
+
+    Two parts.  What EVERY head shares: NAME, TARGET_CONFIG, NMS_CONFIG and the class-agnostic checks (`_refuse_targets`,
+    `_refuse_proposals`), proposal_layer, assign_targets, the status check.  What the heads with a classification and a box
+    regression branch share: `_refuse_loss` and `build_losses` (CLS_LOSS, REG_LOSS, rcnn_cls_weight, rcnn_reg_weight), the
+    loss methods and generate_predicted_boxes.  A head with another loss (SECONDHead: IOU_LOSS, rcnn_iou_weight) overrides
+    those two and get_loss."""
 
     HEAD_NAME = 'RoIHeadTemplate'
 
@@ -265,19 +271,30 @@ class RoIHeadTemplate(nn.Module):
         self.num_class = int(num_class)                 # (detector3d_template.py passes 1 for CLASS_AGNOSTIC: True)
         self._refuse(model_cfg, int(num_class))
         self.code_size = 7
-        ta, lc = _get(model_cfg, 'TARGET_CONFIG'), _get(model_cfg, 'LOSS_CONFIG')
-        self.proposal_target_layer = ProposalTargetLayer(roi_sampler_cfg=ta)
-        lw = _get(lc, 'LOSS_WEIGHTS')
+        self.proposal_target_layer = ProposalTargetLayer(roi_sampler_cfg=_get(model_cfg, 'TARGET_CONFIG'))
+        self.build_losses(_get(model_cfg, 'LOSS_CONFIG'))
+        self.forward_ret_dict = None
+
+    def build_losses(self, losses_cfg):
+        """roi_head_template.py:24-27, plus the weights the fused loss takes"""
+        lw = _get(losses_cfg, 'LOSS_WEIGHTS')
         self.reg_loss_func = WeightedSmoothL1Loss(code_weights=lw['code_weights'])
         self.loss_weights = (float(lw['rcnn_cls_weight']), float(lw['rcnn_reg_weight']), float(lw.get('rcnn_corner_weight', 0.0)))
-        self.corner_loss = bool(_get(lc, 'CORNER_LOSS_REGULARIZATION', False))
-        self.forward_ret_dict = None
+        self.corner_loss = bool(_get(losses_cfg, 'CORNER_LOSS_REGULARIZATION', False))
 
     @classmethod
     def _refuse(cls, model_cfg, num_class):
         """the configurations outside the scope of the kernels: a PcdError that names the key"""
         def no(key, why):
             raise L.PcdError(f"{cls.HEAD_NAME}: {key} {why} is not supported by the HIP RoI head")
+        cls._refuse_targets(no, model_cfg)
+        cls._refuse_loss(no, model_cfg)
+        cls._refuse_proposals(no, model_cfg, num_class)
+        return no
+
+    @classmethod
+    def _refuse_targets(cls, no, model_cfg):
+        """every head: NAME and TARGET_CONFIG"""
         name = _get(model_cfg, 'NAME', cls.HEAD_NAME)
         if name != cls.HEAD_NAME:
             no('NAME', f"= {name!r}")
@@ -289,6 +306,10 @@ class RoIHeadTemplate(nn.Module):
             no('TARGET_CONFIG.BOX_CODER', f"= {coder!r}")
         if _get(ta, 'BOX_CODER_CONFIG', None):
             no('TARGET_CONFIG.BOX_CODER_CONFIG', f"= {dict(_get(ta, 'BOX_CODER_CONFIG'))!r} (code_size 7, no sin / cos heading)")
+
+    @classmethod
+    def _refuse_loss(cls, no, model_cfg):
+        """the heads with a classification and a box regression branch: LOSS_CONFIG"""
         lc = _get(model_cfg, 'LOSS_CONFIG')
         if lc is None:
             no('LOSS_CONFIG', 'missing')
@@ -304,6 +325,10 @@ class RoIHeadTemplate(nn.Module):
             no('LOSS_CONFIG.LOSS_WEIGHTS.code_weights', f"of length {len(lw['code_weights'])} (code_size 7)")
         if _get(lc, 'CORNER_LOSS_REGULARIZATION', False) and 'rcnn_corner_weight' not in lw:
             no('LOSS_CONFIG.LOSS_WEIGHTS.rcnn_corner_weight', 'missing')
+
+    @classmethod
+    def _refuse_proposals(cls, no, model_cfg, num_class):
+        """every head: NMS_CONFIG and the class-agnostic checks"""
         nms = _get(model_cfg, 'NMS_CONFIG')
         for mode in ('TRAIN', 'TEST'):
             cfg = _get(nms, mode, None) if nms is not None else None
@@ -318,7 +343,6 @@ class RoIHeadTemplate(nn.Module):
         if num_class > 1:
             no('num_class', f"= {num_class} with CLASS_AGNOSTIC = True (the detector passes 1; the reference's BinaryCrossEntropy "
                             "and box decoding take one logit and one box per RoI)")
-        return no
 
     @torch.no_grad()
     def proposal_layer(self, batch_dict, nms_config):
@@ -407,6 +431,38 @@ class RoIHeadTemplate(nn.Module):
         tb_dict['rcnn_loss'] = o[0]
         return out[0], tb_dict
 
+    def make_fc_layers(self, input_channels, output_channels, fc_list):
+        """roi_head_template.py:29-43"""
+        fc_layers = []
+        pre_channel = input_channels
+        dp = _get(self.model_cfg, 'DP_RATIO')
+        for k in range(0, fc_list.__len__()):
+            fc_layers.extend([nn.Conv1d(pre_channel, fc_list[k], kernel_size=1, bias=False), nn.BatchNorm1d(fc_list[k]), nn.ReLU()])
+            pre_channel = fc_list[k]
+            if dp >= 0 and k == 0:
+                fc_layers.append(nn.Dropout(dp))
+        fc_layers.append(nn.Conv1d(pre_channel, output_channels, kernel_size=1, bias=True))
+        return nn.Sequential(*fc_layers)
+
+    def init_weights(self, weight_init='xavier'):
+        """the loop pvrcnn_head.py:44-61 and second_head.py:44-61 share: every Conv1d / Conv2d of the head"""
+        if weight_init == 'kaiming':
+            init_func = nn.init.kaiming_normal_
+        elif weight_init == 'xavier':
+            init_func = nn.init.xavier_normal_
+        elif weight_init == 'normal':
+            init_func = nn.init.normal_
+        else:
+            raise NotImplementedError
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d) or isinstance(m, nn.Conv1d):
+                if weight_init == 'normal':
+                    init_func(m.weight, mean=0, std=0.001)
+                else:
+                    init_func(m.weight)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+
     def generate_predicted_boxes(self, batch_size, rois, cls_preds, box_preds):
         """roi_head_template.py:233-261"""
         batch_cls_preds = cls_preds.view(batch_size, -1, cls_preds.shape[-1])
@@ -449,37 +505,9 @@ class PVRCNNHead(RoIHeadTemplate):
                                                                                       'VectorPoolAggregationModuleMSG'):
             no('ROI_GRID_POOL.NAME', f"= {_get(_get(model_cfg, 'ROI_GRID_POOL'), 'NAME')!r}")
 
-    def make_fc_layers(self, input_channels, output_channels, fc_list):
-        """roi_head_template.py:29-43"""
-        fc_layers = []
-        pre_channel = input_channels
-        dp = _get(self.model_cfg, 'DP_RATIO')
-        for k in range(0, fc_list.__len__()):
-            fc_layers.extend([nn.Conv1d(pre_channel, fc_list[k], kernel_size=1, bias=False), nn.BatchNorm1d(fc_list[k]), nn.ReLU()])
-            pre_channel = fc_list[k]
-            if dp >= 0 and k == 0:
-                fc_layers.append(nn.Dropout(dp))
-        fc_layers.append(nn.Conv1d(pre_channel, output_channels, kernel_size=1, bias=True))
-        return nn.Sequential(*fc_layers)
-
     def init_weights(self, weight_init='xavier'):
         """pvrcnn_head.py:44-62"""
-        if weight_init == 'kaiming':
-            init_func = nn.init.kaiming_normal_
-        elif weight_init == 'xavier':
-            init_func = nn.init.xavier_normal_
-        elif weight_init == 'normal':
-            init_func = nn.init.normal_
-        else:
-            raise NotImplementedError
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d) or isinstance(m, nn.Conv1d):
-                if weight_init == 'normal':
-                    init_func(m.weight, mean=0, std=0.001)
-                else:
-                    init_func(m.weight)
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
+        super().init_weights(weight_init)
         nn.init.normal_(self.reg_layers[-1].weight, mean=0, std=0.001)
 
     def roi_grid_pool(self, batch_dict):

@@ -1,0 +1,355 @@
+"""`SECONDHead` -- the IoU-rectification RoI head of SECOND-IoU (pcdet/models/roi_heads/second_head.py; `ROI_HEAD.NAME:
+SECONDHead` in tools/cfgs/kitti_models/second_iou.yaml:87-134, detector SECONDNetIoU) as a registry drop-in: same constructor
+arguments, the modules `shared_fc_layer`, `iou_layers`, `reg_loss_func` built as the reference builds them (a reference state
+dict loads with strict=True), `roi_grid_pool`, `forward`, `get_loss(tb_dict)` and `get_box_iou_layer_loss` with the
+reference's names, keys and returns; plus `post_processing`, the score rectification of SECONDNetIoU
+(pcdet/models/detectors/second_net_iou.py:37-177).
+
+Three pieces run on the device (com_amd/csrc/secondhead.hip; C ABI `pcd_bev_roi_grid_pool`, `pcd_second_head_iou_loss_*`,
+`pcd_points_in_boxes_count`):
+  * the RoI grid pooling of the BEV map -- one launch for the whole batch instead of a per-frame affine_grid + grid_sample
+    over a stride-0 expand of the map.  The reference pools from DETACHED features and RoIs (second_head.py:74-75): the
+    pooling has no backward here either;
+  * the IoU loss -- one launch and one for its backward instead of boolean arithmetic and two `.item()`; `tb_dict` holds
+    DEVICE scalars, so assign_targets + forward + get_loss + backward can sit in a captured graph;
+  * the per-box point counts of `SCORE_TYPE: num_pts_iou_cls` -- one launch for the whole batch instead of a copy of every
+    frame's points and boxes to the host.
+
+Everything RoIHeadTemplate's first part holds (proposal_layer, assign_targets with the `uniforms` / `sampled_inds` hooks, the
+status check) is shared with PVRCNNHead and VoxelRCNNHead; the loss set-up and its refusals are this head's own (IOU_LOSS,
+rcnn_iou_weight).  The FC stack stays torch, as in PVRCNNHead."""
+import torch
+import torch.nn as nn
+
+from .. import _lib as L
+from ._maps import dtype_code as _dt
+from ._maps import like as _like
+from .dense2d import _get
+from .roi_head import RoIHeadTemplate, WeightedSmoothL1Loss
+
+IOU_LOSSES = {'BinaryCrossEntropy': L.PCD_SECOND_IOU_LOSS_BCE, 'L2': L.PCD_SECOND_IOU_LOSS_L2,
+              'smoothL1': L.PCD_SECOND_IOU_LOSS_SMOOTH_L1}
+SCORE_TYPES = ('iou', 'cls', 'weighted_iou_cls', 'score_by_class', 'num_pts_iou_cls')
+
+
+def bev_roi_grid_pool(spatial_features_2d, rois, grid_size, min_x, min_y, cell_x, cell_y):
+    """pcd_bev_roi_grid_pool: spatial_features_2d [B, C, H, W] (f32 / bf16; NCHW-contiguous and channels-last are read as they
+    lie, anything else is made contiguous), rois [B, N, 7+] -> [B * N, C, G, G] contiguous in the feature dtype;
+    second_head.py:87-113.  No gradient flows (the reference detaches both inputs)."""
+    L.require_device("SECONDHead.roi_grid_pool", spatial_features_2d, rois)
+    x, r = spatial_features_2d.detach(), rois.detach()
+    if x.dim() != 4 or r.dim() != 3 or r.shape[2] < 7 or r.shape[0] != x.shape[0]:
+        raise L.PcdError(f"bev_roi_grid_pool: spatial_features_2d {tuple(x.shape)}, rois {tuple(r.shape)}; want [B, C, H, W] "
+                         "and [B, N, 7+]")
+    G = int(grid_size)
+    if not 2 <= G <= L.PCD_SECOND_POOL_MAX_G:
+        raise L.PcdError(f"bev_roi_grid_pool: ROI_GRID_POOL.GRID_SIZE = {G}, want 2 .. {L.PCD_SECOND_POOL_MAX_G}")
+    if not (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)):
+        x = x.contiguous()
+    r = r.float()
+    B, C, H, W = (int(v) for v in x.shape)
+    N = int(r.shape[1])
+    # the kernel finds RoI b * N + n at (b * N + n) * row: ONE row stride has to serve both dimensions.  (The stride of a
+    # dimension of size 1 says nothing: with N == 1 the row stride is the frame stride.)
+    row = int(r.stride(1)) if N > 1 else int(r.stride(0))
+    if r.stride(2) != 1 or (N > 1 and B > 1 and int(r.stride(0)) != N * row) or (B * N > 1 and row < 7):
+        r = r.contiguous()
+        row = int(r.shape[2])
+    out = torch.empty((B * N, C, G, G), dtype=x.dtype, device=x.device)
+    L.check(L.lib().pcd_bev_roi_grid_pool(L.ptr(x), _dt(x), B, C, H, W, *[int(v) for v in x.stride()], L.ptr(r), N,
+                                          max(row, 7), G, float(min_x), float(min_y), float(cell_x),
+                                          float(cell_y), L.ptr(out), L.stream_ptr()), "pcd_bev_roi_grid_pool")
+    return out
+
+
+class _IouLoss(torch.autograd.Function):
+    """get_box_iou_layer_loss through pcd_second_head_iou_loss_forward / _backward: 1 + 1 launches.  Returns out f32 [2]
+    (rcnn_loss_iou, valid count); only out[0] carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, rcnn_iou, labels, kind, weight):
+        L.require_device("SECONDHead.get_box_iou_layer_loss", rcnn_iou, labels)
+        n = int(labels.numel())
+        flat = rcnn_iou.reshape(n, -1) if rcnn_iou.dim() != 2 else rcnn_iou
+        if n < 1 or flat.shape[0] != n or flat.shape[1] != 1:
+            raise L.PcdError(f"SECONDHead loss: rcnn_iou {tuple(rcnn_iou.shape)}, rcnn_cls_labels {tuple(labels.shape)}; want "
+                             "[B*R] or [B*R, 1] and as many labels")
+        out = torch.empty((2,), dtype=torch.float32, device=flat.device)
+        L.check(L.lib().pcd_second_head_iou_loss_forward(L.ptr(flat), _dt(flat), int(flat.stride(0)), L.ptr(labels), n, kind,
+                                                         weight, L.ptr(out), L.stream_ptr()), "pcd_second_head_iou_loss_forward")
+        ctx.save_for_backward(flat, labels, out)
+        ctx.meta = (kind, weight, rcnn_iou.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        flat, labels, out = ctx.saved_tensors
+        kind, weight, shape = ctx.meta
+        d = _like(flat)
+        g = g_out.detach().to(torch.float32)[0:1].contiguous()            # only rcnn_loss_iou is differentiated
+        L.check(L.lib().pcd_second_head_iou_loss_backward(L.ptr(flat), _dt(flat), int(flat.stride(0)), L.ptr(labels),
+                                                          int(labels.numel()), kind, weight, L.ptr(out), L.ptr(g), L.ptr(d),
+                                                          L.stream_ptr()), "pcd_second_head_iou_loss_backward")
+        return d.reshape(shape), None, None, None
+
+
+def iou_loss(rcnn_iou, rcnn_iou_labels, iou_loss_name, weight):
+    """out f32 [2] on the device = (sum over labels >= 0 / max(valid, 1) * weight, valid count); out[0] is differentiable in
+    rcnn_iou [n] / [n, 1] (f32 or bf16)."""
+    if iou_loss_name not in IOU_LOSSES:
+        raise L.PcdError(f"SECONDHead: LOSS_CONFIG.IOU_LOSS = {iou_loss_name!r} is not supported (supported: {sorted(IOU_LOSSES)})")
+    return _IouLoss.apply(rcnn_iou, rcnn_iou_labels.detach().reshape(-1).contiguous().float(), IOU_LOSSES[iou_loss_name],
+                          float(weight))
+
+
+def points_in_boxes_count(points, boxes):
+    """pcd_points_in_boxes_count: points [P, 4+] rows of (batch index, x, y, z, ...), boxes [B, K, 7+] -> int32 [B, K], the
+    number of the frame's points inside each box (the test of points_in_boxes_cpu); second_net_iou.py:133-138."""
+    L.require_device("points_in_boxes_count", points, boxes)
+    if points.dim() != 2 or points.shape[1] < 4 or boxes.dim() != 3 or boxes.shape[2] < 7:
+        raise L.PcdError(f"points_in_boxes_count: points {tuple(points.shape)}, boxes {tuple(boxes.shape)}; want [P, 4+] and "
+                         "[B, K, 7+]")
+    p = points.detach()[:, 0:4].float().contiguous()
+    b = boxes.detach()[:, :, 0:7].float().contiguous()
+    counts = torch.empty((int(b.shape[0]), int(b.shape[1])), dtype=torch.int32, device=b.device)
+    L.check(L.lib().pcd_points_in_boxes_count(L.ptr(p) if p.shape[0] else None, int(p.shape[0]), L.ptr(b) if b.numel() else None,
+                                              int(b.shape[0]), int(b.shape[1]), L.ptr(counts) if counts.numel() else None,
+                                              L.stream_ptr()), "pcd_points_in_boxes_count")
+    return counts
+
+
+class SECONDHead(RoIHeadTemplate):
+    """second_head.py:10-188 + the shared part of roi_head_template.py (module docstring).
+
+    The geometry of the BEV map (POINT_CLOUD_RANGE[0:2], the x / y voxel size) comes from `batch_dict['dataset_cfg']` when
+    the detector put it there, as in the reference (second_net_iou.py:13), otherwise from the `point_cloud_range` /
+    `voxel_size` keyword arguments Detector3DTemplate.build_roi_head passes to every RoI head."""
+
+    HEAD_NAME = 'SECONDHead'
+
+    def __init__(self, input_channels, model_cfg, num_class=1, point_cloud_range=None, voxel_size=None, **kwargs):
+        super().__init__(num_class=num_class, model_cfg=model_cfg)
+        pool = _get(model_cfg, 'ROI_GRID_POOL')
+        self.grid_size = int(_get(pool, 'GRID_SIZE'))
+        self.in_channel = int(_get(pool, 'IN_CHANNEL'))
+        self.point_cloud_range = None if point_cloud_range is None else [float(v) for v in point_cloud_range]
+        self.voxel_size = None if voxel_size is None else [float(v) for v in voxel_size]
+        pre_channel = self.in_channel * self.grid_size * self.grid_size
+        dp = _get(model_cfg, 'DP_RATIO')
+        shared_fc = list(_get(model_cfg, 'SHARED_FC'))
+        shared_fc_list = []
+        for k in range(0, shared_fc.__len__()):
+            shared_fc_list.extend([nn.Conv1d(pre_channel, shared_fc[k], kernel_size=1, bias=False), nn.BatchNorm1d(shared_fc[k]),
+                                   nn.ReLU()])
+            pre_channel = shared_fc[k]
+            if k != shared_fc.__len__() - 1 and dp > 0:
+                shared_fc_list.append(nn.Dropout(dp))
+        self.shared_fc_layer = nn.Sequential(*shared_fc_list)
+        self.iou_layers = self.make_fc_layers(input_channels=pre_channel, output_channels=1, fc_list=_get(model_cfg, 'IOU_FC'))
+        self.init_weights(weight_init='xavier')
+
+    def build_losses(self, losses_cfg):
+        """roi_head_template.py:24-27 (`reg_loss_func` is built though this head has no regression branch, as in the
+        reference) + the IoU loss of second_head.py:163-188"""
+        lw = _get(losses_cfg, 'LOSS_WEIGHTS')
+        self.reg_loss_func = WeightedSmoothL1Loss(code_weights=lw['code_weights'])
+        self.iou_loss_name = _get(losses_cfg, 'IOU_LOSS')
+        self.rcnn_iou_weight = float(lw['rcnn_iou_weight'])
+
+    @classmethod
+    def _refuse_loss(cls, no, model_cfg):
+        """this head's loss: IOU_LOSS and rcnn_iou_weight in place of CLS_LOSS / REG_LOSS and their weights"""
+        lc = _get(model_cfg, 'LOSS_CONFIG')
+        if lc is None:
+            no('LOSS_CONFIG', 'missing')
+        kind = _get(lc, 'IOU_LOSS', None)
+        if kind == 'focalbce':
+            no('LOSS_CONFIG.IOU_LOSS', "= 'focalbce' (the reference calls loss_utils.sigmoid_focal_cls_loss, which its "
+                                       "loss_utils.py does not define)")
+        if kind not in IOU_LOSSES:
+            no('LOSS_CONFIG.IOU_LOSS', f"= {kind!r} (supported: {sorted(IOU_LOSSES)})")
+        lw = _get(lc, 'LOSS_WEIGHTS', None)
+        for key in ('rcnn_iou_weight', 'code_weights'):
+            if lw is None or key not in lw:
+                no(f'LOSS_CONFIG.LOSS_WEIGHTS.{key}', 'missing')
+        if len(lw['code_weights']) != 7:
+            no('LOSS_CONFIG.LOSS_WEIGHTS.code_weights', f"of length {len(lw['code_weights'])} (code_size 7)")
+
+    @classmethod
+    def _refuse(cls, model_cfg, num_class):
+        """the shared refusals, then this head's own keys: the pooling and the FC stack"""
+        no = super()._refuse(model_cfg, num_class)
+        pool = _get(model_cfg, 'ROI_GRID_POOL', None)
+        if pool is None:
+            no('ROI_GRID_POOL', 'missing')
+        for key in ('GRID_SIZE', 'IN_CHANNEL', 'DOWNSAMPLE_RATIO'):
+            if _get(pool, key, None) is None:
+                no(f'ROI_GRID_POOL.{key}', 'missing')
+        if not 2 <= int(_get(pool, 'GRID_SIZE')) <= L.PCD_SECOND_POOL_MAX_G:
+            no('ROI_GRID_POOL.GRID_SIZE', f"= {_get(pool, 'GRID_SIZE')!r} (2 .. {L.PCD_SECOND_POOL_MAX_G}: align_corners=True "
+                                          "divides by GRID_SIZE - 1)")
+        if int(_get(pool, 'IN_CHANNEL')) < 1:
+            no('ROI_GRID_POOL.IN_CHANNEL', f"= {_get(pool, 'IN_CHANNEL')!r}")
+        if not float(_get(pool, 'DOWNSAMPLE_RATIO')) > 0:
+            no('ROI_GRID_POOL.DOWNSAMPLE_RATIO', f"= {_get(pool, 'DOWNSAMPLE_RATIO')!r}")
+        for key in ('SHARED_FC', 'IOU_FC', 'DP_RATIO'):
+            if _get(model_cfg, key, None) is None:
+                no(key, 'missing')
+        return no
+
+    def map_geometry(self, batch_dict):
+        """(min_x, min_y, cell_x, cell_y) of the BEV map: second_head.py:78-83"""
+        dataset_cfg = batch_dict.get('dataset_cfg', None)
+        if dataset_cfg is not None:
+            pcr = _get(dataset_cfg, 'POINT_CLOUD_RANGE')
+            vs = _get(_get(dataset_cfg, 'DATA_PROCESSOR')[-1], 'VOXEL_SIZE')
+        else:
+            pcr, vs = self.point_cloud_range, self.voxel_size
+        if pcr is None or vs is None:
+            raise L.PcdError("SECONDHead: neither batch_dict['dataset_cfg'] (POINT_CLOUD_RANGE, DATA_PROCESSOR[-1].VOXEL_SIZE) nor "
+                             "the point_cloud_range / voxel_size constructor arguments are there")
+        ratio = _get(_get(self.model_cfg, 'ROI_GRID_POOL'), 'DOWNSAMPLE_RATIO')
+        return float(pcr[0]), float(pcr[1]), float(vs[0]) * ratio, float(vs[1]) * ratio
+
+    def roi_grid_pool(self, batch_dict):
+        """second_head.py:63-120 -> [B * N, C, G, G]"""
+        feats = batch_dict['spatial_features_2d']
+        if int(feats.shape[1]) != self.in_channel:
+            raise L.PcdError(f"SECONDHead: ROI_GRID_POOL.IN_CHANNEL = {self.in_channel}, spatial_features_2d has "
+                             f"{int(feats.shape[1])} channels")
+        return bev_roi_grid_pool(feats, batch_dict['rois'], self.grid_size, *self.map_geometry(batch_dict))
+
+    def forward(self, batch_dict):
+        """second_head.py:122-151 (+ the `roi_targets_dict` hook the other RoI heads' forward has)"""
+        nms = _get(self.model_cfg, 'NMS_CONFIG')
+        targets_dict = self.proposal_layer(batch_dict, nms_config=_get(nms, 'TRAIN' if self.training else 'TEST'))
+        if self.training:
+            targets_dict = batch_dict.get('roi_targets_dict', None)
+            if targets_dict is None:
+                targets_dict = self.assign_targets(batch_dict)
+                batch_dict['rois'] = targets_dict['rois']
+                batch_dict['roi_labels'] = targets_dict['roi_labels']
+        pooled_features = self.roi_grid_pool(batch_dict)  # (BxN, C, 7, 7)
+        batch_size_rcnn = pooled_features.shape[0]
+        conv = self.shared_fc_layer[0]
+        shared_features = self.shared_fc_layer(pooled_features.view(batch_size_rcnn, -1, 1).to(conv.weight.dtype))
+        rcnn_iou = self.iou_layers(shared_features).transpose(1, 2).contiguous().squeeze(dim=1)  # (B*N, 1)
+        if not self.training:
+            batch_dict['batch_cls_preds'] = rcnn_iou.view(batch_dict['batch_size'], -1, rcnn_iou.shape[-1])
+            batch_dict['batch_box_preds'] = batch_dict['rois']
+            batch_dict['cls_preds_normalized'] = False
+        else:
+            targets_dict['rcnn_iou'] = rcnn_iou
+            self.forward_ret_dict = targets_dict
+        return batch_dict
+
+    def get_box_iou_layer_loss(self, forward_ret_dict):
+        """second_head.py:163-188; tb_dict['rcnn_loss_iou'] is a device scalar"""
+        out = iou_loss(forward_ret_dict['rcnn_iou'], forward_ret_dict['rcnn_cls_labels'], self.iou_loss_name, self.rcnn_iou_weight)
+        return out[0], {'rcnn_loss_iou': out[0].detach()}
+
+    def get_loss(self, tb_dict=None):
+        """second_head.py:153-161; the tb_dict values are device scalars"""
+        tb_dict = {} if tb_dict is None else tb_dict
+        rcnn_loss, iou_tb_dict = self.get_box_iou_layer_loss(self.forward_ret_dict)
+        tb_dict.update(iou_tb_dict)
+        tb_dict['rcnn_loss'] = rcnn_loss.detach()
+        return rcnn_loss, tb_dict
+
+    def _no_box_branch(self, *args, **kwargs):
+        raise L.PcdError("SECONDHead has no classification / box regression branch (its loss is get_box_iou_layer_loss; its "
+                         "boxes are the RoIs)")
+
+    get_box_reg_layer_loss = get_box_cls_layer_loss = generate_predicted_boxes = _no_box_branch
+
+    def post_processing(self, batch_dict, post_process_cfg, class_names):
+        return post_processing(batch_dict, post_process_cfg, class_names)
+
+
+def cal_scores_by_npoints(cls_scores, iou_scores, num_points_in_gt, cls_thresh=10, iou_thresh=100):
+    """second_net_iou.py:37-57.  A QUIRK of the reference, reproduced: the ramp between the two thresholds subtracts the
+    literal 10, not `cls_thresh` -- with SCORE_THRESH.cls = 5 a box with 6 points gets alpha = (6 - 10) / (iou - 5) < 0."""
+    assert iou_thresh >= cls_thresh
+    n = num_points_in_gt.to(torch.float32)
+    ramp = (n - 10) / (iou_thresh - cls_thresh)
+    alpha = torch.where(n >= iou_thresh, torch.ones_like(n), torch.where(n > cls_thresh, ramp, torch.zeros_like(n)))
+    return (1 - alpha) * cls_scores + alpha * iou_scores
+
+
+def set_nms_score_by_class(iou_preds, cls_preds, label_preds, score_by_class, class_names):
+    """second_net_iou.py:59-73.  A QUIRK of the reference, reproduced: the loop runs over range(number of DISTINCT labels in
+    the frame), not over the classes -- a frame whose labels are {1, 3} visits classes 1 and 2 and leaves class 3 at score 0.
+    The number of distinct labels comes from a presence vector on the device (no torch.unique, nothing read back): the
+    loop becomes `label <= number of distinct labels`."""
+    for name in class_names:
+        if _get(score_by_class, name) not in ('iou', 'cls'):
+            raise L.PcdError(f"post_processing: NMS_CONFIG.SCORE_BY_CLASS.{name} = {_get(score_by_class, name)!r} is not "
+                             "supported (supported: 'iou', 'cls')")
+    num = len(class_names)
+    lab = label_preds.long().clamp(0, num)                                  # (labels are 1 .. num; 0 keeps score 0)
+    presence = torch.zeros((num + 1,), dtype=torch.int32, device=lab.device)
+    presence[lab] = 1
+    n_classes = presence.sum()
+    take_iou = torch.tensor([False] + [score_by_class[name] == 'iou' for name in class_names], device=lab.device)
+    visited = (lab >= 1) & (lab <= n_classes)                              # classes 1 .. n_classes are the ones the loop sees
+    scores = torch.where(take_iou[lab], iou_preds.float(), cls_preds.float())
+    return torch.where(visited, scores, torch.zeros_like(scores))
+
+
+def post_processing(batch_dict, post_process_cfg, class_names):
+    """SECONDNetIoU.post_processing (second_net_iou.py:75-177) in the eager style of anchor_head.post_processing, over
+    center_head.class_agnostic_nms: the reference's list of dicts with pred_boxes, pred_scores, pred_labels,
+    pred_cls_scores, pred_iou_scores.  Recall records are not kept.  NMS_CONFIG.SCORE_TYPE: 'iou' (also when the key is
+    absent), 'cls', 'weighted_iou_cls', 'score_by_class', 'num_pts_iou_cls' -- the last with ONE pcd_points_in_boxes_count
+    call for the whole batch and no tensor on the host."""
+    from .center_head import class_agnostic_nms
+    nms_cfg = _get(post_process_cfg, 'NMS_CONFIG')
+    if _get(nms_cfg, 'MULTI_CLASSES_NMS', False):
+        raise L.PcdError("SECONDHead post_processing: NMS_CONFIG.MULTI_CLASSES_NMS = True is not supported (the reference raises "
+                         "NotImplementedError)")
+    if _get(post_process_cfg, 'OUTPUT_RAW_SCORE', False):
+        raise L.PcdError("SECONDHead post_processing: OUTPUT_RAW_SCORE = True is not supported (the reference raises "
+                         "NotImplementedError)")
+    score_type = _get(nms_cfg, 'SCORE_TYPE', None)
+    if score_type == 'score_by_class' and not _get(nms_cfg, 'SCORE_BY_CLASS', None):
+        raise L.PcdError("SECONDHead post_processing: NMS_CONFIG.SCORE_BY_CLASS missing beside SCORE_TYPE = 'score_by_class'")
+    if score_type is not None and score_type not in SCORE_TYPES:
+        raise L.PcdError(f"SECONDHead post_processing: NMS_CONFIG.SCORE_TYPE = {score_type!r} is not supported "
+                         f"(supported: {list(SCORE_TYPES)})")
+    if batch_dict.get('batch_index', None) is not None:
+        raise L.PcdError("SECONDHead post_processing: batch_index (stacked predictions) is not supported; SECONDHead writes "
+                         "[B, N, .] predictions")
+    L.require_device("SECONDHead post_processing", batch_dict['batch_box_preds'], batch_dict['batch_cls_preds'],
+                     batch_dict['roi_scores'])
+    assert batch_dict['batch_cls_preds'].shape.__len__() == 3
+    counts = None
+    if score_type == 'num_pts_iou_cls':
+        counts = points_in_boxes_count(batch_dict['points'], batch_dict['batch_box_preds'])
+    pred_dicts = []
+    for index in range(int(batch_dict['batch_size'])):
+        box_preds = batch_dict['batch_box_preds'][index]
+        iou_preds = batch_dict['batch_cls_preds'][index].float()
+        cls_preds = batch_dict['roi_scores'][index].float()
+        assert iou_preds.shape[1] in [1, len(class_names)]
+        if not batch_dict['cls_preds_normalized']:
+            iou_preds = torch.sigmoid(iou_preds)
+            cls_preds = torch.sigmoid(cls_preds)
+        iou_preds, label_preds = torch.max(iou_preds, dim=-1)
+        label_preds = batch_dict['roi_labels'][index] if batch_dict.get('has_class_labels', False) else label_preds + 1
+        if score_type == 'score_by_class':
+            nms_scores = set_nms_score_by_class(iou_preds, cls_preds, label_preds, _get(nms_cfg, 'SCORE_BY_CLASS'), class_names)
+        elif score_type == 'iou' or score_type is None:
+            nms_scores = iou_preds
+        elif score_type == 'cls':
+            nms_scores = cls_preds
+        elif score_type == 'weighted_iou_cls':
+            w = _get(nms_cfg, 'SCORE_WEIGHTS')
+            nms_scores = _get(w, 'iou') * iou_preds + _get(w, 'cls') * cls_preds
+        else:
+            thr = _get(nms_cfg, 'SCORE_THRESH')
+            nms_scores = cal_scores_by_npoints(cls_preds, iou_preds, counts[index], _get(thr, 'cls'), _get(thr, 'iou'))
+        selected, selected_scores = class_agnostic_nms(box_scores=nms_scores, box_preds=box_preds, nms_config=nms_cfg,
+                                                       score_thresh=_get(post_process_cfg, 'SCORE_THRESH', None))
+        pred_dicts.append({'pred_boxes': box_preds[selected], 'pred_scores': selected_scores, 'pred_labels': label_preds[selected],
+                           'pred_cls_scores': cls_preds[selected], 'pred_iou_scores': iou_preds[selected]})
+    return pred_dicts

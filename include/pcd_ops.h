@@ -1525,6 +1525,52 @@ int pcd_roi_head_loss_backward(const void *rcnn_cls, int cls_dtype, long long cl
 int pcd_roi_head_decode(const float *rois, const void *box_preds, int dtype, long long row_stride, int num_rows,
                         float *batch_box_preds, void *stream);
 
+/* ============================================================================================
+ * (f7) SECONDHead, the IoU-rectification stage of SECOND-IoU -- replaces the per-frame loop of
+ *      pcdet/models/roi_heads/second_head.py:63-120, its loss (:163-188) and the host round trip of
+ *      pcdet/models/detectors/second_net_iou.py:133-138.  No entry point reads anything back, allocates or has a
+ *      data-dependent shape: all are capturable.
+ *   pcd_bev_roi_grid_pool: roi_grid_pool (second_head.py:87-113: theta, affine_grid and grid_sample with align_corners=True,
+ *                bilinear, zero padding, over a stride-0 expand of the frame's map) for the whole batch in one launch.
+ *                features [batch][channels][height][width] f32 or bf16 with element strides {b, c, y, x} (NCHW and
+ *                channels-last are both native; any positive strides are read correctly); rois f32 [batch][num_rois] rows
+ *                of >= 7 floats, roi_stride elements apart; cell_x / cell_y = voxel size x DOWNSAMPLE_RATIO.  With
+ *                cx = (x - min_x) / cell_x, hx = dx / 2 / cell_x (y alike), u_j = -1 + 2 j / (G - 1), v_i alike, sample
+ *                (i, j) lies at ix = cx + hx (cos a u_j - sin a v_i), iy = cy + hy (sin a u_j + cos a v_i) pixels
+ *                (sincosf, fp32); its value is the sum over the four neighbours of (floor ix, floor iy) inside the map,
+ *                weighted (1 - |ix - X|)(1 - |iy - Y|).  A neighbour outside the map is not read.  pooled
+ *                [batch * num_rois][channels][G][G] dense, in the feature dtype (c-major: shared_fc_layer[0].weight
+ *                indexes c * G * G + p).  Both layouts give the same bits.  PCD_ERR_UNSUPPORTED: G < 2,
+ *                G > PCD_SECOND_POOL_MAX_G, height or width < 2, more than 65535 RoIs.  There is no backward: the
+ *                reference pools from detached features and RoIs (second_head.py:74-75).
+ *   pcd_second_head_iou_loss_forward / _backward: get_box_iou_layer_loss (second_head.py:163-188).  logits [n] f32 or bf16,
+ *                `stride` elements apart; labels f32 [n]; kind = PCD_SECOND_IOU_LOSS_BCE (binary_cross_entropy_with_logits
+ *                in its stable form), _L2 (mse_loss) or _SMOOTH_L1 (loss_utils.py:363-370, beta 1 / 9) over the rows with
+ *                label >= 0.  out = 2 device floats: sum / max(valid, 1) x weight, and the valid count.  One workgroup,
+ *                fp64 partial sums joined by a fixed tree: bit-reproducible.  backward: d_logits (layout and dtype of
+ *                logits, every element written) = *grad_out (device f32) x the derivative; `out` is the forward's.
+ *                ('focalbce' calls loss_utils.sigmoid_focal_cls_loss, which the reference does not define: no kind.)
+ *   pcd_points_in_boxes_count: points_in_boxes_cpu(points of frame b, boxes[b]).sum(dim=1) for every frame
+ *                (second_net_iou.py:133-138).  points [num_points][4] rows of (bs_idx, x, y, z), in any order; boxes
+ *                [batch][num_boxes][7]; counts int32 [batch][num_boxes], zeroed by the call.  A point counts for every box
+ *                that contains it; the test is that of pcd_points_in_boxes_host (MARGIN 1e-2).  Integer atomics only
+ *                (LDS, then one global add per workgroup and box): the result does not depend on the order.
+ * ============================================================================================ */
+#define PCD_SECOND_POOL_MAX_G 16
+#define PCD_SECOND_IOU_LOSS_BCE 0
+#define PCD_SECOND_IOU_LOSS_L2 1
+#define PCD_SECOND_IOU_LOSS_SMOOTH_L1 2
+int pcd_bev_roi_grid_pool(const void *features, int dtype, int batch, int channels, int height, int width,
+                          long long stride_b, long long stride_c, long long stride_y, long long stride_x, const float *rois,
+                          int num_rois, long long roi_stride, int grid_size, float min_x, float min_y, float cell_x,
+                          float cell_y, void *pooled, void *stream);
+int pcd_second_head_iou_loss_forward(const void *logits, int dtype, long long stride, const float *labels, int n, int kind,
+                                     float weight, float *out, void *stream);
+int pcd_second_head_iou_loss_backward(const void *logits, int dtype, long long stride, const float *labels, int n, int kind,
+                                      float weight, const float *out, const float *grad_out, void *d_logits, void *stream);
+int pcd_points_in_boxes_count(const float *points, int num_points, const float *boxes, int batch, int num_boxes, int *counts,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif
