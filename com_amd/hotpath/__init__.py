@@ -12,6 +12,6 @@ from .anchor_head import AnchorGenerator, AnchorHeadSingle, ResidualCoder  # noq
 from .anchor_curriculum_head import (CurriculumAnchorHeadSingle, CurriculumAnchorHeadSingle_car,  # noqa: F401
                                      CurriculumAnchorHeadSingle_car_x2, CurriculumAnchorHeadSingle_x1)
 from .anchor_head_multi import AnchorHeadMulti, SingleHead  # noqa: F401
-from .point_head import PointHeadSimple  # noqa: F401
+from .point_head import PointHeadBox, PointHeadSimple, PointIntraPartOffsetHead, PointResidualCoder  # noqa: F401
 from .roi_head import ProposalTargetLayer, PVRCNNHead, RoIHeadTemplate, VoxelRCNNHead  # noqa: F401
 from .second_head import SECONDHead  # noqa: F401

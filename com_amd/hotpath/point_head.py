@@ -7,8 +7,13 @@ launch for the whole stacked batch instead of a host loop over frames with two p
 indexing and `bs_mask.sum()` syncs each; no `.item()` -- `tb_dict` holds DEVICE scalars, and forward + get_loss + backward
 can sit in a captured graph with a fixed number of points.
 
-Scope: PointHeadSimple with set_ignore_flag targets.  PointHeadBox, PointIntraPartOffsetHead and targets with
-ret_box_labels / ret_part_labels / use_ball_constraint are refused at construction with a PcdError that names the key."""
+Scope: PointHeadSimple with set_ignore_flag targets; it refuses a box / part-offset configuration at construction with a
+PcdError that names the key.  Those configurations belong to `PointHeadBox` (point_head_box.py; PointRCNN) and
+`PointIntraPartOffsetHead` (point_intra_part_head.py; Part-A2, Part-A2-free) below, with `PointResidualCoder`
+(box_coder_utils.py:144-222): box labels (encode_torch) and part labels come out of the same assignment launch, the cls /
+box / part losses out of one forward and one backward launch (`pcd_point_head_full_loss_*`), the proposals of an eval
+forward out of `pcd_point_head_decode`.  Only use_ball_constraint targets stay refused."""
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -179,5 +184,438 @@ class PointHeadSimple(nn.Module):
             targets_dict = self.assign_targets(batch_dict)
             ret_dict['point_cls_labels'] = targets_dict['point_cls_labels']
             ret_dict['point_pos_num'] = targets_dict['point_pos_num']
+        self.forward_ret_dict = ret_dict
+        return batch_dict
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# PointHeadBox / PointIntraPartOffsetHead
+MAX_MEAN_SIZES = 16     # PH_MAX_MEAN of roiaware.hip
+
+
+class PointResidualCoder(object):
+    """box_coder_utils.py:144-222 with its attributes (code_size, use_mean_size, mean_size).  `mean_size` is a CPU float32
+    [K, 3] tensor (the reference calls .cuda() in its constructor); `mean_size_on(device)` is the copy the kernels read, made
+    once per device.  decode_torch runs pcd_point_head_decode; encode_torch is plain torch (the heads encode inside the
+    assignment kernel) and, unlike the reference, leaves gt_boxes as it found them."""
+
+    def __init__(self, code_size=8, use_mean_size=True, **kwargs):
+        super().__init__()
+        if int(code_size) != 8:
+            raise L.PcdError(f"PointResidualCoder: BOX_CODER_CONFIG.code_size = {code_size!r} is not supported by the HIP point "
+                             "head (8: x, y, z, dx, dy, dz, cos, sin)")
+        self.code_size = 8
+        self.use_mean_size = bool(use_mean_size)
+        self._on = {}
+        if self.use_mean_size:
+            if kwargs.get('mean_size', None) is None:
+                raise L.PcdError("PointResidualCoder: BOX_CODER_CONFIG.mean_size missing (use_mean_size = True)")
+            self.mean_size = torch.from_numpy(np.array(kwargs['mean_size'], dtype=np.float64)).float().reshape(-1, 3).contiguous()
+            assert self.mean_size.min() > 0
+            if self.mean_size.shape[0] > MAX_MEAN_SIZES:
+                raise L.PcdError(f"PointResidualCoder: BOX_CODER_CONFIG.mean_size has {self.mean_size.shape[0]} rows, the HIP "
+                                 f"point head takes at most {MAX_MEAN_SIZES}")
+
+    def mean_size_on(self, device):
+        """the [K, 3] table on `device` (None without mean sizes); copied on first use -- before a capture, not inside one"""
+        if not self.use_mean_size:
+            return None
+        key = torch.device(device)
+        if key not in self._on:
+            self._on[key] = self.mean_size.to(key)
+        return self._on[key]
+
+    def encode_torch(self, gt_boxes, points, gt_classes=None):
+        """:153-187; gt_boxes (N, 7), points (N, 3), gt_classes (N) in [1, K] -> (N, 8)"""
+        if gt_boxes.shape[-1] != 7:
+            raise L.PcdError(f"PointResidualCoder.encode_torch: gt_boxes {tuple(gt_boxes.shape)}, want (N, 7) (code_size 8)")
+        xg, yg, zg, dxg, dyg, dzg, rg = torch.split(gt_boxes, 1, dim=-1)
+        dxg, dyg, dzg = (torch.clamp_min(d, 1e-5) for d in (dxg, dyg, dzg))
+        xa, ya, za = torch.split(points, 1, dim=-1)
+        if self.use_mean_size:
+            mean_size = self.mean_size.to(gt_boxes.device)
+            assert gt_classes.max() <= mean_size.shape[0]
+            dxa, dya, dza = torch.split(mean_size[gt_classes - 1].to(gt_boxes.dtype), 1, dim=-1)
+            diagonal = torch.sqrt(dxa ** 2 + dya ** 2)
+            xt, yt, zt = (xg - xa) / diagonal, (yg - ya) / diagonal, (zg - za) / dza
+            dxt, dyt, dzt = torch.log(dxg / dxa), torch.log(dyg / dya), torch.log(dzg / dza)
+        else:
+            xt, yt, zt = xg - xa, yg - ya, zg - za
+            dxt, dyt, dzt = torch.log(dxg), torch.log(dyg), torch.log(dzg)
+        return torch.cat([xt, yt, zt, dxt, dyt, dzt, torch.cos(rg), torch.sin(rg)], dim=-1)
+
+    def decode_torch(self, box_encodings, points, pred_classes=None):
+        """:189-222 through pcd_point_head_decode: box_encodings (..., 8), points (..., 3), pred_classes (...) in [1, K] ->
+        float32 (..., 7).  Not differentiable."""
+        if self.use_mean_size and pred_classes is None:
+            raise L.PcdError("PointResidualCoder.decode_torch: pred_classes missing (use_mean_size = True)")
+        lead = box_encodings.shape[:-1]
+        classes = None if pred_classes is None or not self.use_mean_size else pred_classes.reshape(-1).long().contiguous()
+        boxes = decode_boxes(box_encodings.reshape(-1, box_encodings.shape[-1]), points.reshape(-1, 3),
+                             None if not self.use_mean_size else self.mean_size_on(box_encodings.device), pred_classes=classes)
+        return boxes.reshape(*lead, 7)
+
+
+def _rows(t, width, what):
+    """a [N, width] f32 / bf16 device tensor whose rows the kernels can walk (unit inner stride)"""
+    if t.dim() != 2 or t.shape[1] != width:
+        raise L.PcdError(f"point head: {what} {tuple(t.shape)}, want [N, {width}]")
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        t = t.float()
+    return t if t.stride(1) == 1 and t.stride(0) >= width else t.contiguous()
+
+
+def decode_boxes(box_encodings, points, mean_size, cls_preds=None, pred_classes=None):
+    """pcd_point_head_decode: float32 [N, 7] boxes from [N, 8] encodings at the points [N, 3]; the mean size of a point is
+    picked by pred_classes (int64, 1-based) or by the first maximum of its cls_preds row; mean_size None: no mean sizes."""
+    L.require_device("PointResidualCoder.decode_torch", box_encodings, points)
+    L.require_device("PointResidualCoder.decode_torch", cls_preds, pred_classes, mean_size, allow_none=True)
+    enc = _rows(box_encodings.detach(), 8, "box encodings")
+    n = int(enc.shape[0])
+    pts = points.detach()
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] != n:
+        raise L.PcdError(f"point head: points {tuple(pts.shape)}, want [{n}, 3]")
+    if pts.dtype != torch.float32 or pts.stride(1) != 1:
+        pts = pts.float().contiguous()
+    cls, num_class = None, 0
+    if mean_size is not None and pred_classes is None:
+        if cls_preds is None:
+            raise L.PcdError("point head: decoding with mean sizes needs cls_preds or pred_classes")
+        cls = _rows(cls_preds.detach(), cls_preds.shape[-1], "cls_preds")
+        num_class = int(cls.shape[1])
+        if cls.dtype != enc.dtype:
+            cls, enc = cls.float(), enc.float()
+        if cls.shape[0] != n:
+            raise L.PcdError(f"point head: cls_preds {tuple(cls.shape)} for {n} box encodings")
+    if pred_classes is not None and (pred_classes.dtype != torch.int64 or pred_classes.numel() != n):
+        raise L.PcdError(f"point head: pred_classes {pred_classes.dtype} {tuple(pred_classes.shape)}, want int64 [{n}]")
+    boxes = torch.empty((n, 7), dtype=torch.float32, device=enc.device)
+    k = 0 if mean_size is None else int(mean_size.shape[0])
+    L.check(L.lib().pcd_point_head_decode(L.ptr(cls) if n else None, int(cls.stride(0)) if cls is not None else 0, num_class,
+                                          L.ptr(pred_classes) if n else None, L.ptr(enc) if n else None, int(enc.stride(0)),
+                                          _dt(enc), L.ptr(pts) if n else None, int(pts.stride(0)), L.ptr(mean_size), k, n,
+                                          L.ptr(boxes) if n else None, L.stream_ptr()), "pcd_point_head_decode")
+    return boxes
+
+
+def assign_targets_full(point_coords, gt_boxes, extra_width, num_class, mean_size=None, ret_box_labels=True,
+                        ret_part_labels=False):
+    """pcd_point_head_assign_targets_full: (point_cls_labels int64 [N], point_box_labels f32 [N, 8] | None, point_part_labels
+    f32 [N, 3] | None, num_pos int32 [1]); mean_size: device f32 [K, 3] or None (use_mean_size False)."""
+    if not point_coords.is_cuda or not gt_boxes.is_cuda or (mean_size is not None and not mean_size.is_cuda):
+        raise L.PcdError("point head assign_targets needs HIP device tensors (there is no CPU fallback)")
+    assert gt_boxes.shape.__len__() == 3, 'gt_boxes.shape=%s' % str(gt_boxes.shape)
+    assert point_coords.shape.__len__() in [2], 'points.shape=%s' % str(point_coords.shape)
+    if point_coords.shape[1] != 4 or gt_boxes.shape[2] != 8:
+        raise L.PcdError(f"point head assign_targets: point_coords {tuple(point_coords.shape)}, gt_boxes "
+                         f"{tuple(gt_boxes.shape)}; want [N, 4] and [B, M, 8]")
+    pc, gt = point_coords.contiguous().float(), gt_boxes.contiguous().float()
+    n, b, m = int(pc.shape[0]), int(gt.shape[0]), int(gt.shape[1])
+    labels = torch.empty((n,), dtype=torch.int64, device=pc.device)
+    box = torch.empty((n, 8), dtype=torch.float32, device=pc.device) if ret_box_labels else None
+    part = torch.empty((n, 3), dtype=torch.float32, device=pc.device) if ret_part_labels else None
+    num_pos = torch.empty((1,), dtype=torch.int32, device=pc.device)
+    ex, ey, ez = (float(v) for v in extra_width)
+    ms = mean_size.contiguous().float() if mean_size is not None else None
+    L.check(L.lib().pcd_point_head_assign_targets_full(
+        L.ptr(pc) if n else None, n, L.ptr(gt) if m else None, b, m, ex, ey, ez, int(num_class), L.ptr(ms),
+        0 if ms is None else int(ms.shape[0]), L.ptr(labels) if n else None, L.ptr(box) if n else None, L.ptr(part) if n else None,
+        L.ptr(num_pos), L.stream_ptr()), "pcd_point_head_assign_targets_full")
+    return labels, box, part, num_pos
+
+
+class _PointHeadLoss(torch.autograd.Function):
+    """the cls / box / part losses through pcd_point_head_full_loss_forward / _backward: 2 + 1 launches.  Returns the four
+    device floats (total, cls, box, part); box / part predictions may be None."""
+
+    @staticmethod
+    def forward(ctx, cls, box, part, labels, box_labels, part_labels, num_pos, code_weights, num_class, weights):
+        n = int(cls.shape[0])
+        lib = L.lib()
+        out = torch.empty((4,), dtype=torch.float32, device=cls.device)
+        ws = L.workspace(lib.pcd_point_head_full_loss_workspace_bytes(n), cls.device)
+        L.check(lib.pcd_point_head_full_loss_forward(
+            L.ptr(cls), int(cls.stride(0)), L.ptr(box), int(box.stride(0)) if box is not None else 0, L.ptr(part),
+            int(part.stride(0)) if part is not None else 0, _dt(cls), L.ptr(labels), L.ptr(box_labels), L.ptr(part_labels),
+            L.ptr(num_pos), L.ptr(code_weights), n, num_class, weights[0], weights[1], weights[2], L.ptr(out), L.ptr(ws),
+            ws.numel(), L.stream_ptr()), "pcd_point_head_full_loss_forward")
+        ctx.save_for_backward(cls, box, part, labels, box_labels, part_labels, num_pos, code_weights)
+        ctx.meta = (num_class, weights)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        cls, box, part, labels, box_labels, part_labels, num_pos, code_weights = ctx.saved_tensors
+        num_class, weights = ctx.meta
+        d = [None if t is None else torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device) for t in (cls, box, part)]
+        g = g_out.detach().to(torch.float32).reshape(4).contiguous()
+        L.check(L.lib().pcd_point_head_full_loss_backward(
+            L.ptr(cls), L.ptr(d[0]), int(cls.stride(0)), L.ptr(box), L.ptr(d[1]), int(box.stride(0)) if box is not None else 0,
+            L.ptr(part), L.ptr(d[2]), int(part.stride(0)) if part is not None else 0, _dt(cls), L.ptr(labels), L.ptr(box_labels),
+            L.ptr(part_labels), L.ptr(num_pos), L.ptr(code_weights), int(cls.shape[0]), num_class, weights[0], weights[1],
+            weights[2], L.ptr(g), L.stream_ptr()), "pcd_point_head_full_loss_backward")
+        return d[0], d[1], d[2], None, None, None, None, None, None, None
+
+
+def point_head_loss(cls_preds, labels, num_pos, num_class, cls_weight, box_preds=None, box_labels=None, code_weights=None,
+                    box_weight=0.0, part_preds=None, part_labels=None, part_weight=0.0):
+    """device float32 [4] = (point_loss, point_loss_cls, point_loss_box, point_loss_part), differentiable in cls_preds
+    [N, num_class], box_preds [N, 8] and part_preds [N, 3] (f32 or bf16, one dtype; a branch that is None gives 0)."""
+    preds = [t for t in (cls_preds, box_preds, part_preds) if t is not None]
+    given = [t for t in (labels, num_pos, box_labels, part_labels, code_weights) if t is not None]
+    if not all(t.is_cuda for t in preds + given):
+        raise L.PcdError("point head get_loss needs HIP device tensors (there is no CPU fallback)")
+    if box_preds is not None and (box_labels is None or code_weights is None or code_weights.numel() != 8):
+        raise L.PcdError("point head: box_preds need point_box_labels and 8 code_weights")
+    if part_preds is not None and part_labels is None:
+        raise L.PcdError("point head: part_preds need point_part_labels")
+    if len({t.dtype for t in preds}) != 1:
+        preds = [t.float() for t in preds]
+    it = iter(preds)
+    cls = _rows(next(it), num_class, "point_cls_preds")
+    box = _rows(next(it), 8, "point_box_preds") if box_preds is not None else None
+    part = _rows(next(it), 3, "point_part_preds") if part_preds is not None else None
+    n = int(cls.shape[0])
+    if labels.shape[0] != n or any(t is not None and t.shape[0] != n for t in (box, part)):
+        raise L.PcdError(f"point head: {n} cls rows, labels {tuple(labels.shape)}, box / part predictions "
+                         f"{[None if t is None else tuple(t.shape) for t in (box, part)]}")
+    if n == 0:
+        return torch.stack([sum(t.float().sum() for t in preds) * 0.0] * 4)
+    bl = box_labels.detach().reshape(n, 8).float().contiguous() if box is not None else None
+    pl = part_labels.detach().reshape(n, 3).float().contiguous() if part is not None else None
+    cw = code_weights.detach().float().contiguous() if box is not None else None
+    return _PointHeadLoss.apply(cls, box, part, labels.long().contiguous(), bl, pl, num_pos, cw, int(num_class),
+                                (float(cls_weight), float(box_weight), float(part_weight)))
+
+
+class _PointHeadWithBranches(nn.Module):
+    """what PointHeadBox and PointIntraPartOffsetHead share: the refusals by key, the box coder, the fused targets and loss"""
+    HEAD = None             # the registry name
+
+    def _configure(self, num_class, model_cfg, has_box, has_part, predict_boxes_when_training):
+        self.model_cfg = model_cfg
+        self.num_class = int(num_class)
+        self.predict_boxes_when_training = predict_boxes_when_training
+        self.forward_ret_dict = None
+        self._branches = (bool(has_box), bool(has_part))
+        head = self.HEAD
+
+        def no(key, why):
+            raise L.PcdError(f"{head}: {key} {why} is not supported by the HIP point head")
+        name = _get(model_cfg, 'NAME', head)
+        if name != head:
+            no('NAME', f"= {name!r}")
+        ta = _get(model_cfg, 'TARGET_CONFIG')
+        if ta is None or _get(ta, 'GT_EXTRA_WIDTH', None) is None:
+            no('TARGET_CONFIG.GT_EXTRA_WIDTH', 'missing')
+        self.extra_width = tuple(float(v) for v in _get(ta, 'GT_EXTRA_WIDTH'))
+        if len(self.extra_width) != 3:
+            no('TARGET_CONFIG.GT_EXTRA_WIDTH', f"with {len(self.extra_width)} values")
+        for k in ('use_ball_constraint', 'USE_BALL_CONSTRAINT'):
+            if _get(ta, k, False):
+                no(f'TARGET_CONFIG.{k}', '= True')
+        for key, need in (('CLS_FC', True), ('REG_FC', has_box), ('PART_FC', has_part)):
+            if need and _get(model_cfg, key, None) is None:
+                no(key, 'missing')
+        self.box_coder = None
+        if has_box:
+            coder = _get(ta, 'BOX_CODER', None)
+            if coder != 'PointResidualCoder':
+                no('TARGET_CONFIG.BOX_CODER', f"= {coder!r}")
+            self.box_coder = PointResidualCoder(**(_get(ta, 'BOX_CODER_CONFIG', None) or {}))
+            if self.box_coder.use_mean_size and self.num_class > self.box_coder.mean_size.shape[0]:
+                no('TARGET_CONFIG.BOX_CODER_CONFIG.mean_size', f"with {self.box_coder.mean_size.shape[0]} rows for {self.num_class} classes")
+        lc = _get(model_cfg, 'LOSS_CONFIG')
+        lw = _get(lc, 'LOSS_WEIGHTS', None) if lc is not None else None
+        if lw is None:
+            no('LOSS_CONFIG.LOSS_WEIGHTS', 'missing')
+        wanted = [('point_cls_weight', True), ('point_box_weight', has_box), ('point_part_weight', has_part)]
+        for key, need in wanted:
+            if need and _get(lw, key, None) is None:
+                no(f'LOSS_CONFIG.LOSS_WEIGHTS.{key}', 'missing')
+        self.point_cls_weight = float(_get(lw, 'point_cls_weight'))
+        self.point_box_weight = float(_get(lw, 'point_box_weight')) if has_box else 0.0
+        self.point_part_weight = float(_get(lw, 'point_part_weight')) if has_part else 0.0
+        if has_box:
+            # (the reference itself fails with any other LOSS_REG here: F.smooth_l1_loss / F.l1_loss take no `weights`)
+            reg = _get(lc, 'LOSS_REG', None)
+            if reg != 'WeightedSmoothL1Loss':
+                no('LOSS_CONFIG.LOSS_REG', f"= {reg!r}")
+            cw = _get(lw, 'code_weights', None)
+            if cw is None or len(cw) != 8:
+                no('LOSS_CONFIG.LOSS_WEIGHTS.code_weights', 'missing' if cw is None else f"with {len(cw)} values")
+            # follows .cuda() / .to() with the module; not in the state dict (the reference keeps it on its loss module)
+            self.register_buffer('_code_weights', torch.tensor([float(v) for v in cw], dtype=torch.float32), persistent=False)
+
+    make_fc_layers = staticmethod(PointHeadSimple.make_fc_layers)
+
+    def _apply(self, fn, *args, **kwargs):
+        """.cuda() / .to(): the coder's mean-size table follows the module, so that a captured step never copies it"""
+        out = super()._apply(fn, *args, **kwargs)
+        cw = getattr(self, '_code_weights', None)
+        if cw is not None and cw.is_cuda and self.box_coder is not None:
+            self.box_coder.mean_size_on(cw.device)
+        return out
+
+    def _mean_size(self, device):
+        return self.box_coder.mean_size_on(device) if self.box_coder is not None else None
+
+    def _assign(self, input_dict, ret_box_labels, ret_part_labels):
+        labels, box, part, num_pos = assign_targets_full(
+            input_dict['point_coords'], input_dict['gt_boxes'], self.extra_width, self.num_class,
+            mean_size=self._mean_size(input_dict['point_coords'].device) if ret_box_labels else None,
+            ret_box_labels=ret_box_labels, ret_part_labels=ret_part_labels)
+        return {'point_cls_labels': labels, 'point_box_labels': box, 'point_part_labels': part, 'point_pos_num': num_pos}
+
+    def _losses(self):
+        """ONE fused call per get_loss / get_*_layer_loss: float32 [4] = total, cls, box, part (+ num_pos)"""
+        f = self.forward_ret_dict
+        labels = f['point_cls_labels'].view(-1)
+        num_pos = f.get('point_pos_num')
+        if num_pos is None:                       # labels that did not come from assign_targets
+            num_pos = (labels > 0).sum().to(torch.int32).reshape(1)
+        box = f.get('point_box_preds') if self._branches[0] else None
+        part = f.get('point_part_preds') if self._branches[1] else None
+        out = point_head_loss(
+            f['point_cls_preds'].view(-1, self.num_class), labels, num_pos, self.num_class, self.point_cls_weight,
+            box_preds=box, box_labels=f.get('point_box_labels') if box is not None else None,
+            code_weights=getattr(self, '_code_weights', None) if box is not None else None, box_weight=self.point_box_weight,
+            part_preds=part, part_labels=f.get('point_part_labels') if part is not None else None,
+            part_weight=self.point_part_weight)
+        return out, num_pos
+
+    def _term(self, k, name, tb_dict):
+        out, num_pos = self._losses()
+        tb_dict = {} if tb_dict is None else tb_dict
+        tb_dict[name] = out[k].detach()
+        if k == 1:
+            tb_dict['point_pos_num'] = num_pos[0].float()
+        return out[k], tb_dict
+
+    def get_cls_layer_loss(self, tb_dict=None):
+        """point_head_template.py:131-155; the tb_dict values are device scalars"""
+        return self._term(1, 'point_loss_cls', tb_dict)
+
+    def get_box_layer_loss(self, tb_dict=None):
+        """point_head_template.py:172-191"""
+        return self._term(2, 'point_loss_box', tb_dict)
+
+    def get_part_layer_loss(self, tb_dict=None):
+        """point_head_template.py:157-170"""
+        return self._term(3, 'point_loss_part', tb_dict)
+
+    def get_loss(self, tb_dict=None):
+        """point_head_box.py:61-69 / point_intra_part_head.py:68-77: one forward launch (+ the ordered finish) for all terms,
+        one backward launch; tb_dict holds device scalars"""
+        tb_dict = {} if tb_dict is None else tb_dict
+        out, num_pos = self._losses()
+        tb_dict.update({'point_loss_cls': out[1].detach(), 'point_pos_num': num_pos[0].float()})
+        if self._branches[1]:
+            tb_dict['point_loss_part'] = out[3].detach()
+        if self._branches[0]:
+            tb_dict['point_loss_box'] = out[2].detach()
+        return out[0], tb_dict
+
+    def generate_predicted_boxes(self, points, point_cls_preds, point_box_preds):
+        """point_head_template.py:193-207 through pcd_point_head_decode: (point_cls_preds, float32 [N, 7] boxes); the boxes
+        carry no gradient"""
+        if not point_box_preds.is_cuda:
+            raise L.PcdError(f"{self.HEAD}.generate_predicted_boxes needs HIP device tensors (there is no CPU fallback)")
+        boxes = decode_boxes(point_box_preds, points, self._mean_size(point_box_preds.device), cls_preds=point_cls_preds)
+        return point_cls_preds, boxes
+
+    def _predict(self, batch_dict, point_cls_preds, point_box_preds):
+        point_cls_preds, point_box_preds = self.generate_predicted_boxes(
+            points=batch_dict['point_coords'][:, 1:4], point_cls_preds=point_cls_preds, point_box_preds=point_box_preds)
+        batch_dict['batch_cls_preds'] = point_cls_preds
+        batch_dict['batch_box_preds'] = point_box_preds
+        batch_dict['batch_index'] = batch_dict['point_coords'][:, 0]
+        batch_dict['cls_preds_normalized'] = False
+
+
+class PointHeadBox(_PointHeadWithBranches):
+    """point_head_box.py:7-115 (PointRCNN) + point_head_template.py (module docstring)."""
+    HEAD = 'PointHeadBox'
+
+    def __init__(self, num_class, input_channels, model_cfg, predict_boxes_when_training=False, **kwargs):
+        super().__init__()
+        self._configure(num_class, model_cfg, True, False, predict_boxes_when_training)
+        self.use_before_fusion = bool(_get(model_cfg, 'USE_POINT_FEATURES_BEFORE_FUSION', False))
+        self.cls_layers = self.make_fc_layers(fc_cfg=_get(model_cfg, 'CLS_FC'), input_channels=input_channels,
+                                              output_channels=self.num_class)
+        self.box_layers = self.make_fc_layers(fc_cfg=_get(model_cfg, 'REG_FC'), input_channels=input_channels,
+                                              output_channels=self.box_coder.code_size)
+
+    def assign_targets(self, input_dict):
+        """point_head_box.py:32-59: point_cls_labels int64 [N], point_box_labels f32 [N, 8], point_part_labels None
+        (+ 'point_pos_num', device int32 [1])"""
+        return self._assign(input_dict, True, False)
+
+    def forward(self, batch_dict):
+        """point_head_box.py:71-115"""
+        if self.use_before_fusion:
+            point_features = batch_dict['point_features_before_fusion']
+        else:
+            point_features = batch_dict['point_features']
+        point_cls_preds = self.cls_layers(point_features)  # (total_points, num_class)
+        point_box_preds = self.box_layers(point_features)  # (total_points, box_code_size)
+        point_cls_preds_max, _ = point_cls_preds.max(dim=-1)
+        batch_dict['point_cls_scores'] = torch.sigmoid(point_cls_preds_max)
+        ret_dict = {'point_cls_preds': point_cls_preds, 'point_box_preds': point_box_preds}
+        if self.training:
+            targets_dict = self.assign_targets(batch_dict)
+            ret_dict['point_cls_labels'] = targets_dict['point_cls_labels']
+            ret_dict['point_box_labels'] = targets_dict['point_box_labels']
+            ret_dict['point_pos_num'] = targets_dict['point_pos_num']
+        if not self.training or self.predict_boxes_when_training:
+            self._predict(batch_dict, point_cls_preds, point_box_preds)
+        self.forward_ret_dict = ret_dict
+        return batch_dict
+
+
+class PointIntraPartOffsetHead(_PointHeadWithBranches):
+    """point_intra_part_head.py:7-127 (Part-A2, Part-A2-free) + point_head_template.py (module docstring)."""
+    HEAD = 'PointIntraPartOffsetHead'
+
+    def __init__(self, num_class, input_channels, model_cfg, predict_boxes_when_training=False, **kwargs):
+        super().__init__()
+        has_box = _get(_get(model_cfg, 'TARGET_CONFIG') or {}, 'BOX_CODER', None) is not None
+        self._configure(num_class, model_cfg, has_box, True, predict_boxes_when_training)
+        self.cls_layers = self.make_fc_layers(fc_cfg=_get(model_cfg, 'CLS_FC'), input_channels=input_channels,
+                                              output_channels=self.num_class)
+        self.part_reg_layers = self.make_fc_layers(fc_cfg=_get(model_cfg, 'PART_FC'), input_channels=input_channels,
+                                                   output_channels=3)
+        if has_box:
+            self.box_layers = self.make_fc_layers(fc_cfg=_get(model_cfg, 'REG_FC'), input_channels=input_channels,
+                                                  output_channels=self.box_coder.code_size)
+        else:
+            self.box_layers = None
+
+    def assign_targets(self, input_dict):
+        """point_intra_part_head.py:39-66: point_cls_labels int64 [N], point_part_labels f32 [N, 3], point_box_labels f32
+        [N, 8] with a box branch, else None (+ 'point_pos_num', device int32 [1])"""
+        return self._assign(input_dict, self.box_layers is not None, True)
+
+    def forward(self, batch_dict):
+        """point_intra_part_head.py:79-127"""
+        point_features = batch_dict['point_features']
+        point_cls_preds = self.cls_layers(point_features)  # (total_points, num_class)
+        point_part_preds = self.part_reg_layers(point_features)
+        ret_dict = {'point_cls_preds': point_cls_preds, 'point_part_preds': point_part_preds}
+        if self.box_layers is not None:
+            point_box_preds = self.box_layers(point_features)
+            ret_dict['point_box_preds'] = point_box_preds
+        point_cls_scores = torch.sigmoid(point_cls_preds)
+        point_part_offset = torch.sigmoid(point_part_preds)
+        batch_dict['point_cls_scores'], _ = point_cls_scores.max(dim=-1)
+        batch_dict['point_part_offset'] = point_part_offset
+        if self.training:
+            targets_dict = self.assign_targets(batch_dict)
+            ret_dict['point_cls_labels'] = targets_dict['point_cls_labels']
+            ret_dict['point_part_labels'] = targets_dict.get('point_part_labels')
+            ret_dict['point_box_labels'] = targets_dict.get('point_box_labels')
+            ret_dict['point_pos_num'] = targets_dict['point_pos_num']
+        if self.box_layers is not None and (not self.training or self.predict_boxes_when_training):
+            self._predict(batch_dict, point_cls_preds, ret_dict['point_box_preds'])
         self.forward_ret_dict = ret_dict
         return batch_dict

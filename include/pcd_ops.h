@@ -1418,6 +1418,35 @@ int pcd_sparse_conv_subm_window_f32(const void *x, int n_rows, int c_in, const v
  *                order (bit-reproducible) and multiplied by cls_weight.  out = 4 device floats: out[0] = out[1] = the loss,
  *                out[2] = out[3] = 0 (the ordered finish pass of the anchor heads is reused).  backward: d_logits (layout
  *                and dtype of logits, every element written) = *grad_out (device f32) x d loss / d logits.
+ *   pcd_point_head_assign_targets_full: the targets of PointHeadBox (point_head_box.py:32-59) and PointIntraPartOffsetHead
+ *                (point_intra_part_head.py:39-66): assign_stack_targets with set_ignore_flag and ret_box_labels and / or
+ *                ret_part_labels (point_head_template.py:49-129), one launch for the whole stacked batch.  Labels and *num_pos
+ *                by the rules of pcd_point_head_assign_targets.  point_box_labels f32 [num_points][8] (NULL: not wanted; 16-byte
+ *                aligned) = PointResidualCoder.encode_torch (box_coder_utils.py:153-187) of the first containing box at the
+ *                point: sizes clamped to 1e-5; mean_size (DEVICE f32 [num_mean][3], num_mean <= 16; NULL / 0 =
+ *                use_mean_size False) is indexed by (int)column 7 - 1 of the GT row even when num_class == 1, CLAMPED to
+ *                [0, num_mean - 1] (the reference asserts class <= num_mean and wraps class 0 to the last row).
+ *                point_part_labels f32 [num_points][3] (NULL: not wanted) = the point in the box's frame / (dx, dy, dz) + 0.5
+ *                (:114-122; the clamped sizes when box labels are written too, as encode_torch clamps in place).  Both are
+ *                zero on every point that is not foreground; every row is written.
+ *   pcd_point_head_full_loss_forward / _backward: get_cls_layer_loss + get_box_layer_loss + get_part_layer_loss
+ *                (point_head_template.py:131-191) in one pass.  Predictions f32 or bf16 (one dtype), rows *_stride elements
+ *                apart; box_preds / part_preds NULL = the head has no such branch.  cls: as pcd_point_head_loss_forward.
+ *                box: WeightedSmoothL1Loss (loss_utils.py:338-399; nan targets ignored, code_weights = 8 device floats, beta
+ *                1/9) with weights (label > 0) / max(*num_pos, 1), x box_weight.  part: F.binary_cross_entropy(sigmoid(p), t)
+ *                over the 3 columns of the positives / (3 max(*num_pos, 1)) x part_weight, computed from the LOGIT as
+ *                t softplus(-p) + (1 - t) softplus(p) with each log term capped at 100: the reference in EXACT arithmetic
+ *                (its fp32 path rounds sigmoid(p) to 0 or 1 near |p| = 17 and then differs; this does not).  out = 4 device
+ *                floats: cls + (box + part), cls, box, part (0 for an absent branch); fixed summation order.  backward:
+ *                d_cls / d_box / d_part (layout and dtype of the predictions, every element written: zeros on ignored points
+ *                for cls, on non-positive points and nan targets for box / part); grad_out = 4 device floats, the upstream
+ *                gradients of out[0..4): a term is scaled by grad_out[0] + grad_out[1 + term].
+ *   pcd_point_head_decode: generate_predicted_boxes (point_head_template.py:193-207) + PointResidualCoder.decode_torch
+ *                (box_coder_utils.py:189-222).  box_encodings [num_points][8] (f32 / bf16, rows enc_stride apart), points f32
+ *                rows (x, y, z) point_stride apart, boxes f32 [num_points][7].  The class that picks the mean size is
+ *                pred_classes[n] (int64, 1-based) when given, else 1 + the FIRST maximum of the point's num_class logits
+ *                (dtype of the encodings); its index is clamped into the table.  PCD_ERR_UNSUPPORTED: num_mean > 16, or
+ *                num_class > num_mean without pred_classes.
  *   pcd_roiaware_pool3d_forward: roiaware_pool3d_gpu (roiaware_pool3d.cpp:29-66).  rois [num_rois][7], pts [num_pts][3],
  *                pts_feature [num_pts][channels] f32.  pts_idx_of_voxels int32 [num_rois][out_x][out_y][out_z]
  *                [max_pts_each_voxel]: slot 0 = count, then the ASCENDING indices of the voxel's points, cut after
@@ -1443,6 +1472,26 @@ int pcd_point_head_loss_forward(const void *logits, int dtype, long long row_str
 int pcd_point_head_loss_backward(const void *logits, void *d_logits, int dtype, long long row_stride,
                                  const long long *point_cls_labels, const int *num_pos, int num_points, int num_class,
                                  float cls_weight, const float *grad_out, void *stream);
+int pcd_point_head_assign_targets_full(const float *point_coords, int num_points, const float *gt_boxes, int batch, int n_boxes,
+                                       float extra_x, float extra_y, float extra_z, int num_class, const float *mean_size,
+                                       int num_mean, long long *point_cls_labels, float *point_box_labels,
+                                       float *point_part_labels, int *num_pos, void *stream);
+size_t pcd_point_head_full_loss_workspace_bytes(int num_points);
+int pcd_point_head_full_loss_forward(const void *cls_preds, long long cls_stride, const void *box_preds, long long box_stride,
+                                     const void *part_preds, long long part_stride, int dtype,
+                                     const long long *point_cls_labels, const float *point_box_labels,
+                                     const float *point_part_labels, const int *num_pos, const float *code_weights,
+                                     int num_points, int num_class, float cls_weight, float box_weight, float part_weight,
+                                     float *out, void *workspace, size_t workspace_bytes, void *stream);
+int pcd_point_head_full_loss_backward(const void *cls_preds, void *d_cls, long long cls_stride, const void *box_preds, void *d_box,
+                                      long long box_stride, const void *part_preds, void *d_part, long long part_stride, int dtype,
+                                      const long long *point_cls_labels, const float *point_box_labels,
+                                      const float *point_part_labels, const int *num_pos, const float *code_weights,
+                                      int num_points, int num_class, float cls_weight, float box_weight, float part_weight,
+                                      const float *grad_out, void *stream);
+int pcd_point_head_decode(const void *cls_preds, long long cls_stride, int num_class, const long long *pred_classes,
+                          const void *box_encodings, long long enc_stride, int dtype, const float *points, long long point_stride,
+                          const float *mean_size, int num_mean, int num_points, float *boxes, void *stream);
 int pcd_roiaware_pool3d_forward(const float *rois, int num_rois, const float *pts, int num_pts, const float *pts_feature,
                                 int channels, int out_x, int out_y, int out_z, int max_pts_each_voxel, int pool_method,
                                 int *pts_idx_of_voxels, int *argmax, float *pooled_features, void *stream);

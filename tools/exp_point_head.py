@@ -6,6 +6,10 @@ Config-4 size (PV-RCNN on Waymo): 4 frames x 4096 keypoints, 128 padded GT rows,
       the torch chain of get_cls_layer_loss (:131-155, with its two `.item()` calls) + backward -- calling this project's
       points_in_boxes_gpu, so (a) pays nothing for the reference's own point-in-box kernel;
   (b) the fused assign + loss + backward (pcd_point_head_*), eager and replayed from a captured graph.
+The same size through the box + part head (PointIntraPartOffsetHead with all three branches): (a) additionally encodes the
+box labels (encode_torch as a dozen elementwise launches per frame), rotates the part labels and runs get_part_layer_loss
+and get_box_layer_loss with their three `.item()` calls; (b) is pcd_point_head_assign_targets_full +
+pcd_point_head_full_loss_forward / _backward.
 Also: points_in_boxes_gpu on one 160 k-point frame (128 boxes), and RoIAwarePool3d forward / backward at PartA2 size
 (128 RoIs, 16384 points, 128 channels, out_size 12), max and avg.
 
@@ -67,6 +71,89 @@ def reference_cls_loss(point_cls_preds, point_cls_labels, num_class, weight):
     point_loss_cls = loss.sum() * weight
     tb = {'point_loss_cls': point_loss_cls.item(), 'point_pos_num': pos_normalizer.item()}
     return point_loss_cls, tb
+
+
+def reference_assign_full(points, gt_boxes, extend_gt_boxes, num_class, points_in_boxes_gpu, mean_size):
+    """point_head_template.py:73-129 with ret_box_labels and ret_part_labels (set_ignore_flag branch), statement by statement;
+    encode_torch (box_coder_utils.py:162-187) and rotate_points_along_z (common_utils.py) written out"""
+    import torch
+    batch_size = gt_boxes.shape[0]
+    bs_idx = points[:, 0]
+    point_cls_labels = points.new_zeros(points.shape[0]).long()
+    point_box_labels = gt_boxes.new_zeros((points.shape[0], 8))
+    point_part_labels = gt_boxes.new_zeros((points.shape[0], 3))
+    for k in range(batch_size):
+        bs_mask = (bs_idx == k)
+        points_single = points[bs_mask][:, 1:4]
+        point_cls_labels_single = point_cls_labels.new_zeros(bs_mask.sum())
+        box_idxs_of_pts = points_in_boxes_gpu(points_single.unsqueeze(dim=0), gt_boxes[k:k + 1, :, 0:7].contiguous()
+                                              ).long().squeeze(dim=0)
+        box_fg_flag = (box_idxs_of_pts >= 0)
+        extend_box_idxs_of_pts = points_in_boxes_gpu(points_single.unsqueeze(dim=0), extend_gt_boxes[k:k + 1, :, 0:7].contiguous()
+                                                     ).long().squeeze(dim=0)
+        fg_flag = box_fg_flag
+        ignore_flag = fg_flag ^ (extend_box_idxs_of_pts >= 0)
+        point_cls_labels_single[ignore_flag] = -1
+        gt_box_of_fg_points = gt_boxes[k][box_idxs_of_pts[fg_flag]]
+        point_cls_labels_single[fg_flag] = 1 if num_class == 1 else gt_box_of_fg_points[:, -1].long()
+        point_cls_labels[bs_mask] = point_cls_labels_single
+        if gt_box_of_fg_points.shape[0] > 0:
+            point_box_labels_single = point_box_labels.new_zeros((bs_mask.sum(), 8))
+            boxes, pts, gt_classes = gt_box_of_fg_points[:, :-1], points_single[fg_flag], gt_box_of_fg_points[:, -1].long()
+            boxes[:, 3:6] = torch.clamp_min(boxes[:, 3:6], min=1e-5)
+            xg, yg, zg, dxg, dyg, dzg, rg = torch.split(boxes, 1, dim=-1)
+            xa, ya, za = torch.split(pts, 1, dim=-1)
+            assert gt_classes.max() <= mean_size.shape[0]
+            point_anchor_size = mean_size[gt_classes - 1]
+            dxa, dya, dza = torch.split(point_anchor_size, 1, dim=-1)
+            diagonal = torch.sqrt(dxa ** 2 + dya ** 2)
+            xt = (xg - xa) / diagonal
+            yt = (yg - ya) / diagonal
+            zt = (zg - za) / dza
+            dxt = torch.log(dxg / dxa)
+            dyt = torch.log(dyg / dya)
+            dzt = torch.log(dzg / dza)
+            point_box_labels_single[fg_flag] = torch.cat([xt, yt, zt, dxt, dyt, dzt, torch.cos(rg), torch.sin(rg)], dim=-1)
+            point_box_labels[bs_mask] = point_box_labels_single
+        point_part_labels_single = point_part_labels.new_zeros((bs_mask.sum(), 3))
+        transformed_points = points_single[fg_flag] - gt_box_of_fg_points[:, 0:3]
+        angle = -gt_box_of_fg_points[:, 6]
+        cosa, sina = torch.cos(angle), torch.sin(angle)
+        zeros, ones = angle.new_zeros(angle.shape[0]), angle.new_ones(angle.shape[0])
+        rot_matrix = torch.stack((cosa, sina, zeros, -sina, cosa, zeros, zeros, zeros, ones), dim=1).view(-1, 3, 3).float()
+        transformed_points = torch.matmul(transformed_points.view(-1, 1, 3), rot_matrix).view(-1, 3)
+        offset = torch.tensor([0.5, 0.5, 0.5]).view(1, 3).type_as(transformed_points)
+        point_part_labels_single[fg_flag] = (transformed_points / gt_box_of_fg_points[:, 3:6]) + offset
+        point_part_labels[bs_mask] = point_part_labels_single
+    return point_cls_labels, point_box_labels, point_part_labels
+
+
+def reference_box_part_loss(point_cls_labels, point_box_preds, point_box_labels, point_part_preds, point_part_labels, code_weights,
+                            box_weight, part_weight):
+    """get_part_layer_loss and get_box_layer_loss (point_head_template.py:157-191, loss_utils.py:372-399), statement by
+    statement, their three .item() calls included"""
+    import torch
+    import torch.nn.functional as F
+    pos_mask = point_cls_labels > 0
+    pos_normalizer = max(1, (pos_mask > 0).sum().item())
+    point_loss_part = F.binary_cross_entropy(torch.sigmoid(point_part_preds), point_part_labels, reduction='none')
+    point_loss_part = (point_loss_part.sum(dim=-1) * pos_mask.float()).sum() / (3 * pos_normalizer)
+    point_loss_part = point_loss_part * part_weight
+    tb = {'point_loss_part': point_loss_part.item()}
+    reg_weights = pos_mask.float()
+    pos_normalizer = pos_mask.sum().float()
+    reg_weights /= torch.clamp(pos_normalizer, min=1.0)
+    inp, target, weights = point_box_preds[None, ...], point_box_labels[None, ...], reg_weights[None, ...]
+    target = torch.where(torch.isnan(target), inp, target)
+    diff = inp - target
+    diff = diff * code_weights.view(1, 1, -1)
+    n = torch.abs(diff)
+    beta = 1.0 / 9.0
+    loss = torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta)
+    loss = loss * weights.unsqueeze(-1)
+    point_loss_box = loss.sum() * box_weight
+    tb['point_loss_box'] = point_loss_box.item()
+    return point_loss_part, point_loss_box, tb
 
 
 def timed(fn, iters=ITERS):
@@ -154,6 +241,52 @@ def main():
     for k, v in t.items():
         result[f"point_head_{k}_us"] = [round(x, 1) for x in v]
         print(f"point head, assign + loss + backward, {k:22s}: median {v[0]:8.1f} us  (min {v[1]:.1f}, max {v[2]:.1f})")
+
+    # ---- the same size through the box + part head (PointIntraPartOffsetHead with all three branches, Part-A2-free):
+    #      targets with box and part labels + the three losses + backward
+    mean_cpu = torch.tensor([[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]])
+    mean_dev = mean_cpu.cuda()
+    code_w = torch.ones(8, device="cuda")
+    WB, WP = 1.0, 1.0
+    box_preds = torch.randn(B * P, 8, device="cuda", requires_grad=True)
+    part_preds = torch.randn(B * P, 3, device="cuda", requires_grad=True)
+    preds = [logits, box_preds, part_preds]
+
+    def ref_full_step():
+        ext = gtd.clone()
+        ext[:, :, 3:6] += gtd.new_tensor(extra)[None, None, :]
+        labels, bl, pl = reference_assign_full(pc, gtd, ext, NC, RP.points_in_boxes_gpu, mean_dev)
+        loss_cls, _ = reference_cls_loss(logits, labels, NC, W)
+        loss_part, loss_box, _ = reference_box_part_loss(labels, box_preds, bl, part_preds, pl, code_w, WB, WP)
+        loss = loss_cls + loss_part
+        loss += loss_box
+        return labels, loss, torch.autograd.grad(loss, preds)
+
+    def fused_full_step():
+        labels, bl, pl, num_pos = PH.assign_targets_full(pc, gtd, extra, NC, mean_size=mean_dev, ret_box_labels=True,
+                                                         ret_part_labels=True)
+        out = PH.point_head_loss(logits, labels, num_pos, NC, W, box_preds=box_preds, box_labels=bl, code_weights=code_w,
+                                 box_weight=WB, part_preds=part_preds, part_labels=pl, part_weight=WP)
+        return labels, out[0], torch.autograd.grad(out[0], preds)
+
+    la, lossa, ga = ref_full_step()
+    lb2, lossb2, gb = fused_full_step()
+    assert torch.equal(la, lb2), "the fused labels differ from the reference formulation's"
+    assert abs(float(lossa) - float(lossb2)) <= 1e-5 * abs(float(lossa))
+    assert all(float((p - q).abs().max()) <= 1e-5 * float(p.abs().max()) for p, q in zip(ga, gb))
+    lossb2 = lossb2.detach().clone()
+    del la, lossa, ga, gb
+    torch.cuda.synchronize()
+    graph_full = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph_full):
+        static_full = fused_full_step()
+    graph_full.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(static_full[0], lb2) and torch.equal(static_full[1], lossb2)
+    t = compare({"reference_formulation": ref_full_step, "fused_eager": fused_full_step, "fused_graph": graph_full.replay})
+    for k, v in t.items():
+        result[f"point_head_box_part_{k}_us"] = [round(x, 1) for x in v]
+        print(f"box + part head, assign + 3 losses + backward, {k:22s}: median {v[0]:8.1f} us  (min {v[1]:.1f}, max {v[2]:.1f})")
 
     # ---- one 160 k-point frame through points_in_boxes_gpu
     P1 = 160000
