@@ -416,15 +416,6 @@ __global__ __launch_bounds__(256) void ph_decode_kernel(const void *__restrict__
 
 // ---------------------------------------------------------------------------------------------------------------------
 // RoI-aware pooling
-__device__ __forceinline__ int ra_voxel_index(float local, float d, float res, int out) {
-    // int((local + d / 2) / res) clamped to [0, out - 1]   (roiaware_pool3d_kernel.cu:60-70).  nan and every negative
-    // quotient give 0: the reference's unsigned compare would send a quotient <= -1 to out - 1, which local + d / 2 >=
-    // -MARGIN makes unreachable for a box wider than 1e-5 m per voxel
-    const float q = __fdiv_rn(local + d / 2.f, res);
-    if (!(q >= 1.f)) return 0;
-    return q < (float)out ? (int)q : out - 1;
-}
-
 __global__ __launch_bounds__(256) void ra_collect_kernel(const float *__restrict__ rois, const float *__restrict__ pts, int np, int ox,
                                                          int oy, int oz, int mpv, int *__restrict__ lists) {
     extern __shared__ int s_cnt[];                    // [ox * oy * oz]

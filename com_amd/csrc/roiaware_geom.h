@@ -59,3 +59,15 @@ __host__ __device__ inline bool ra_point_in_box(const RaBox &b, float x, float y
     ra_local(b, x, y, lx, ly);
     return ra_xy_inside(lx, ly, b.tx, b.ty);
 }
+
+#ifdef __HIPCC__
+// The voxel of a point inside a RoI along one axis (RoI-aware pooling, roiaware.hip and parta2.hip):
+// int((local + d / 2) / res) clamped to [0, out - 1]   (roiaware_pool3d_kernel.cu:60-70).  nan and every negative
+// quotient give 0: the reference's unsigned compare would send a quotient <= -1 to out - 1, which local + d / 2 >=
+// -MARGIN makes unreachable for a box wider than 1e-5 m per voxel
+__device__ __forceinline__ int ra_voxel_index(float local, float d, float res, int out) {
+    const float q = __fdiv_rn(local + d / 2.f, res);
+    if (!(q >= 1.f)) return 0;
+    return q < (float)out ? (int)q : out - 1;
+}
+#endif

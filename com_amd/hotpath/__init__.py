@@ -13,5 +13,5 @@ from .anchor_curriculum_head import (CurriculumAnchorHeadSingle, CurriculumAncho
                                      CurriculumAnchorHeadSingle_car_x2, CurriculumAnchorHeadSingle_x1)
 from .anchor_head_multi import AnchorHeadMulti, SingleHead  # noqa: F401
 from .point_head import PointHeadBox, PointHeadSimple, PointIntraPartOffsetHead, PointResidualCoder  # noqa: F401
-from .roi_head import ProposalTargetLayer, PVRCNNHead, RoIHeadTemplate, VoxelRCNNHead  # noqa: F401
+from .roi_head import PartA2FCHead, ProposalTargetLayer, PVRCNNHead, RoIHeadTemplate, VoxelRCNNHead, parta2_pool  # noqa: F401
 from .second_head import SECONDHead  # noqa: F401

@@ -19,7 +19,10 @@ Scope: code_size 7, ResidualCoder, BinaryCrossEntropy, smooth-l1, class-agnostic
 construction with a PcdError that names the key.
 
 `VoxelRCNNHead` (pcdet/models/roi_heads/voxelrcnn_head.py) shares all of that through `RoIHeadTemplate` and pools over the
-sparse levels themselves (com_amd/csrc/voxelpool.hip; its class docstring)."""
+sparse levels themselves (com_amd/csrc/voxelpool.hip; its class docstring).
+
+`PartA2FCHead` (pcdet/models/roi_heads/partA2_head.py) shares it too; its RoI-aware pooling of the whole stacked batch goes
+straight to sparse rows (com_amd/csrc/parta2.hip, `parta2_pool`; its class docstring)."""
 import ctypes
 
 import numpy as np
@@ -28,6 +31,9 @@ import torch.nn as nn
 
 from .. import _lib as L
 from .. import iou3d_nms
+from .. import ops
+from .. import spconv
+from ..spconv import functional as Fsp
 from ._maps import dtype_code as _dt
 from ._maps import like as _like
 from .dense2d import _get
@@ -732,6 +738,260 @@ class VoxelRCNNHead(RoIHeadTemplate):
         shared_features = self.shared_fc_layer(pooled_features)
         rcnn_cls = self.cls_pred_layer(self.cls_fc_layers(shared_features))
         rcnn_reg = self.reg_pred_layer(self.reg_fc_layers(shared_features))
+        if not self.training:
+            batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(
+                batch_size=batch_dict['batch_size'], rois=batch_dict['rois'], cls_preds=rcnn_cls, box_preds=rcnn_reg)
+            batch_dict['batch_cls_preds'] = batch_cls_preds
+            batch_dict['batch_box_preds'] = batch_box_preds
+            batch_dict['cls_preds_normalized'] = False
+        else:
+            targets_dict['rcnn_cls'] = rcnn_cls
+            targets_dict['rcnn_reg'] = rcnn_reg
+            self.forward_ret_dict = targets_dict
+        return batch_dict
+
+
+class _PartA2Pool(torch.autograd.Function):
+    """pcd_parta2_pool_plan / _forward / _backward: (coords, part_rows, rpn_rows, state); the gradient flows to point_part
+    (avg; none to the masked points) and point_features (max, through argmax)."""
+
+    @staticmethod
+    def forward(ctx, point_part, point_features, rois, point_coords, point_scores, thresh, pool_size, max_pts, max_rows, max_listed,
+                status):
+        dev = rois.device
+        B, N = int(rois.shape[0]), int(rois.shape[1])
+        P, C = int(point_features.shape[0]), int(point_features.shape[1])
+        i32 = dict(dtype=torch.int32, device=dev)
+        voxels = torch.empty((B * N, pool_size ** 3), **i32)
+        roi_counts, offsets = torch.empty((2, B * N), **i32), torch.empty((2, B * N + 1), **i32)
+        state = torch.empty((L.PCD_PARTA2_STATE_WORDS,), **i32)
+        scene = (L.ptr(rois), B, N, L.ptr(point_coords), P, L.ptr(point_part), int(point_part.stride(0)), L.ptr(point_scores),
+                 float(thresh))
+        static = max_rows is not None
+        big = 2 ** 31 - 1
+        L.check(L.lib().pcd_parta2_pool_plan(*scene, pool_size, max_pts, max_rows if static else big, max_listed if static else big,
+                                             L.ptr(voxels), L.ptr(roi_counts), L.ptr(offsets), L.ptr(state),
+                                             L.ptr(status) if static else None, L.stream_ptr()), "pcd_parta2_pool_plan")
+        if not static:
+            if torch.cuda.is_current_stream_capturing():
+                raise L.PcdError("parta2_pool: under capture the row capacity has to be given (max_rows)")
+            _, max_rows, max_listed, _ = state.tolist()          # the one read-back (the reference syncs in nonzero())
+        coords = torch.empty((max_rows, 4), **i32)
+        part_rows = torch.empty((max_rows, 4), dtype=torch.float32, device=dev)
+        rpn_rows = torch.empty((max_rows, C), dtype=torch.float32, device=dev)
+        row_entries, entries = torch.empty((max_rows, 2), **i32), torch.empty((max(max_listed, 1),), **i32)
+        argmax = torch.empty((max_rows, C), **i32)
+        L.check(L.lib().pcd_parta2_pool_forward(*scene, L.ptr(point_features), C, pool_size, max_pts, max_rows, max_listed,
+                                                L.ptr(voxels), L.ptr(offsets), L.ptr(state), L.ptr(coords), L.ptr(part_rows),
+                                                L.ptr(rpn_rows), L.ptr(row_entries), L.ptr(entries), L.ptr(argmax), L.stream_ptr()),
+                "pcd_parta2_pool_forward")
+        ctx.save_for_backward(state, row_entries, entries, argmax, point_scores)
+        ctx.meta = (P, C, max_rows, float(thresh), tuple(point_part.shape))
+        ctx.mark_non_differentiable(coords, state)
+        return coords, part_rows, rpn_rows, state
+
+    @staticmethod
+    def backward(ctx, _g_coords, g_part, g_rpn, _g_state):
+        state, row_entries, entries, argmax, point_scores = ctx.saved_tensors
+        P, C, max_rows, thresh, part_shape = ctx.meta
+        dev = state.device
+        want_part = ctx.needs_input_grad[0]
+        g_part = torch.zeros((max_rows, 4), dtype=torch.float32, device=dev) if g_part is None else g_part.contiguous().float()
+        g_rpn = torch.zeros((max_rows, C), dtype=torch.float32, device=dev) if g_rpn is None else g_rpn.contiguous().float()
+        d_part = torch.empty((P, 3), dtype=torch.float32, device=dev) if want_part else None
+        d_feat = torch.empty((P, C), dtype=torch.float32, device=dev)
+        L.check(L.lib().pcd_parta2_pool_backward(L.ptr(g_part), L.ptr(g_rpn), C, P, max_rows, L.ptr(state), L.ptr(row_entries),
+                                                 L.ptr(entries), L.ptr(argmax), L.ptr(point_scores), thresh, L.ptr(d_part),
+                                                 L.ptr(d_feat), L.stream_ptr()), "pcd_parta2_pool_backward")
+        return d_part, d_feat, None, None, None, None, None, None, None, None, None
+
+
+def parta2_pool(rois, point_coords, point_features, point_part, point_scores, score_thresh, pool_size, max_pts_each_voxel,
+                max_rows=None, max_listed=None, status=None):
+    """roiaware_pool + the nonzero() / gather of PartA2FCHead.forward (partA2_head.py:104-151, :184-195) for the whole stacked
+    batch: (coords int32 [rows, 4] as (roi, x, y, z) in nonzero()'s order, part_rows f32 [rows, 4], rpn_rows f32 [rows, C],
+    state int32 [4] on the device: rows clamped to the capacity, rows, list entries, 1 on the fake path).
+
+    rois [B, N, 7]; point_coords [P, 4] rows of (bs_idx, x, y, z); point_part [P, 3] (a view with a row stride is read in
+    place: point_coords[:, 1:4] for DISABLE_PART); point_scores [P].  max_rows None: the row count is read back once and the
+    outputs have exactly that many rows.  max_rows given (static shapes, capture): outputs of max_rows rows, cleared behind
+    state[0]; `status` (device int32 [1]) collects the overflow bits."""
+    L.require_device("parta2_pool", rois, point_coords, point_features, point_part, point_scores)
+    if rois.dim() != 3 or rois.shape[2] < 7 or point_coords.dim() != 2 or point_coords.shape[1] != 4:
+        raise L.PcdError(f"parta2_pool: rois {tuple(rois.shape)}, point_coords {tuple(point_coords.shape)}; want [B, N, 7+] and [P, 4]")
+    P = int(point_coords.shape[0])
+    scores = point_scores.detach().reshape(-1).contiguous().float()
+    if point_features.dim() != 2 or point_features.shape[0] != P or tuple(point_part.shape) != (P, 3) or scores.shape[0] != P:
+        raise L.PcdError(f"parta2_pool: point_features {tuple(point_features.shape)}, point_part {tuple(point_part.shape)}, "
+                         f"point_scores {tuple(point_scores.shape)} for {P} points")
+    if not 1 <= int(pool_size) <= L.PCD_PARTA2_MAX_POOL:
+        raise L.PcdError(f"parta2_pool: POOL_SIZE {pool_size} (1 .. {L.PCD_PARTA2_MAX_POOL})")
+    if point_part.dtype != torch.float32 or (P and (point_part.stride(1) != 1 or point_part.stride(0) < 3)):
+        point_part = point_part.float().contiguous()
+    r = rois.detach()[:, :, :7].contiguous().float()
+    if max_rows is not None:
+        max_rows = int(max_rows)
+        max_listed = 4 * max_rows if max_listed is None else int(max_listed)
+        if status is None or max_rows < 1 or max_listed < 1:
+            raise L.PcdError("parta2_pool: max_rows needs a status word and positive capacities")
+    return _PartA2Pool.apply(point_part, point_features.contiguous().float(), r, point_coords.detach().contiguous().float(), scores,
+                             float(score_thresh), int(pool_size), int(max_pts_each_voxel), max_rows, max_listed, status)
+
+
+class PartA2FCHead(RoIHeadTemplate):
+    """partA2_head.py:10-224 (`ROI_HEAD.NAME: PartA2FCHead` in tools/cfgs/kitti_models/PartA2.yaml, PartA2_free.yaml and
+    waymo_models/PartA2.yaml): same constructor arguments, the modules `conv_part`, `conv_rpn`, `shared_fc_layer`,
+    `cls_layers`, `reg_layers` built and initialised as the reference builds them (a reference state dict loads with
+    strict=True), `roiaware_pool` and `forward(batch_dict)` with the reference's names and returns; everything
+    RoIHeadTemplate holds is shared with PVRCNNHead.
+
+    The pooling is `parta2_pool`: the voxel lists of the whole batch are built once and never leave their compact form, and
+    the rows come out sparse, in nonzero()'s order, with a DEVICE row count.  `conv_part` and `conv_rpn` run over ONE SubM
+    rulebook in fp32 (the fp32-exact kernels of spconv_f32.hip: the input widths 4 and `input_channels` have no bf16 window
+    kernel, and the head's rows are few), their BatchNorm through the fused kernels that respect the row count.  The first
+    shared FC runs on `dense()` as in the reference.
+
+    `max_rows` (constructor or attribute; None = eager): the row capacity of a static-shape forward.  With it nothing is read
+    back -- the fake path (fewer than three rows) fills `rcnn_cls_labels` and `reg_valid_mask` with -1 through the device
+    flag -- and forward + get_loss + backward can sit in a captured graph; `check_status()` raises when a step overflowed
+    the capacity.  Without it the row count is read back once per forward, where the reference syncs in nonzero()."""
+
+    HEAD_NAME = 'PartA2FCHead'
+
+    def __init__(self, input_channels, model_cfg, num_class=1, max_rows=None, max_listed=None, **kwargs):
+        super().__init__(num_class=num_class, model_cfg=model_cfg)
+        pool = _get(model_cfg, 'ROI_AWARE_POOL')
+        self.pool_size = int(_get(pool, 'POOL_SIZE'))
+        self.max_pts_each_voxel = int(_get(pool, 'MAX_POINTS_PER_VOXEL'))
+        self.max_rows, self.max_listed = max_rows, max_listed
+        self.pool_status = None         # device int32 [1]: overflow bits of the static-shape pooling since the last check
+        block = self.post_act_block
+        c0 = int(_get(pool, 'NUM_FEATURES')) // 2
+        self.conv_part = spconv.SparseSequential(block(4, 64, 3, padding=1, indice_key='rcnn_subm1'),
+                                                 block(64, c0, 3, padding=1, indice_key='rcnn_subm1_1'))
+        self.conv_rpn = spconv.SparseSequential(block(input_channels, 64, 3, padding=1, indice_key='rcnn_subm2'),
+                                                block(64, c0, 3, padding=1, indice_key='rcnn_subm1_2'))
+        pre_channel = int(_get(pool, 'NUM_FEATURES')) * self.pool_size ** 3
+        dp = _get(model_cfg, 'DP_RATIO')
+        shared_fc = list(_get(model_cfg, 'SHARED_FC'))
+        shared_fc_list = []
+        for k in range(0, shared_fc.__len__()):
+            shared_fc_list.extend([nn.Conv1d(pre_channel, shared_fc[k], kernel_size=1, bias=False), nn.BatchNorm1d(shared_fc[k]),
+                                   nn.ReLU()])
+            pre_channel = shared_fc[k]
+            if k != shared_fc.__len__() - 1 and dp > 0:
+                shared_fc_list.append(nn.Dropout(dp))
+        self.shared_fc_layer = nn.Sequential(*shared_fc_list)
+        self.cls_layers = self.make_fc_layers(input_channels=pre_channel, output_channels=self.num_class,
+                                              fc_list=_get(model_cfg, 'CLS_FC'))
+        self.reg_layers = self.make_fc_layers(input_channels=pre_channel, output_channels=self.code_size * self.num_class,
+                                              fc_list=_get(model_cfg, 'REG_FC'))
+        self.init_weights(weight_init='xavier')
+
+    @classmethod
+    def _refuse(cls, model_cfg, num_class):
+        """the configurations outside the scope of the kernels: a PcdError that names the key"""
+        no = super()._refuse(model_cfg, num_class)
+        pool = _get(model_cfg, 'ROI_AWARE_POOL', None)
+        if pool is None:
+            no('ROI_AWARE_POOL', 'missing')
+        for key in ('POOL_SIZE', 'NUM_FEATURES', 'MAX_POINTS_PER_VOXEL'):
+            if _get(pool, key, None) is None:
+                no(f'ROI_AWARE_POOL.{key}', 'missing')
+        if not isinstance(_get(pool, 'POOL_SIZE'), int) or not 1 <= _get(pool, 'POOL_SIZE') <= L.PCD_PARTA2_MAX_POOL:
+            no('ROI_AWARE_POOL.POOL_SIZE', f"= {_get(pool, 'POOL_SIZE')!r} (one int of 1 .. {L.PCD_PARTA2_MAX_POOL})")
+        if int(_get(pool, 'MAX_POINTS_PER_VOXEL')) < 2:
+            no('ROI_AWARE_POOL.MAX_POINTS_PER_VOXEL', f"= {_get(pool, 'MAX_POINTS_PER_VOXEL')!r}")
+        nf = int(_get(pool, 'NUM_FEATURES'))
+        if nf < 8 or nf % 8 or nf > 256:
+            no('ROI_AWARE_POOL.NUM_FEATURES', f"= {nf} (a multiple of 8 up to 256: the fused BatchNorm and the fp32 conv kernels)")
+        if _get(model_cfg, 'SEG_MASK_SCORE_THRESH', None) is None:
+            no('SEG_MASK_SCORE_THRESH', 'missing')
+        if not list(_get(model_cfg, 'SHARED_FC', None) or []):
+            no('SHARED_FC', 'missing or empty')
+        return no
+
+    def init_weights(self, weight_init='xavier'):
+        """partA2_head.py:59-77"""
+        super().init_weights(weight_init)
+        nn.init.normal_(self.reg_layers[-1].weight, mean=0, std=0.001)
+
+    def post_act_block(self, in_channels, out_channels, kernel_size, indice_key, stride=1, padding=0, conv_type='subm'):
+        """partA2_head.py:79-102; the head builds 'subm' blocks only"""
+        if conv_type != 'subm':
+            raise L.PcdError(f"PartA2FCHead.post_act_block: conv_type {conv_type!r} is not supported (the head uses 'subm')")
+        return spconv.SparseSequential(spconv.SubMConv3d(in_channels, out_channels, kernel_size, bias=False, indice_key=indice_key),
+                                       nn.BatchNorm1d(out_channels, eps=1e-3, momentum=0.01), nn.ReLU())
+
+    def check_status(self):
+        """raises when a static-shape forward since the last check had more rows or list entries than its capacity (one
+        read-back: call it outside capture), after the sampler's own check"""
+        self.proposal_target_layer.check_status()
+        if self.pool_status is None or torch.cuda.is_current_stream_capturing():
+            return 0
+        bits = int(self.pool_status.item())
+        if bits:
+            self.pool_status.zero_()
+            what = " and ".join(w for b, w in ((1, f"rows (max_rows = {self.max_rows})"), (2, "list entries (max_listed)")) if bits & b)
+            raise L.PcdError(f"PartA2FCHead: the pooled {what} did not fit the static capacity; rows were dropped")
+        return 0
+
+    def roiaware_pool(self, batch_dict):
+        """partA2_head.py:104-151 and :184-195 -> (coords, part_rows, rpn_rows, state) of parta2_pool"""
+        point_coords = batch_dict['point_coords']
+        disable_part = bool(_get(self.model_cfg, 'DISABLE_PART', False))
+        part = point_coords[:, 1:4] if disable_part else batch_dict['point_part_offset']
+        if self.max_rows is not None and (self.pool_status is None or self.pool_status.device != point_coords.device):
+            self.pool_status = torch.zeros((1,), dtype=torch.int32, device=point_coords.device)
+        return parta2_pool(batch_dict['rois'], point_coords, batch_dict['point_features'], part, batch_dict['point_cls_scores'],
+                           _get(self.model_cfg, 'SEG_MASK_SCORE_THRESH'), self.pool_size, self.max_pts_each_voxel,
+                           max_rows=self.max_rows, max_listed=self.max_listed, status=self.pool_status)
+
+    @staticmethod
+    def _convs(seq, x, rb, num_rows):
+        """conv_part / conv_rpn over the shared rulebook: SubMConv3d in fp32, BatchNorm1d + ReLU fused, both by the row count"""
+        for blk in seq:
+            conv, bn = blk[0], blk[1]
+            x = Fsp.SparseConvExactFunction.apply(x, conv.weight, conv.bias, rb)
+            x = Fsp.batch_norm_act(bn, x, None, True, num_rows)
+        return x
+
+    def sparse_features(self, batch_dict):
+        """partA2_head.py:179-205: pooling, conv_part / conv_rpn, dense() -> (the input of shared_fc_layer
+        [B_rcnn, NUM_FEATURES * POOL_SIZE^3, 1], the pooling's state words).  Everything in here runs on this project's kernels.
+        Eager (no max_rows): the row count is exact and no device count is passed on, so a BatchNorm the fused kernels do not
+        serve (SyncBatchNorm on several ranks) goes through torch's own module."""
+        coords, part_rows, rpn_rows, state = self.roiaware_pool(batch_dict)
+        batch_size_rcnn = int(batch_dict['rois'].shape[0] * batch_dict['rois'].shape[1])
+        sparse_shape = [self.pool_size] * 3
+        num_rows = state[0:1] if self.max_rows is not None else None
+        rb = ops.rulebook_subm(coords, batch_size_rcnn, sparse_shape, 3, 1, want_pairs=torch.is_grad_enabled(), n_dev=num_rows)
+        x_part = self._convs(self.conv_part, part_rows, rb, num_rows)
+        x_rpn = self._convs(self.conv_rpn, rpn_rows, rb, num_rows)
+        merged_feature = torch.cat((x_rpn, x_part), dim=1)
+        dense = Fsp.bev_dense(merged_feature, coords, batch_size_rcnn, sparse_shape, num_rows)
+        return dense.view(batch_size_rcnn, -1, 1), state
+
+    def forward(self, batch_dict):
+        """partA2_head.py:163-224 (+ the `roi_targets_dict` hook PVRCNNHead.forward has)"""
+        nms = _get(self.model_cfg, 'NMS_CONFIG')
+        targets_dict = self.proposal_layer(batch_dict, nms_config=_get(nms, 'TRAIN' if self.training else 'TEST'))
+        if self.training:
+            targets_dict = batch_dict.get('roi_targets_dict', None)
+            if targets_dict is None:
+                targets_dict = self.assign_targets(batch_dict)
+                batch_dict['rois'] = targets_dict['rois']
+                batch_dict['roi_labels'] = targets_dict['roi_labels']
+        shared_feature, state = self.sparse_features(batch_dict)
+        if self.training:
+            # fewer than three rows: these are invalid samples (:186-191), by the device flag
+            invalid = state[3] > 0
+            targets_dict = dict(targets_dict)
+            targets_dict['rcnn_cls_labels'] = targets_dict['rcnn_cls_labels'].masked_fill(invalid, -1)
+            targets_dict['reg_valid_mask'] = targets_dict['reg_valid_mask'].masked_fill(invalid, -1)
+        shared_feature = self.shared_fc_layer(shared_feature)
+        rcnn_cls = self.cls_layers(shared_feature).transpose(1, 2).contiguous().squeeze(dim=1)  # (B, 1 or 2)
+        rcnn_reg = self.reg_layers(shared_feature).transpose(1, 2).contiguous().squeeze(dim=1)  # (B, C)
         if not self.training:
             batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(
                 batch_size=batch_dict['batch_size'], rois=batch_dict['rois'], cls_preds=rcnn_cls, box_preds=rcnn_reg)

@@ -1620,6 +1620,56 @@ int pcd_second_head_iou_loss_backward(const void *logits, int dtype, long long s
 int pcd_points_in_boxes_count(const float *points, int num_points, const float *boxes, int batch, int num_boxes, int *counts,
                               void *stream);
 
+/* ============================================================================================
+ * (f8) PartA2FCHead's RoI-aware pooling for the whole stacked batch, straight to sparse rows -- replaces roiaware_pool
+ *      (pcdet/models/roi_heads/partA2_head.py:104-151: a host loop over frames, RoIAwarePool3d 'avg' over the part features
+ *      and 'max' over the RPN features per frame) and the nonzero() / gather of forward (:184-195).  The list contract is
+ *      that of pcd_roiaware_pool3d_forward: a voxel's points in ascending index within the frame, cut after
+ *      max_pts_each_voxel - 1 entries; avg = sum in list order / number listed, max = first strict maximum.  No
+ *      [RoIs][voxels][max_pts] list, no [RoIs][points] mask and no dense pooled tensor is allocated; a fixed number of
+ *      launches serves the batch.  rois f32 [batch][num_rois][7]; point_coords f32 [num_points][4] rows of (bs_idx, x, y, z),
+ *      in any order; point_part rows of 3 f32, part_stride elements apart (point_part_offset, or point_coords + 1 with
+ *      stride 4 for DISABLE_PART); point_scores f32 [num_points].  The part features of a point are (part[0..3), score) with
+ *      the first three zeroed where score < score_thresh (strict, :125).
+ *   pcd_parta2_pool_plan: the counting pass.  voxels int32 [batch * num_rois][pool_size^3] receives the number listed per
+ *                voxel, | 1 << 30 where the voxel is a ROW: the fp32 sum ((p0 + p1) + p2) + p3 of its four pooled part
+ *                features is non-zero (:185).  roi_counts int32 [2][batch * num_rois] (rows, listed points) and offsets
+ *                int32 [2][batch * num_rois + 1] (their exclusive scans, totals last) are scratch for the forward.  state =
+ *                PCD_PARTA2_STATE_WORDS device int32: [0] the row count clamped to max_rows (the n_dev of the sparse
+ *                tensors), [1] the row count, [2] the number of list entries, [3] 1 on the fake path.  Fewer than three rows
+ *                (:186-191): the fake path, one row per RoI at cell (0, 0, 0) with whatever was pooled there, row count =
+ *                batch * num_rois.  max_rows / max_listed = the capacities the forward will be given (INT_MAX: the caller
+ *                reads state back and allocates); *status (device int32, may be NULL, cleared by the caller) |= 1 when the
+ *                rows, 2 when the list entries do not fit.
+ *   pcd_parta2_pool_forward: coords int32 [max_rows][4] rows of (roi, x, y, z) in the ascending order nonzero() gives,
+ *                part_rows f32 [max_rows][4], rpn_rows f32 [max_rows][channels], and the record the backward reads:
+ *                row_entries int32 [max_rows][2] (start, count) into entries int32 [max_listed] (point indices in list
+ *                order), argmax int32 [max_rows][channels] (-1: empty).  Rows behind state[0] are cleared (argmax -1); rows
+ *                and entries that do not fit are dropped.  coords and part_rows 16-byte aligned.
+ *   pcd_parta2_pool_backward: grad_part f32 [num_points][3] (NULL: not wanted) and grad_features f32
+ *                [num_points][channels], every element written: grad_part_rows[.][0..3) / count over the entries whose score
+ *                is not below the threshold (none to the score), grad_rpn_rows through argmax.  Float atomics: the order of
+ *                the additions into one point's row is not fixed.
+ *   PCD_ERR_UNSUPPORTED: pool_size above PCD_PARTA2_MAX_POOL, more than 65535 RoIs, or RoIs x min(num_points, pool_size^3 x
+ *                (max_pts_each_voxel - 1)), the bound of the list entries (int32 offsets), not below 2^31.  No entry point reads
+ *                anything back.
+ * ============================================================================================ */
+#define PCD_PARTA2_MAX_POOL 14
+#define PCD_PARTA2_STATE_WORDS 4
+int pcd_parta2_pool_plan(const float *rois, int batch, int num_rois, const float *point_coords, int num_points,
+                         const float *point_part, long long part_stride, const float *point_scores, float score_thresh,
+                         int pool_size, int max_pts_each_voxel, int max_rows, int max_listed, int *voxels, int *roi_counts,
+                         int *offsets, int *state, int *status, void *stream);
+int pcd_parta2_pool_forward(const float *rois, int batch, int num_rois, const float *point_coords, int num_points,
+                            const float *point_part, long long part_stride, const float *point_scores, float score_thresh,
+                            const float *point_features, int channels, int pool_size, int max_pts_each_voxel, int max_rows,
+                            int max_listed, const int *voxels, const int *offsets, const int *state, int *coords,
+                            float *part_rows, float *rpn_rows, int *row_entries, int *entries, int *argmax, void *stream);
+int pcd_parta2_pool_backward(const float *grad_part_rows, const float *grad_rpn_rows, int channels, int num_points, int max_rows,
+                             const int *state, const int *row_entries, const int *entries, const int *argmax,
+                             const float *point_scores, float score_thresh, float *grad_part, float *grad_features,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif
