@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .hotpath import backbone3d, center_head, curriculum_head, dense2d, map_to_bev, vfe
+from .hotpath import backbone3d, center_head, curriculum_head, dense2d, map_to_bev, unet, vfe
 from .hotpath.conv2d_fast import BatchNormReLU2d
 from .spconv.conv import SparseConvolution
 
@@ -206,6 +206,23 @@ def _adopt_backbone3d(path, s, cls, **_):
     return _rehome(path, s, new)
 
 
+def _adopt_unet(path, s, cls, **_):
+    cfg, cin, grid = _backbone_args(path, s)
+    cfg = dict(cfg) if hasattr(cfg, "keys") else {}
+    cfg["RETURN_ENCODED_TENSOR"] = getattr(s, "conv_out", None) is not None
+    if cfg["RETURN_ENCODED_TENSOR"]:
+        try:
+            cfg["last_pad"] = s.conv_out._modules["0"].padding
+        except (AttributeError, KeyError) as exc:
+            raise _Refuse(path, f"no conv_out[0] conv ({exc})") from exc
+    for a in ("voxel_size", "point_cloud_range"):
+        if getattr(s, a, None) is None:
+            raise _Refuse(path, f"no {a}")
+    new = _build(lambda: cls(cfg, cin, grid, s.voxel_size, s.point_cloud_range))
+    _match(path, s, new)
+    return _rehome(path, s, new)
+
+
 def _adopt_height_compression(path, s, channels_last=True, **_):
     cfg = dict(s.model_cfg) if hasattr(s.model_cfg, "keys") else {"NUM_BEV_FEATURES": s.num_bev_features}
     cfg["CHANNELS_LAST"] = bool(channels_last)
@@ -250,6 +267,7 @@ RECOGNISED = {
     "MeanVFE": (_adopt_vfe, vfe.MeanVFE),
     "VoxelResBackBone8x": (_adopt_backbone3d, backbone3d.VoxelResBackBone8x),
     "VoxelBackBone8x": (_adopt_backbone3d, backbone3d.VoxelBackBone8x),
+    "UNetV2": (_adopt_unet, unet.UNetV2),
     "HeightCompression": (_adopt_height_compression, map_to_bev.HeightCompression),
     "BaseBEVBackbone": (_adopt_bev_backbone, dense2d.BaseBEVBackbone),
     "CenterHead": (_adopt_head, center_head.CenterHead),

@@ -779,6 +779,32 @@ extern "C" int pcd_bn_forward_ld(const void *x, const void *residual, int dtype,
     return PCD_OK;
 }
 
+// The statistics half of pcd_bn_forward_ld's training form alone, for an apply pass that lives elsewhere (unet.hip): the same
+// two launches (the stats pass unless the producing conv took the sums, then the mid reduction), same values.
+extern "C" int pcd_bn_stats_mid(const void *x, int dtype, int n, int c, const int32_t *n_dev, const float *ext_partial,
+                                int ext_rows, double *mid, void *workspace, size_t workspace_bytes, void *stream) {
+    PCD_ENTER();
+    if (n <= 0 || c <= 0 || !mid || (dtype != PCD_F32 && dtype != PCD_BF16)) return PCD_ERR_INVALID_ARG;
+    if (!shape_ok(c, dtype)) return PCD_ERR_UNSUPPORTED;
+    if (ext_partial ? ext_rows < 0 : !x) return PCD_ERR_INVALID_ARG;
+    BnWs L;
+    if (!bn_ws(workspace, workspace_bytes, c, L)) return PCD_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int N = dtype == PCD_F32 ? 4 : 8;
+    const int pcs = c / N;
+    const int grid = grid_for((size_t)n * pcs, pcs);
+    if (ext_partial)
+        ;
+    else if (dtype == PCD_F32)
+        bn_stats_kernel<float><<<grid, bn_threads(pcs), bn_reduce_lds_bytes(c, 4), st>>>((const float *)x, n, n_dev, c, L.partial);
+    else
+        bn_stats_kernel<unsigned short><<<grid, bn_threads(pcs), bn_reduce_lds_bytes(c, 8), st>>>((const unsigned short *)x, n,
+                                                                                                 n_dev, c, L.partial);
+    bn_mid_kernel<<<MID_ROWS, 1024, 0, st>>>(ext_partial ? ext_partial : L.partial, ext_partial ? ext_rows : grid, c, mid);
+    PCD_RETURN_IF_LAUNCH_FAILED();
+    return PCD_OK;
+}
+
 __global__ __launch_bounds__(1024) void col_sum_finalize_kernel(const float *__restrict__ partial, int nblocks,
                                                                 int c, float *out) {
     __shared__ double lds[2 * 1024];

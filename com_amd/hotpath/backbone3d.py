@@ -33,14 +33,16 @@ def post_act_block(in_channels, out_channels, kernel_size, indice_key=None, stri
 
 
 class SparseBasicBlock(spconv.SparseModule):
-    """spconv_backbone.py:30-66 (both convs have bias=True: `bias = norm_fn is not None`)."""
+    """spconv_backbone.py:30-66 (both convs have bias=True: `bias = norm_fn is not None`); bias=False: the block of
+    spconv_unet.py:11-46, the same dataflow without conv biases."""
     expansion = 1
     fuse_identity_grad = True      # identity-branch gradient added inside conv1's dgrad kernel
 
-    def __init__(self, inplanes, planes, stride=1, norm_fn=None, downsample=None, indice_key=None):
+    def __init__(self, inplanes, planes, stride=1, norm_fn=None, downsample=None, indice_key=None, bias=None):
         super().__init__()
         assert norm_fn is not None
-        bias = norm_fn is not None
+        if bias is None:
+            bias = norm_fn is not None
         self.conv1 = spconv.SubMConv3d(inplanes, planes, kernel_size=3, stride=stride, padding=1, bias=bias,
                                        indice_key=indice_key)
         self.bn1 = norm_fn(planes)
@@ -206,12 +208,7 @@ class _BackboneBase(nn.Module):
             return
         if not hasattr(self, "_conv_list"):
             self._conv_list = [m for m in self.modules() if isinstance(m, spconv.conv.SparseConvolution)]
-            units = [[]]
-            for conv in self._conv_list:
-                if not conv.subm and units[-1]:
-                    units.append([])
-                units[-1].append(conv)
-            self._rb_units = units
+            self._rb_units = self._make_units(self._conv_list)
         cur = torch.cuda.current_stream()
         dev = x0.features.device
         side = Fsp.side_stream(dev, "rulebook")
@@ -242,6 +239,15 @@ class _BackboneBase(nn.Module):
         with torch.cuda.stream(pack_side):
             self._pack_all()
         cur.wait_stream(pack_side)
+
+    def _make_units(self, convs):
+        """The prefetcher's units: every strided conv opens one, the SubM convs behind it share its level."""
+        units = [[]]
+        for conv in convs:
+            if not conv.subm and units[-1]:
+                units.append([])
+            units[-1].append(conv)
+        return units
 
     def pack_after_update(self):
         """Pack the weights for the NEXT forward / backward now, on the current stream -- call it right after the
@@ -313,7 +319,7 @@ class _BackboneBase(nn.Module):
         x_conv4 = x4
         ops.stamp("conv4")
         hook_point("conv4")
-        out = self.conv_out(x_conv4)
+        out = self.conv_out(x_conv4) if self.conv_out is not None else None    # (UNetV2 without RETURN_ENCODED_TENSOR)
         ops.stamp("conv_out")
         if "__prefetcher__" in x0.indice_dict:                 # every unit was consumed; join the stream(s) anyway
             pf = x0.indice_dict.pop("__prefetcher__")
@@ -321,7 +327,8 @@ class _BackboneBase(nn.Module):
             torch.cuda.current_stream().wait_stream(pf.side)
             if pf.unit0_stream is not None:
                 torch.cuda.current_stream().wait_stream(pf.unit0_stream)
-        batch_dict.update({'encoded_spconv_tensor': out, 'encoded_spconv_tensor_stride': 8})
+        if out is not None:
+            batch_dict.update({'encoded_spconv_tensor': out, 'encoded_spconv_tensor_stride': 8})
         batch_dict.update({'multi_scale_3d_features': {
             'x_conv1': x_conv1, 'x_conv2': x_conv2, 'x_conv3': x_conv3, 'x_conv4': x_conv4}})
         batch_dict.update({'multi_scale_3d_strides': {'x_conv1': 1, 'x_conv2': 2, 'x_conv3': 4, 'x_conv4': 8}})

@@ -1731,6 +1731,112 @@ def bn_backward(dy, x, y, gamma, save_mean, save_invstd, relu, training, want_dr
     return dx, dres, dgamma, dbeta
 
 
+# ---- UNetV2's UR block and point outputs (unet.hip) ------------------------------------------------------------------
+def _unet_rows(*ts):
+    _require_cuda(*ts)
+    for t in ts:
+        assert t.dim() == 2 and t.is_contiguous() and t.dtype == ts[0].dtype and t.shape[0] == ts[0].shape[0], \
+            "UNet merge passes take contiguous [n, c] matrices of one dtype and row count"
+
+
+def _unet_out(out, shape, like):
+    if out is None:
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    assert out.shape == tuple(shape) and out.dtype == like.dtype and out.device == like.device and out.is_contiguous()
+    return out
+
+
+def unet_merge_cat(bottom, trans, n_dev=None, out=None):
+    """cat [n, 2C] = (bottom, trans) per row, one pass over each input (spconv_unet.py:138 torch.cat)."""
+    _unet_rows(bottom, trans)
+    n, c = bottom.shape
+    assert trans.shape == (n, c)
+    cat = _unet_out(out, (n, 2 * c), bottom)
+    L.check(L.lib().pcd_unet_merge_cat(L.ptr(bottom), L.ptr(trans), L.dtype_code(bottom), n, c, L.ptr(n_dev), L.ptr(cat),
+                                       L.stream_ptr()), "pcd_unet_merge_cat")
+    return cat
+
+
+def unet_bn_pairadd(x, cat, gamma, beta, eps, momentum, training, running_mean, running_var, n_dev=None, partials=None,
+                    out=None):
+    """out[j] = relu(bn(x)[j]) + (cat[2j] + cat[2j+1]) in fp32, one rounding (spconv_unet.py:139-141: conv_m's BatchNorm +
+    ReLU, channel_reduction and the add); relu(bn(x)) is not stored.  `partials` as in bn_forward.
+    Returns (out, save_mean, save_invstd); the last two are None in the evaluation form."""
+    _unet_rows(x, cat)
+    n, c = x.shape
+    assert cat.shape == (n, 2 * c)
+    dev, lib = x.device, L.lib()
+    out = _unet_out(out, (n, c), x)
+    mid = save_mean = save_invstd = None
+    if training and n > 0:
+        save_mean = torch.empty((c,), dtype=torch.float32, device=dev)
+        save_invstd = torch.empty((c,), dtype=torch.float32, device=dev)
+        if partials is not None and partials[1] == L.BN_EXT_MID:
+            mid = partials[0]                    # the conv launch folded its rows already
+        else:
+            mid = torch.empty((L.BN_MID_ROWS, 2, c), dtype=torch.float64, device=dev)
+            ws = L.workspace(lib.pcd_bn_workspace_bytes(c), dev)
+            L.check(lib.pcd_bn_stats_mid(L.ptr(x), L.dtype_code(x), n, c, L.ptr(n_dev),
+                                         L.ptr(partials[0]) if partials else None, partials[1] if partials else 0,
+                                         L.ptr(mid), L.ptr(ws), ws.numel(), L.stream_ptr()), "pcd_bn_stats_mid")
+    L.check(lib.pcd_unet_bn_pairadd(L.ptr(x), L.ptr(cat), L.dtype_code(x), n, c, L.ptr(gamma), L.ptr(beta), float(eps),
+                                    float(momentum), L.ptr(mid), L.ptr(running_mean), L.ptr(running_var), L.ptr(save_mean),
+                                    L.ptr(save_invstd), L.ptr(n_dev), L.ptr(out), L.stream_ptr()), "pcd_unet_bn_pairadd")
+    return out, save_mean, save_invstd
+
+
+def unet_merge_backward(d_cat, dy, n_dev=None, out=None):
+    """(d_bottom, d_trans) [n, C] from d_cat [n, 2C] and the gradient dy [n, C] of the pair sum: d_bottom[c] = d_cat[c] + dy[c >> 1],
+    d_trans[c] = d_cat[C + c] + dy[(C + c) >> 1]."""
+    _unet_rows(d_cat, dy)
+    n, c = dy.shape
+    assert d_cat.shape == (n, 2 * c)
+    d_bottom, d_trans = (_unet_out(o, (n, c), dy) for o in (out if out is not None else (None, None)))
+    L.check(L.lib().pcd_unet_merge_backward(L.ptr(d_cat), L.ptr(dy), L.dtype_code(dy), n, c, L.ptr(n_dev), L.ptr(d_bottom),
+                                            L.ptr(d_trans), L.stream_ptr()), "pcd_unet_merge_backward")
+    return d_bottom, d_trans
+
+
+def unet_point_outputs(indices, voxel_size, point_cloud_range, n_dev=None, features=None, out=None):
+    """point_coords f32 [n, 4] = (b, x, y, z) voxel centres of indices int32 [n, 4] = (b, z, y, x), bit-equal to
+    common_utils.get_voxel_centers (spconv_unet.py:207-211).  With `n_dev`, rows [n_dev, n) become (-1, 0, 0, 0) and those rows
+    of `features` (written in place) zero."""
+    _require_cuda(indices)
+    assert indices.dtype == torch.int32 and indices.dim() == 2 and indices.shape[1] == 4 and indices.is_contiguous()
+    n = indices.shape[0]
+    coords = _unet_out(out, (n, 4), torch.empty((0,), dtype=torch.float32, device=indices.device))
+    row_bytes = 0
+    if features is not None:
+        assert features.is_cuda and features.is_contiguous() and features.shape[0] == n
+        row_bytes = features.shape[1] * features.element_size()
+    v = [float(t) for t in voxel_size]
+    r = [float(t) for t in point_cloud_range[:3]]
+    L.check(L.lib().pcd_unet_point_outputs(L.ptr(indices), n, L.ptr(n_dev), v[0], v[1], v[2], r[0], r[1], r[2], L.ptr(coords),
+                                           L.ptr(features) if n_dev is not None else None, row_bytes, L.stream_ptr()),
+            "pcd_unet_point_outputs")
+    return coords
+
+
+def transpose_wgrad(src, out=None):
+    """[cin, K, cout] f32 -> [cout, K, cin] f32 (into `out`, e.g. the parameter's .grad, when usable)."""
+    _require_cuda(src)
+    assert src.dtype == torch.float32 and src.dim() == 3 and src.is_contiguous()
+    cin, kvol, cout = src.shape
+    dst = out if _usable_out(out, src.numel()) else torch.empty((cout, kvol, cin), dtype=torch.float32, device=src.device)
+    L.check(L.lib().pcd_unet_transpose_wgrad(L.ptr(src), cin, kvol, cout, L.ptr(dst), L.stream_ptr()), "pcd_unet_transpose_wgrad")
+    return dst
+
+
+def unet_zero_padding_rows(features, n_dev):
+    """Zero the rows [n_dev, capacity) of `features` in place (the padding-row contract of UNetV2's point_features)."""
+    _require_cuda(features, n_dev)
+    assert features.dim() == 2 and features.is_contiguous()
+    L.check(L.lib().pcd_unet_point_outputs(None, features.shape[0], L.ptr(n_dev), 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, None,
+                                           L.ptr(features), features.shape[1] * features.element_size(), L.stream_ptr()),
+            "pcd_unet_point_outputs")
+    return features
+
+
 def col_sum_finalize(partial, rows, out=None):
     """out[c] = sum of the rows of partial [rows, c] (see bn_backward(colsum=True))."""
     c = partial.shape[1]

@@ -568,3 +568,172 @@ def batch_norm_act(bn, x, residual=None, relu=True, n_dev=None, out=None):
     if residual is not None:
         y = y + residual
     return torch.relu(y) if relu else y
+
+
+class UNetMergeFunction(Function):
+    """cat = (bottom, trans) per row for UNetV2's UR block (spconv_unet.py:138), plus a [n, C] token that stands for the pair sum
+    reduce(cat)[j] = cat[2j] + cat[2j+1] in the autograd graph: the consumer of the pair sum (UNetPairAddFunction) hands its
+    gradient to the token, so backward receives d_cat and that gradient in ONE call and writes d_bottom / d_trans in one pass
+    (the pass-through pattern of SparseConvFunction's identity branch: autograd inserts no add of its own)."""
+
+    @staticmethod
+    def forward(ctx, bottom, trans, n_dev=None):
+        b, t = bottom.detach().contiguous(), trans.detach().contiguous()
+        if t.dtype != b.dtype:
+            t = t.to(b.dtype)
+        cat = ops.unet_merge_cat(b, t, n_dev=n_dev)
+        ctx.n_dev, ctx.c, ctx.dtype = n_dev, b.shape[1], b.dtype
+        token = cat[:, :b.shape[1]]              # (a view: it carries no data of its own, only the pair sum's gradient)
+        return cat, token
+
+    @staticmethod
+    def backward(ctx, d_cat, d_pair):
+        if d_cat is None and d_pair is None:
+            return None, None, None
+        n = (d_cat if d_cat is not None else d_pair).shape[0]
+        dev = (d_cat if d_cat is not None else d_pair).device
+        if d_cat is None:
+            d_cat = torch.zeros((n, 2 * ctx.c), dtype=ctx.dtype, device=dev)
+        if d_pair is None:
+            d_pair = torch.zeros((n, ctx.c), dtype=ctx.dtype, device=dev)
+        d_cat = d_cat.to(ctx.dtype).contiguous()
+        d_pair = d_pair.to(ctx.dtype).contiguous()
+        d_bottom, d_trans = ops.unet_merge_backward(d_cat, d_pair, n_dev=ctx.n_dev)
+        return d_bottom, d_trans, None
+
+
+class UNetPairAddFunction(Function):
+    """out = relu(bn(x)) + reduce(cat) (spconv_unet.py:139-141) in one apply pass; `token` is UNetMergeFunction's second output
+    and `cat` the detached matrix itself.  Backward: the BatchNorm's existing one with the ReLU mask recomputed from x; dy goes
+    to the token unchanged."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, token, cat, bn, n_dev=None):
+        xc = x.detach().contiguous()
+        training = bn.training or bn.running_mean is None
+        momentum = bn.momentum if bn.momentum is not None else 0.1
+        g, b = gamma.detach().float(), beta.detach().float()
+        partials = None
+        st = getattr(x, "_pcd_stats", None) if (FUSE_BN_REDUCTIONS and training) else None
+        if st is not None and st.partial is not None and xc.data_ptr() == x.data_ptr() \
+                and xc.dtype == torch.bfloat16 and st.partial.shape[2] == xc.shape[1]:
+            partials = (st.partial, st.rows)
+        out, save_mean, save_invstd = ops.unet_bn_pairadd(xc, cat, g, b, bn.eps, momentum, training, bn.running_mean,
+                                                          bn.running_var, n_dev=n_dev, partials=partials)
+        if not training:
+            save_mean = bn.running_mean
+            save_invstd = torch.rsqrt(bn.running_var + bn.eps)
+        ctx.training, ctx.n_dev, ctx.bn = training, n_dev, bn
+        ctx.save_for_backward(xc, g, b, save_mean, save_invstd)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, g, b, save_mean, save_invstd = ctx.saved_tensors
+        if dy.dtype != x.dtype:
+            dy = dy.to(x.dtype)
+        dy = dy.contiguous()
+        if not ctx.training:
+            raise RuntimeError("UNetPairAddFunction: the backward pass needs batch statistics (BatchNorm in training mode)")
+        bn = ctx.bn
+        gw = bn.weight.grad if (DIRECT_GRAD and ctx.needs_input_grad[1]) else None
+        gb = bn.bias.grad if (DIRECT_GRAD and ctx.needs_input_grad[2]) else None
+        direct = gw is not None and gb is not None and ops._usable_out(gw, x.shape[1]) and ops._usable_out(gb, x.shape[1])
+        dx, _, dgamma, dbeta = ops.bn_backward(dy, x, None, g, save_mean, save_invstd, True, True, False, n_dev=ctx.n_dev,
+                                               dgamma_out=gw if direct else None, dbeta_out=gb if direct else None, beta=b)
+        if direct:
+            dgamma = dbeta = None
+        return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
+                dy if ctx.needs_input_grad[3] else None, None, None, None)
+
+
+def unet_merge(bottom, trans, n_dev=None):
+    """(cat, token) of UNetMergeFunction; CPU tensors are refused (no fallback)."""
+    return UNetMergeFunction.apply(bottom, trans, n_dev)
+
+
+def unet_bn_relu_pairadd(bn, x, cat, token, n_dev=None):
+    """relu(bn(x)) + pair sum of `cat`, with (cat, token) from unet_merge()."""
+    if not (_fusable(bn, x) and bn.weight is not None and bn.bias is not None):
+        raise RuntimeError("unet_bn_relu_pairadd: needs an affine BatchNorm1d over a device matrix the fused kernels accept")
+    if bn.training and bn.num_batches_tracked is not None and not getattr(bn, "_defer_nbt", False):
+        bn.num_batches_tracked.add_(1)
+    return UNetPairAddFunction.apply(x, bn.weight, bn.bias, token, cat.detach(), bn, n_dev)
+
+
+# ---- SparseInverseConv3d on the strided conv's own kernels (bf16 form) ------------------------------------------------------
+# An inverse conv with weight U [Cout, K, Cin] over the rulebook R of the strided conv that shares its indice_key computes
+# y[i] = sum_k U_k x[R.nbr_in[k][i]].  That is the shape of R's data gradient, its data gradient the shape of R's forward, and
+# its weight gradient R's with the two operands swapped -- so the three run on R's compact tables (nbr_cls, nbr_out_packed,
+# the parity classes) and nothing derives pair lists, sorts them or expands a 27-wide table (ops.Rulebook.inverse() does all
+# three; it stays for the fp32-exact path and for widths outside the kernels).
+INVERSE_ON_STRIDED = True
+
+
+def inverse_on_strided(conv, rb, features):
+    """The bf16 form above serves this inverse conv over the strided rulebook `rb` and these input features."""
+    cin, cout = conv.in_channels, conv.out_channels
+    if not (INVERSE_ON_STRIDED and features.is_cuda and features.dtype == torch.bfloat16 and features.shape[1] == cin):
+        return False
+    if rb.subm or conv.bias is not None or rb.kvol != 27 or tuple(rb.dilation) != (1, 1, 1):
+        return False
+    # widths of the class data-gradient kernel (contraction over cin: a power of two >= 32) and of the packed forward kernel
+    if cin < 32 or (cin & (cin - 1)) or cout not in (16, 32, 64, 128) or cin > 128:
+        return False
+    if torch.is_grad_enabled() and (features.requires_grad or conv.weight.requires_grad):
+        return rb.classes is not None          # (built by the strided conv whenever autograd runs through it)
+    return rb.classes is not None or rb._nbr_in is not None
+
+
+class SparseInverseConvFunction(Function):
+    """`rb` is the STRIDED conv's rulebook; packed_fwd / packed_dgrad the forward / data-gradient packs of the inverse conv's
+    own weight (generic layout)."""
+
+    @staticmethod
+    def forward(ctx, features, weight, rb, packed_fwd, packed_dgrad):
+        cout, cin = weight.shape[0], weight.shape[-1]
+        x = _to_bf16_padded(features.detach(), cin)
+        stats = None
+        if FUSE_BN_REDUCTIONS and cout % 16 == 0 and ctx.needs_input_grad[1]:
+            stats = ops.BnReduce(1)
+        if rb.classes is not None:
+            y = ops.dgrad_classes(x, packed_fwd, rb, cout, torch.bfloat16, bn_reduce=stats)
+        else:                                    # an evaluation build: full tables, no parity classes
+            y = ops.gather_gemm(x, packed_fwd, None, rb.nbr_in, rb.kvol, False, rb.n_in, cout, torch.bfloat16,
+                                n_dev=rb.n_in_dev, bn_reduce=stats)
+        if stats is not None:
+            y._pcd_stats = stats
+        ctx.rb, ctx.packed_dgrad, ctx.cin, ctx.cout = rb, packed_dgrad, cin, cout
+        ctx.weight_param = weight if isinstance(weight, torch.nn.Parameter) else None
+        ctx.in_dtype = features.dtype
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        rb, cin, cout = ctx.rb, ctx.cin, ctx.cout
+        dy16 = _to_bf16_padded(dy, cout)
+        keep = [x, dy16]
+
+        def dgrad():
+            packed_d = ctx.packed_dgrad() if ctx.packed_dgrad is not None else ops.pack_weight(weight, 1)
+            packed = rb.nbr_out_packed is not None and not ops.gather_gemm_is_wide(dy16.shape[0], cout, rb.kvol, rb.n_out, cin)
+            return ops.gather_gemm(dy16, packed_d, None, rb.nbr_out_packed if packed else rb.nbr_out, rb.kvol, False, rb.n_out,
+                                   cin, ctx.in_dtype, n_dev=rb.n_out_dev, nbr_packed=packed)
+
+        def wgrad(direct, jobs):
+            # R's weight gradient with x := dy (on R's input rows) and dy := x (on R's output rows) is dU transposed; the
+            # reduction runs now (not with the deferred jobs): the transpose reads its result
+            t = ops.wgrad(dy16, cout, x, None, None, rb.kvol, rb=rb)                       # [Cin, K, Cout]
+            du = ops.transpose_wgrad(t.view(cin, rb.kvol, cout), out=ctx.weight_param.grad if direct else None)
+            return None if direct else du.view(weight.shape).to(weight.dtype)
+
+        dx, dw, _ = scheduled_backward(ctx.needs_input_grad[0], ctx.needs_input_grad[1], False, ctx.weight_param, None,
+                                       dgrad, wgrad, None, keep, direct_without_deferral=True, flush=False,
+                                       sparse_stamps=True)
+        return dx, dw, None, None, None
+
+
+def sparse_inverse_conv(features, weight, rb, packed_fwd, packed_dgrad=None):
+    return SparseInverseConvFunction.apply(features, weight, rb, packed_fwd, packed_dgrad)

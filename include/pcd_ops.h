@@ -602,6 +602,11 @@ int pcd_bn_forward_ld(const void *x, const void *residual, int dtype, int n, int
                       float *running_var, int relu, void *y, int y_ld, float *save_mean, float *save_invstd,
                       const int32_t *n_dev, const float *ext_partial, int ext_rows, void *workspace,
                       size_t workspace_bytes, void *stream);
+/* The statistics half of pcd_bn_forward_ld's training form alone, for an apply pass that lives elsewhere
+ * (pcd_unet_bn_pairadd): mid [PCD_BN_MID_ROWS][2][c] f64 receives the folded column sums (sum x, sum x^2) of the n (> 0) rows
+ * of x, taken by the same launches; ext_partial / ext_rows (>= 0) as there, x is then not read. */
+int pcd_bn_stats_mid(const void *x, int dtype, int n, int c, const int32_t *n_dev, const float *ext_partial, int ext_rows,
+                     double *mid, void *workspace, size_t workspace_bytes, void *stream);
 int pcd_bn_backward_ld(const void *dy, int dy_ld, const void *x, const void *y, int dtype, int n, int c,
                        const float *gamma, const float *beta, const float *save_mean, const float *save_invstd,
                        int relu, int training, void *dx, void *dresidual, float *dgamma, float *dbeta,
@@ -1669,6 +1674,36 @@ int pcd_parta2_pool_backward(const float *grad_part_rows, const float *grad_rpn_
                              const int *state, const int *row_entries, const int *entries, const int *argmax,
                              const float *point_scores, float score_thresh, float *grad_part, float *grad_features,
                              void *stream);
+
+/* ---- UNetV2's UR block and point outputs (unet.hip; pcdet/models/backbones_3d/spconv_unet.py:135-160,206-211) ----------
+ * Matrices are row-major [n][c] of PCD_F32 / PCD_BF16 with c * element size a multiple of 16 that divides 4096, 16-byte
+ * aligned; n is the capacity and *n_dev (optional) the row count on the device: rows behind it are neither read nor written
+ * (but for the padding rows of pcd_unet_point_outputs).  fp32 arithmetic, one rounding to the storage type.
+ *   pcd_unet_merge_cat       cat [n][2c]: cat[r] = (bottom[r], trans[r]), both [n][c]; bit copies.
+ *   pcd_unet_bn_pairadd      out[r][j] = relu(x[r][j] * scale[j] + shift[j]) + (cat[r][2j] + cat[r][2j+1]), x and out [n][c],
+ *                            cat [n][2c]; scale = gamma * invstd, shift = beta - mean * gamma * invstd.  Training form: mid =
+ *                            the rows pcd_bn_stats_mid (or a conv launch: PcdBnReduce.mid) left; mean / invstd are finished
+ *                            from them as pcd_bn_forward_ld does, written to save_mean / save_invstd, and the running
+ *                            statistics (optional) are updated.  mid == NULL: running_mean / running_var are the statistics.
+ *                            The backward pass is pcd_bn_backward_ld's (relu, y == NULL: the mask from x).
+ *   pcd_unet_merge_backward  d_bottom[r][q] = d_cat[r][q] + dy[r][q >> 1], d_trans[r][q] = d_cat[r][c + q] + dy[r][(c + q) >> 1];
+ *                            d_cat [n][2c], the others [n][c].
+ *   pcd_unet_point_outputs   indices int32 [n][4] = (b, z, y, x) -> coords f32 [n][4] = (b, cx, cy, cz), c = (idx + 0.5) * v + c0
+ *                            with the product and the sum rounded separately.  With n_dev, rows [*n_dev, n) of coords become
+ *                            (-1, 0, 0, 0) and those rows of features (optional, feature_row_bytes each, a multiple of 16)
+ *                            become zero.  coords == NULL (needs n_dev and features): only that, indices is not read. */
+/* dst [cout][kvol][cin] f32 = the transpose of src [cin][kvol][cout] f32 (distinct buffers): the weight gradient of an inverse
+ * conv taken by the strided conv's class weight-gradient kernel with the two operands swapped, into parameter layout. */
+int pcd_unet_transpose_wgrad(const float *src, int cin, int kvol, int cout, float *dst, void *stream);
+int pcd_unet_merge_cat(const void *bottom, const void *trans, int dtype, int n, int c, const int32_t *n_dev, void *cat,
+                       void *stream);
+int pcd_unet_bn_pairadd(const void *x, const void *cat, int dtype, int n, int c, const float *gamma, const float *beta,
+                        float eps, float momentum, const double *mid, float *running_mean, float *running_var,
+                        float *save_mean, float *save_invstd, const int32_t *n_dev, void *out, void *stream);
+int pcd_unet_merge_backward(const void *d_cat, const void *dy, int dtype, int n, int c, const int32_t *n_dev, void *d_bottom,
+                            void *d_trans, void *stream);
+int pcd_unet_point_outputs(const int32_t *indices, int n, const int32_t *n_dev, float vx, float vy, float vz, float x0,
+                           float y0, float z0, float *coords, void *features, int feature_row_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,812 @@
+"""GPU: hotpath.UNetV2 (pcdet/models/backbones_3d/spconv_unet.py:49-212) and the kernels under it.
+
+  * the four kernels of com_amd/csrc/unet.hip against the formulas of tests/unet_ref.py computed by torch on the same inputs --
+    bit-equal (cat is a copy; the post-add apply and the merge backward are fp32 arithmetic in a stated order with one rounding,
+    and the apply's scale / shift are formed from the kernel's own save_mean / save_invstd, so the statistics' last bits do not
+    enter); rows behind the device row count are neither read (NaN there) nor written;
+  * the inverse convs on the strided conv's kernels against fp64 on the op's own bf16 inputs, OP_TOL = 1e-3 relative L2 -- and
+    the generic path (Rulebook.inverse()) on the same inputs, same bar;
+  * UNetV2 end to end against fixture G54 (tests/golden/make_golden_unet.py: G7's method and constants): eager, z-fastest rows,
+    static plan + graph replay, fp32-exact; eval mode; every op in situ.
+
+Worst measured ratios over the runs of this file: test_unet_end_to_end's docstring; the one constant that differs from G7's:
+test_unet_fp32_exact_path_end_to_end's."""
+import contextlib
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(HERE, "golden"))
+import g54_params as P  # noqa: E402
+import unet_ref as UR  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+OP_TOL = 1e-3            # relative L2 of ONE op's output vs fp64 on its own inputs (+ bf16 rounding)
+NOISE_FACTOR = 1.1       # err(HIP, exact) <= NOISE_FACTOR * err(bf16-emulating fp64 chain, exact)
+GRAD_NOISE_FACTOR = 1.6  # same for a parameter-gradient tensor (+ 0.01)
+GRAD_MIN_COS = 0.85
+FIRST_TAP_TOL = 2e-3
+FP32_GRAD_TOL = 8.3e-3   # fp32-exact parameter gradients: test_unet_fp32_exact_path_end_to_end's docstring
+CAP = 512
+_plan_scope = contextlib.ExitStack()
+
+
+def _rel(a, b):
+    a = np.asarray(a, np.float64).reshape(-1)
+    b = np.asarray(b, np.float64).reshape(-1)
+    return float(np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30))
+
+
+def _rel_t(a, b):
+    a, b = a.double(), b.double()
+    return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+def _bf16(t):
+    return t.float().bfloat16().double()
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+
+def _padded(n, c, dtype, seed, scale=1.0):
+    """[CAP, c] with n real rows and NaN behind them."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    t = torch.full((CAP, c), float("nan"))
+    t[:n] = torch.randn((n, c), generator=g) * scale
+    return t.to(dtype).to(DEV)
+
+
+def _untouched(t, n):
+    return bool(torch.isnan(t[n:].float()).all())
+
+
+KERNEL_CASES = [(c, dt, n) for c in (16, 32, 64) for dt in (torch.float32, torch.bfloat16) for n in (1, 7, 300)]
+
+
+@pytest.mark.parametrize("c,dtype,n", KERNEL_CASES)
+def test_merge_kernels_bit_exact(c, dtype, n):
+    from com_amd import ops
+    n_dev = torch.tensor([n], dtype=torch.int32, device=DEV)
+    bottom, trans = _padded(n, c, dtype, 1), _padded(n, c, dtype, 2)
+    cat = torch.full((CAP, 2 * c), float("nan"), dtype=dtype, device=DEV)
+    ops.unet_merge_cat(bottom, trans, n_dev=n_dev, out=cat)
+    assert torch.equal(_bits(cat[:n]), _bits(UR.merge(bottom[:n], trans[:n]))) and _untouched(cat, n)
+    # without a device count the capacity is the row count
+    assert torch.equal(_bits(ops.unet_merge_cat(bottom[:n].contiguous(), trans[:n].contiguous())), _bits(cat[:n]))
+    d_cat, dy = _padded(n, 2 * c, dtype, 3), _padded(n, c, dtype, 4)
+    outs = tuple(torch.full((CAP, c), float("nan"), dtype=dtype, device=DEV) for _ in range(2))
+    ops.unet_merge_backward(d_cat, dy, n_dev=n_dev, out=outs)
+    want = UR.merge_backward(d_cat[:n], dy[:n])
+    for got, w in zip(outs, want):
+        assert torch.equal(_bits(got[:n]), _bits(w)) and _untouched(got, n)
+
+
+@pytest.mark.parametrize("c,dtype,n", KERNEL_CASES)
+def test_bn_relu_pairadd_apply_bit_exact(c, dtype, n):
+    from com_amd import ops
+    n_dev = torch.tensor([n], dtype=torch.int32, device=DEV)
+    x, cat = _padded(n, c, dtype, 5, 2.0), _padded(n, 2 * c, dtype, 6)
+    g = torch.Generator().manual_seed(7)
+    gamma = (torch.rand(c, generator=g) + 0.5).to(DEV)
+    beta = (torch.rand(c, generator=g) * 0.6 - 0.3).to(DEV)
+    rm, rv = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
+    out = torch.full((CAP, c), float("nan"), dtype=dtype, device=DEV)
+    eps, mom = 1e-3, 0.01
+    _, mean, invstd = ops.unet_bn_pairadd(x, cat, gamma, beta, eps, mom, True, rm, rv, n_dev=n_dev, out=out)
+    # statistics against fp64 over the real rows
+    xd = x[:n].double()
+    m64, v64 = xd.mean(0), xd.var(0, unbiased=False)
+    assert torch.allclose(mean.double(), m64, rtol=1e-5, atol=1e-6)
+    # the variance is E[x^2] - mean^2 over fp32 squares and partial sums (the arithmetic of the existing BatchNorm passes): an
+    # absolute error of a few 2^-24 E[x^2], i.e. relative 2^-22 E[x^2] / (var + eps) / 2 in invstd -- visible where var << E[x^2]
+    is64 = 1.0 / torch.sqrt(v64 + eps)
+    tol = 2.0 ** -22 * (xd * xd).mean(0) / (v64 + eps) + 1e-6
+    assert bool(((invstd.double() - is64).abs() <= tol * is64).all()), ((invstd.double() - is64).abs() / is64, tol)
+    assert torch.allclose(rm.double(), mom * m64, rtol=1e-5, atol=1e-7)
+    assert torch.allclose(rv.double(), (1 - mom) + mom * v64 * n / max(n - 1, 1), rtol=1e-5)
+    # the apply: the stated fp32 formula on the kernel's own statistics, bit for bit
+    scale = gamma * invstd
+    shift = beta - mean * gamma * invstd
+    assert torch.equal(_bits(out[:n]), _bits(UR.bn_relu_pairadd(x[:n], cat[:n], scale, shift))) and _untouched(out, n)
+    # evaluation form: the running statistics (1 / sqrt in fp32 on the device: within one storage ulp of fp64)
+    rm2, rv2 = (torch.rand(c, generator=g) - 0.5).to(DEV), (torch.rand(c, generator=g) + 0.5).to(DEV)
+    out2, _, _ = ops.unet_bn_pairadd(x, cat, gamma, beta, eps, mom, False, rm2, rv2, n_dev=n_dev)
+    is64 = 1.0 / torch.sqrt(rv2.double() + eps)
+    want = torch.relu(xd * (gamma.double() * is64) + (beta.double() - rm2.double() * gamma.double() * is64)) \
+        + UR.pair_sum(cat[:n].double())
+    ulp = 2.0 ** -7 if dtype == torch.bfloat16 else 2.0 ** -20
+    assert bool(((out2[:n].double() - want).abs() <= ulp * want.abs() + 1e-5).all())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_point_outputs_bit_equal_and_padding_rows(dtype):
+    from com_amd import ops
+    g = torch.Generator().manual_seed(9)
+    n = 300
+    idx = torch.stack([torch.randint(0, 2, (CAP,), generator=g), torch.randint(0, 25, (CAP,), generator=g),
+                       torch.randint(0, 64, (CAP,), generator=g), torch.randint(0, 48, (CAP,), generator=g)], 1).int().to(DEV)
+    want = UR.point_coords(idx, list(P.VOXEL), list(P.RANGE))
+    got = ops.unet_point_outputs(idx, P.VOXEL, P.RANGE)
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    n_dev = torch.tensor([n], dtype=torch.int32, device=DEV)
+    idx[n:] = 2 ** 30                                       # rows behind the count are not read
+    feats = torch.full((CAP, 16), float("nan"), dtype=dtype, device=DEV)
+    feats[:n] = 1.5
+    got = ops.unet_point_outputs(idx, P.VOXEL, P.RANGE, n_dev=n_dev)
+    assert torch.equal(got[:n].view(torch.int32), want[:n].view(torch.int32))
+    pad = torch.tensor([-1.0, 0.0, 0.0, 0.0], device=DEV)
+    assert torch.equal(got[n:], pad.expand(CAP - n, 4))
+    ops.unet_zero_padding_rows(feats, n_dev)
+    assert bool((feats[:n] == 1.5).all()) and bool((feats[n:] == 0).all())
+
+
+@pytest.mark.parametrize("c", [16, 64])
+def test_ur_merge_autograd_against_the_reference_operations(c):
+    """unet_merge + unet_bn_relu_pairadd in fp32 under autograd against the literal torch.cat / BatchNorm / ReLU /
+    view(n, C, -1).sum(2) of spconv_unet.py:138-141 (a linear map stands for conv_m): both gradients of `cat` reach bottom and
+    trans through ONE backward call of the merge."""
+    from com_amd.spconv import functional as Fsp
+    torch.manual_seed(5)
+    n = 300
+    bn = torch.nn.BatchNorm1d(c, eps=1e-3, momentum=0.01).to(DEV).train()
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.uniform_(-0.3, 0.3)
+    w = torch.randn(2 * c, c, device=DEV) / (2 * c) ** 0.5
+    g_out = torch.randn(n, c, device=DEV)
+    res = {}
+    for tag in ("ref", "hip"):
+        bottom = torch.randn(n, c, device=DEV, generator=torch.Generator(DEV).manual_seed(1)).requires_grad_(True)
+        trans = torch.randn(n, c, device=DEV, generator=torch.Generator(DEV).manual_seed(2)).requires_grad_(True)
+        bn.zero_grad()
+        bn.running_mean.zero_(), bn.running_var.fill_(1.0)
+        if tag == "ref":
+            cat = torch.cat((bottom, trans), dim=1)
+            out = torch.relu(bn(cat @ w)) + cat.view(n, c, -1).sum(dim=2)
+        else:
+            cat, token = Fsp.unet_merge(bottom, trans)
+            out = Fsp.unet_bn_relu_pairadd(bn, cat @ w, cat, token)
+        out.backward(g_out)
+        res[tag] = [t.detach().double().clone() for t in (out, bottom.grad, trans.grad, bn.weight.grad, bn.bias.grad,
+                                                           bn.running_mean, bn.running_var)]
+    for name, a, b in zip(("out", "d_bottom", "d_trans", "dgamma", "dbeta", "running_mean", "running_var"), res["hip"], res["ref"]):
+        # fp32 against fp32: sums over 300 rows (<= 300 * 2^-24 = 2e-5 relative, worst case) and the BatchNorm backward's
+        # cancellation of the mean and xhat components of dy on top of them
+        assert _rel_t(a, b) < 1e-4, (name, _rel_t(a, b))
+
+
+# ---------------------------------------------------------------------------------------------
+def _net(dtype=torch.bfloat16, train=True):
+    from com_amd import hotpath
+    net = hotpath.UNetV2({}, P.IN_CHANNELS, list(P.GRID), list(P.VOXEL), list(P.RANGE)).to(DEV)
+    sd = {k: torch.from_numpy(v) for k, v in P.state_dict().items()}
+    missing, unexpected = net.load_state_dict(sd, strict=False)
+    assert not unexpected and all("running_" in k or "num_batches" in k for k in missing), (missing, unexpected)
+    net.feature_dtype = dtype
+    net.train(train)
+    bev = hotpath.HeightCompression({"NUM_BEV_FEATURES": 128})
+    return net, bev
+
+
+def _inputs(g):
+    from com_amd import hotpath
+    pts, offs = hotpath.collate_points([g[f"points{b}"] for b in range(P.BATCH)], DEV)
+    return pts, torch.tensor(offs, dtype=torch.int32, device=DEV)
+
+
+def _voxels(pts, offs, row_order="first", bf16=True):
+    from com_amd import hotpath
+    bd = {"points": pts, "frame_offsets": offs, "batch_size": P.BATCH}
+    return hotpath.transform_points_to_voxels(bd, P.RANGE, P.VOXEL, P.MAX_POINTS, P.MAX_VOXELS, bf16_features=bf16,
+                                              row_order=row_order)
+
+
+def _key_order(idx, mode):
+    idx = np.asarray(idx, np.int64)
+    if mode == "yxz":                                # (b, y, x, z): z fastest
+        return np.lexsort((idx[:, 1], idx[:, 3], idx[:, 2], idx[:, 0]))
+    if mode == "zyx":
+        return np.lexsort((idx[:, 3], idx[:, 2], idx[:, 1], idx[:, 0]))
+    return np.arange(idx.shape[0])
+
+
+def _projections(g, mode, rows=None):
+    """(P over the BEV map, Q over point_features in the DEVICE's row order, zero rows up to `rows`)."""
+    n1 = g["coords"].shape[0]
+    proj = torch.from_numpy(P.loss_projection(P.BATCH * 128 * 8 * 6)).to(DEV).view(P.BATCH, 128, 8, 6)
+    q = P.loss_projection(n1 * 16, 98).reshape(n1, 16)[_key_order(g["coords"], mode)]
+    qq = np.zeros((rows or n1, 16), np.float32)
+    qq[:n1] = q
+    return proj, torch.from_numpy(qq).to(DEV), n1
+
+
+def _step(net, bev, pts, offs, proj, projp, n1, row_order="first", bf16=True):
+    bd = bev(net(_voxels(pts, offs, row_order, bf16)))
+    sf, pf = bd["spatial_features"].float(), bd["point_features"].float()
+    loss = P.LOSS_QUAD * 0.5 * ((sf * sf).mean() + (pf * pf).sum() / (n1 * 16)) + torch.sum(sf * proj) + torch.sum(pf * projp)
+    for p in net.parameters():
+        p.grad = None
+    loss.backward()
+    return bd, loss
+
+
+def _reset_bn(net):
+    for m in net.modules():
+        if isinstance(m, torch.nn.BatchNorm1d):
+            m.running_mean.zero_()
+            m.running_var.fill_(1.0)
+
+
+LEVEL_OF = {"x_conv1": 1, "x_conv2": 2, "x_conv3": 3, "x_conv4": 4, "out": "out", "x_up4": 3, "x_up3": 2, "x_up2": 1, "x_up1": 1}
+
+
+def _taps(bd):
+    taps = dict(bd["multi_scale_3d_features"])
+    taps["out"] = bd["encoded_spconv_tensor"]
+    taps.update(bd["unet_decoder_features"])
+    return taps
+
+
+def _fixture_rows(t, want_idx, mode, level, static):
+    """The features of sparse tensor `t` in the fixture's row order, after the bit-exact check of its row set and order."""
+    n = want_idx.shape[0]
+    if static:
+        assert int(t.num_rows.item()) == n and t.indices.shape[0] >= n
+    else:
+        assert t.indices.shape[0] == n, (t.indices.shape, n)
+    # level 1 carries the voxeliser's order; deeper levels are key-ordered (sorted (b, z, y, x) unless the chain is z-fastest)
+    order = _key_order(want_idx, mode if (level == 1 or mode == "yxz") else "first")
+    np.testing.assert_array_equal(t.indices[:n].cpu().numpy(), want_idx[order].astype(np.int32))
+    f = t.features[:n].detach().float().cpu().numpy()
+    out = np.empty_like(f)
+    out[order] = f
+    return out
+
+
+def _check_against_g54(g, net, bd, loss, mode="first", static=False, ratios=None):
+    ratios = ratios if ratios is not None else {}
+    fails, report = [], {}
+    n1 = g["coords"].shape[0]
+    np.testing.assert_array_equal(bd["voxel_coords"][:n1].cpu().numpy(), g["coords"][_key_order(g["coords"], mode)])
+    # point_coords: bit-equal to the reference's get_voxel_centers (fixture) and to the formula on the device's own rows
+    pc = bd["point_coords"]
+    want_pc = UR.point_coords(bd["voxel_coords"][:n1].int(), list(P.VOXEL), list(P.RANGE))
+    assert torch.equal(pc[:n1].view(torch.int32), want_pc.view(torch.int32))
+    back = np.empty((n1, 4), np.float32)
+    back[_key_order(g["coords"], mode)] = pc[:n1].cpu().numpy()
+    np.testing.assert_array_equal(back[::4], g["point_coords"])
+    if static:
+        rows = int(bd["point_num_rows"].item())
+        assert rows == n1 and pc.shape[0] > n1 and bool((pc[n1:, 0] == -1).all()) and bool((pc[n1:, 1:] == 0).all())
+        assert bool((bd["point_features"][n1:] == 0).all())
+    rows = {}
+    for name, t in _taps(bd).items():
+        lv = LEVEL_OF[name]
+        assert list(t.spatial_shape) == list(g[f"shape_{lv}"]), name
+        rows[name] = _fixture_rows(t, g[f"idx_{lv}"], mode, lv, static)
+        e_hip, e_emu = _rel(P.tap_sample(rows[name]), g["exact_" + name]), float(g["bf16err_" + name][0])
+        report[name] = (round(e_hip, 5), round(e_emu, 5))
+        ratios["tap " + name] = max(ratios.get("tap " + name, 0.0), e_hip / e_emu)
+        fails += [(name, e_hip, e_emu)] if e_hip > NOISE_FACTOR * e_emu else []
+    np.testing.assert_array_equal(rows["x_up1"], _fixture_rows(
+        type("T", (), dict(indices=bd["voxel_coords"].int(), features=bd["point_features"], num_rows=bd.get("point_num_rows")))(),
+        g["idx_1"], mode, 1, static))                                               # point_features IS x_up1
+    if _rel(P.tap_sample(rows["x_conv1"]), g["bf16_x_conv1"]) > FIRST_TAP_TOL:
+        fails.append(("x_conv1 vs bf16 chain", _rel(P.tap_sample(rows["x_conv1"]), g["bf16_x_conv1"])))
+    s = bd["spatial_features"].detach().float().cpu().numpy()
+    assert s.shape == g["exact_spatial_features"].shape
+    assert np.array_equal(np.abs(s).sum(1) != 0, g["bf16_occupied"])
+    e_hip, e_emu = _rel(s, g["exact_spatial_features"]), float(g["bf16err_spatial_features"][0])
+    report["spatial_features"] = (round(e_hip, 5), round(e_emu, 5))
+    fails += [("spatial_features", e_hip, e_emu)] if e_hip > NOISE_FACTOR * e_emu else []
+    l_ex = float(g["exact_loss"][0])
+    report["loss"] = (float(loss), float(g["bf16_loss"][0]), l_ex)
+    fails += [("loss", report["loss"])] if abs(float(loss) - l_ex) > 1e-2 * abs(l_ex) else []
+    grads = {}
+    names = [n for n, _ in net.named_parameters()]
+    assert names == [n for n, _, _ in P.param_specs()]        # no conv bias anywhere: no tensor is left out
+    for name, p in net.named_parameters():
+        key = name.replace(".", "__")
+        assert p.grad is not None and bool(torch.isfinite(p.grad).all()), name
+        got, ex = P.grad_sample(p.grad.detach().float().cpu().numpy()), g["exact_grad__" + key]
+        assert got.shape == ex.shape, name
+        e_hip, e_emu = _rel(got, ex), float(g["bf16err_grad__" + key][0])
+        cos = float(np.dot(got.astype(np.float64), ex) / (np.linalg.norm(got) * np.linalg.norm(ex) + 1e-30))
+        grads[name] = (round(e_hip, 4), round(e_emu, 4), round(cos, 4))
+        ratios["grad"] = max(ratios.get("grad", 0.0), (e_hip - 0.01) / e_emu)
+        ratios["min cos"] = min(ratios.get("min cos", 1.0), cos)
+        fails += [(name, "grad", e_hip, e_emu, cos)] if (e_hip > GRAD_NOISE_FACTOR * e_emu + 0.01 or cos < GRAD_MIN_COS) else []
+    for name, b in net.named_buffers():
+        if name.endswith("running_mean") or name.endswith("running_var"):
+            np.testing.assert_allclose(b.detach().cpu().numpy(), g["exact_" + name.replace(".", "__")], rtol=2e-2, atol=2e-4,
+                                       err_msg=name)
+    report["grads (err HIP-exact, err bf16chain-exact, cosine)"] = grads
+    print("G54 report:", report)
+    print("G54 worst ratios so far:", {k: round(v, 4) for k, v in ratios.items()})
+    assert not fails, fails
+    return report
+
+
+def _strided_rulebooks(bd):
+    d = bd["multi_scale_3d_features"]["x_conv1"].indice_dict
+    return {k: d[k][0] for k in ("spconv2", "spconv3", "spconv4")}
+
+
+@pytest.mark.parametrize("mode", ["first", "yxz"])
+def test_unet_end_to_end(golden, mode):
+    """Eager, in the voxeliser's first-appearance row order and with the whole chain z-fastest (the window path).
+
+    G7's constants hold unchanged.  Worst figures over the runs of this file (eager first / yxz, static eager, graph replay):
+    tap error over the bf16 chain's 1.015 (x_conv4; bar NOISE_FACTOR 1.1), parameter gradients (err - 0.01) / bf16 chain's 1.31
+    (bar GRAD_NOISE_FACTOR 1.6), cosine 0.918 (bar 0.85); evaluation form 1.017 (x_up3)."""
+    g = golden("g54_unet")
+    net, bev = _net()
+    pts, offs = _inputs(g)
+    proj, projp, n1 = _projections(g, mode)
+    bd, loss = _step(net, bev, pts, offs, proj, projp, n1, row_order=mode)
+    torch.cuda.synchronize()
+    _check_against_g54(g, net, bd, loss.detach(), mode=mode)
+    for key, rb in _strided_rulebooks(bd).items():
+        assert rb._pairs is None, key                        # the inverse convs derived no pair lists
+
+
+def test_unet_static_plan_and_graph_replay(golden):
+    """Counts observed eagerly, buffers at capacity, forward + backward captured into ONE graph and replayed -- on another point
+    order first, then on the fixture's: bit-identical to the static eager run, checked against the fixture; the three strided
+    rulebooks keep their compact tables (no pair lists, no 27-wide tables)."""
+    from com_amd import ops
+    g = golden("g54_unet")
+    net, bev = _net()
+    pts, offs = _inputs(g)
+    plan = ops.StaticPlan(margin=1.25, round_to=256)
+    _plan_scope.close(); _plan_scope.enter_context(plan)
+    try:
+        proj, projp, n1 = _projections(g, "yxz")
+        _step(net, bev, pts, offs, proj, projp, n1, row_order="yxz")     # eager: observes the counts
+        plan.active = True
+        cap = _voxels(pts, offs, "yxz")["voxel_coords"].shape[0]
+        assert cap > n1
+        proj, projp, n1 = _projections(g, "yxz", rows=cap)
+        _reset_bn(net)
+        bd, loss = _step(net, bev, pts, offs, proj, projp, n1, row_order="yxz")
+        torch.cuda.synchronize()
+        assert plan.check()
+        _check_against_g54(g, net, bd, loss.detach(), mode="yxz", static=True)
+        for key, rb in _strided_rulebooks(bd).items():
+            assert rb._pairs is None, key
+            if rb.nbr_cls is not None:                       # compact build: still unexpanded after forward + backward
+                assert rb._nbr_in is None and not rb.nbr_complete, key
+        assert any(rb.nbr_cls is not None for rb in _strided_rulebooks(bd).values())
+        eager = {n: p.grad.detach().clone() for n, p in net.named_parameters()}
+        eager_pf = bd["point_features"].detach().clone()
+        del bd, loss
+        s_pts, s_offs = pts.clone(), offs.clone()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                _step(net, bev, s_pts, s_offs, proj, projp, n1, row_order="yxz")
+        torch.cuda.current_stream().wait_stream(side)
+        for p in net.parameters():
+            p.grad = None
+        plan.recorded.clear()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            bd, loss = _step(net, bev, s_pts, s_offs, proj, projp, n1, row_order="yxz")
+        s_pts.copy_(pts.flip(0))                             # a different point order
+        graph.replay()
+        _reset_bn(net)
+        s_pts.copy_(pts)
+        graph.replay()
+        torch.cuda.synchronize()
+        assert plan.check()
+        _check_against_g54(g, net, bd, loss.detach(), mode="yxz", static=True)
+        assert torch.equal(bd["point_features"], eager_pf)
+        for n, p in net.named_parameters():
+            assert torch.equal(p.grad, eager[n]), n          # the replay is the static eager step, bit for bit
+    finally:
+        _plan_scope.close()
+
+
+def test_unet_fp32_exact_path_end_to_end(golden):
+    """fp32 features through the fp32-exact kernels (functional.EXACT_FP32; the inverse convs through Rulebook.inverse()): taps,
+    BEV map and loss within 1e-5 (G7's bar; measured 3e-7 .. 2.8e-6).
+
+    Parameter gradients: G7's 3e-3 is the weight of ~3 ReLU flips (a pre-activation within fp32 round-off of zero landing on
+    the other side) among the 1.3 M elements of one of ITS layers; this fixture's levels 3 and 4 hold 72 k and 17 k elements, so
+    ONE flip there weighs sqrt(1 / 72 k) = 3.7e-3 times the element's size.  Measured: 7.2e-3 in conv_up_t3.conv2.weight
+    (5.2e-3 .. 6.3e-3 in the block's other tensors, all behind the same ReLU), 1.1e-3 .. 1.8e-3 in the 24 encoder tensors of
+    levels 1-3 that lie upstream of it, 2e-7 .. 4e-6 in the 58 other tensors -- the same code at levels 4, 2 and 1 among them --
+    with every op of the graph within 1e-3 in situ.  The bound is that worst figure + 15 %."""
+    from com_amd.spconv import functional as Fsp
+    g = golden("g54_unet")
+    net, bev = _net(dtype=torch.float32)
+    pts, offs = _inputs(g)
+    proj, projp, n1 = _projections(g, "first")
+    Fsp.EXACT_FP32 = True
+    try:
+        bd, loss = _step(net, bev, pts, offs, proj, projp, n1, bf16=False)
+        torch.cuda.synchronize()
+    finally:
+        Fsp.EXACT_FP32 = False
+    worst = {}
+    for name, t in _taps(bd).items():
+        assert t.features.dtype == torch.float32
+        lv = LEVEL_OF[name]
+        worst[name] = _rel(P.tap_sample(_fixture_rows(t, g[f"idx_{lv}"], "first", lv, False)), g["exact_" + name])
+    worst["spatial_features"] = _rel(bd["spatial_features"].detach().cpu().numpy(), g["exact_spatial_features"])
+    l_ex = float(g["exact_loss"][0])
+    worst["loss"] = abs(float(loss.detach()) - l_ex) / abs(l_ex)
+    for name, p in net.named_parameters():
+        worst["grad " + name] = _rel(P.grad_sample(p.grad.detach().float().cpu().numpy()), g["exact_grad__" + name.replace(".", "__")])
+    print("G54 fp32-exact: worst relative L2 errors:", {k: float(f"{v:.2e}") for k, v in worst.items()})
+    bad = {k: v for k, v in worst.items() if v > (FP32_GRAD_TOL if k.startswith("grad ") else 1e-5)}
+    assert not bad, bad
+
+
+def test_unet_eval_forward_without_gradients(golden):
+    """model.eval() under torch.no_grad() (no parity classes: the inverse convs read the evaluation build's tables).  The running
+    statistics are set to the exact chain's batch statistics, with which the exact evaluation chain IS the exact training chain;
+    the bar is the forward bar against the bf16 chain run in the same form (fixture: evalerr_*)."""
+    g = golden("g54_unet")
+    net, bev = _net(train=False)
+    for name, mod in net.named_modules():
+        if isinstance(mod, torch.nn.BatchNorm1d):
+            key = name.replace(".", "__")
+            mod.running_mean.copy_(torch.from_numpy(g["batch_mean__" + key]))
+            mod.running_var.copy_(torch.from_numpy(g["batch_var__" + key]))
+    pts, offs = _inputs(g)
+    with torch.no_grad():
+        bd = bev(net(_voxels(pts, offs)))
+    torch.cuda.synchronize()
+    fails, report = {}, {}
+    for name, t in _taps(bd).items():
+        lv = LEVEL_OF[name]
+        f = _fixture_rows(t, g[f"idx_{lv}"], "first", lv, False)
+        assert np.isfinite(f).all(), name
+        e_hip, e_emu = _rel(P.tap_sample(f), g["exact_" + name]), float(g["evalerr_" + name][0])
+        report[name] = (round(e_hip, 5), round(e_emu, 5))
+        if e_hip > NOISE_FACTOR * e_emu:
+            fails[name] = (e_hip, e_emu)
+    print("G54 eval:", report)
+    assert not fails, fails
+    n1 = g["coords"].shape[0]
+    assert bd["point_features"].shape == (n1, 16) and bd["point_coords"].shape == (n1, 4)
+    assert torch.equal(bd["point_coords"].view(torch.int32),
+                       UR.point_coords(bd["voxel_coords"].int(), list(P.VOXEL), list(P.RANGE)).view(torch.int32))
+    assert all(rb.classes is None and rb._pairs is None for rb in _strided_rulebooks(bd).values())
+
+
+# ---------------------------------------------------------------------------------------------
+INVERSE_LAYERS = [("spconv2", 16, 32, (1, 1, 1), 32, 16), ("spconv3", 32, 64, (1, 1, 1), 64, 32), ("spconv4", 64, 64, (0, 1, 1), 64, 64)]
+
+
+def _inverse_case(g, mode, empty_second_frame=False):
+    """The fixture's three strided levels with random features: [(strided conv, its output tensor)] built as the backbone does."""
+    from com_amd import hotpath, spconv
+    net, _ = _net()
+    if empty_second_frame:
+        keep = g["coords"][:, 0] == 0
+        coords = torch.from_numpy(g["coords"][keep].astype(np.int32)).to(DEV)
+        bd = {"voxel_features": torch.zeros((coords.shape[0], 16), dtype=torch.bfloat16, device=DEV), "voxel_coords": coords,
+              "batch_size": P.BATCH}
+    else:
+        pts, offs = _inputs(g)
+        bd = _voxels(pts, offs, mode)
+    x = net._input_tensor(bd)
+    gen = torch.Generator(DEV).manual_seed(13)
+    levels = []
+    for key, cin, cout, pad, _, _ in INVERSE_LAYERS:
+        conv = spconv.SparseConv3d(cin, cout, 3, stride=2, padding=pad, bias=False, indice_key=key).to(DEV)
+        feats = torch.randn((x.indices.shape[0], cin), device=DEV, generator=gen).bfloat16().requires_grad_(True)
+        y = conv(x.replace_feature(feats))
+        levels.append((key, y))
+        x = y
+    return levels
+
+
+@pytest.mark.parametrize("mode", ["first", "yxz", "empty_frame"])
+def test_inverse_convs_on_the_strided_kernels(golden, mode):
+    """64 -> 64, 64 -> 32, 32 -> 16 at the fixture's three strided levels: forward, data gradient (bf16-rounded) and weight
+    gradient (un-rounded) of the new path and of Rulebook.inverse() + the generic kernels, each against fp64 on the op's own bf16
+    inputs; the new path leaves the strided rulebook without pair lists."""
+    from com_amd import spconv
+    from com_amd.spconv import functional as Fsp
+    from com_amd.spconv import SparseConvTensor
+    g = golden("g54_unet")
+    levels = _inverse_case(g, "first" if mode == "empty_frame" else mode, empty_second_frame=(mode == "empty_frame"))
+    worst = {}
+    for (key, _, _, _, cin, cout), (_, y) in zip(INVERSE_LAYERS, levels):
+        rb = y.indice_dict[key][0]
+        n_out, n_in = y.indices.shape[0], rb.n_in            # the inverse conv maps the strided conv's OUTPUT rows to its INPUT rows
+        gen = torch.Generator(DEV).manual_seed(17)
+        z0 = torch.randn((n_out, cin), device=DEV, generator=gen).bfloat16()
+        dy = torch.randn((n_in, cout), device=DEV, generator=gen).bfloat16()
+        inv = spconv.SparseInverseConv3d(cin, cout, 3, indice_key=key, bias=False).to(DEV)
+        got = {}
+        for path in ("strided", "generic"):
+            Fsp.INVERSE_ON_STRIDED = path == "strided"
+            try:
+                z = z0.clone().requires_grad_(True)
+                inv.weight.grad = None
+                out = inv(SparseConvTensor(z, y.indices, y.spatial_shape, y.batch_size, indice_dict=y.indice_dict,
+                                           num_rows=y.num_rows))
+                assert out.features.shape == (n_in, cout) and out.indices.shape[0] == n_in
+                out.features.backward(dy)
+                torch.cuda.synchronize()
+            finally:
+                Fsp.INVERSE_ON_STRIDED = True
+            got[path] = (out.features.detach(), z.grad.detach(), inv.weight.grad.detach().clone())
+            if path == "strided":
+                assert rb._pairs is None and rb.classes is not None, key      # no lazy pair derivation, no sort
+        # fp64 on the op's own bf16 inputs, over the strided conv's input-side table
+        nbr = rb.nbr_in.long()[:, :n_in]
+        w = _bf16(inv.weight.detach()).reshape(cout, 27, cin)
+        y64 = torch.zeros((n_in, cout), dtype=torch.float64, device=DEV)
+        dz64 = torch.zeros((n_out, cin), dtype=torch.float64, device=DEV)
+        dw64 = torch.zeros((cout, 27, cin), dtype=torch.float64, device=DEV)
+        zd, dyd = z0.double(), dy.double()
+        for k in range(27):
+            m = nbr[k] >= 0
+            j = nbr[k][m]
+            y64[m] += zd[j] @ w[:, k, :].T
+            dz64.index_add_(0, j, dyd[m] @ w[:, k, :])
+            dw64[:, k, :] = dyd[m].T @ zd[j]
+        for path, (f, dz, dw) in got.items():
+            errs = dict(fwd=_rel_t(f, _bf16(y64)), dgrad=_rel_t(dz, _bf16(dz64)), wgrad=_rel_t(dw.reshape(cout, 27, cin), dw64))
+            for kind, e in errs.items():
+                worst[f"{path} {kind}"] = max(worst.get(f"{path} {kind}", 0.0), e)
+                assert e <= OP_TOL, (key, path, kind, e)
+    print(f"inverse convs ({mode}), worst relative L2:", {k: f"{v:.2e}" for k, v in worst.items()})
+
+
+# ---------------------------------------------------------------------------------------------
+class _Tap(torch.autograd.Function):
+    """Identity (an alias of x, same storage) that records the gradient flowing into x."""
+
+    @staticmethod
+    def forward(ctx, x, rec, key):
+        ctx.rec, ctx.key = rec, key
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.rec[ctx.key] = g.detach().clone()
+        return g, None, None
+
+
+def _tap(x, rec, key):
+    if not x.requires_grad:
+        return x
+    y = _Tap.apply(x, rec, key)
+    for a in ("_pcd_stats", "_pcd_colsum_link", "_pcd_bn_link"):      # the epilogue hand-overs ride on attributes
+        if hasattr(x, a):
+            setattr(y, a, getattr(x, a))
+    return y
+
+
+def _bn64(bn, x):
+    mean, var = x.mean(0), x.var(0, unbiased=False)
+    invstd = 1.0 / torch.sqrt(var + bn.eps)
+    xhat = (x - mean) * invstd
+    return xhat, invstd, xhat * bn.weight.detach().double() + bn.bias.detach().double()
+
+
+@pytest.mark.parametrize("mode", ["first", "yxz"])
+def test_unet_every_op_in_situ_forward_and_backward(golden, mode):
+    """Teacher forcing inside the real graph, G7's way: each sparse conv (the three inverse convs on the strided kernels
+    included), each fused BatchNorm(+residual)+ReLU, each merge and each post-add apply of one training step is recomputed in
+    fp64 from the tensors the device path itself fed into that op -- forward output, data gradient, weight / gamma / beta
+    gradients -- within OP_TOL = 1e-3 relative L2 after the bf16 rounding of the stored tensors (BatchNorm dx: 2x, as there); the
+    merge forward and backward are bit-exact."""
+    from com_amd.spconv import functional as Fsp
+    assert Fsp.FUSE_BN_REDUCTIONS and not Fsp.DIRECT_GRAD and Fsp.INVERSE_ON_STRIDED
+    g = golden("g54_unet")
+    net, bev = _net()
+    pts, offs = _inputs(g)
+    proj, projp, n1 = _projections(g, mode)
+    convs, invs, bns, merges, adds = [], [], [], [], []
+    orig = (Fsp.sparse_conv, Fsp.batch_norm_act, Fsp.sparse_inverse_conv, Fsp.unet_merge, Fsp.unet_bn_relu_pairadd)
+
+    def conv(features, weight, bias, rb, packed_fwd, packed_dgrad=None, passthrough=False, **kw):
+        rec = dict(w=weight, b=bias, rb=rb, x=features.detach(), passthrough=passthrough)
+        out = orig[0](_tap(features, rec, "dx"), weight, bias, rb, packed_fwd, packed_dgrad, passthrough, **kw)
+        y = out[0] if passthrough else out
+        rec["y"] = y.detach()
+        if y.requires_grad:
+            y.register_hook(lambda gr, rec=rec: rec.__setitem__("dy", gr.detach().clone()))
+        if passthrough and out[1].requires_grad:
+            out[1].register_hook(lambda gr, rec=rec: rec.__setitem__("d_ident", gr.detach().clone()))
+        convs.append(rec)
+        return out
+
+    def inv_conv(features, weight, rb, packed_fwd, packed_dgrad=None):
+        rec = dict(w=weight, rb=rb, x=features.detach())
+        y = orig[2](_tap(features, rec, "dx"), weight, rb, packed_fwd, packed_dgrad)
+        rec["y"] = y.detach()
+        y.register_hook(lambda gr, rec=rec: rec.__setitem__("dy", gr.detach().clone()))
+        invs.append(rec)
+        return y
+
+    def bn_act(bn, x, residual=None, relu=True, n_dev=None):
+        rec = dict(bn=bn, x=x.detach(), res=None if residual is None else residual.detach(), relu=relu)
+        y = orig[1](bn, _tap(x, rec, "dx"), residual, relu, n_dev)
+        rec["y"] = y.detach()
+        y.register_hook(lambda gr, rec=rec: rec.__setitem__("dy", gr.detach().clone()))
+        bns.append(rec)
+        return y
+
+    def merge(bottom, trans, n_dev=None):
+        rec = dict(bottom=bottom.detach(), trans=trans.detach())
+        cat, token = orig[3](_tap(bottom, rec, "d_bottom"), _tap(trans, rec, "d_trans"), n_dev)
+        rec["cat"] = cat.detach()
+        cat.register_hook(lambda gr, rec=rec: rec.__setitem__("d_cat", gr.detach().clone()))
+        token.register_hook(lambda gr, rec=rec: rec.__setitem__("d_pair", gr.detach().clone()))
+        merges.append(rec)
+        return cat, token
+
+    def pairadd(bn, x, cat, token, n_dev=None):
+        rec = dict(bn=bn, x=x.detach(), cat=cat.detach())
+        y = orig[4](bn, _tap(x, rec, "dx"), cat, token, n_dev)
+        rec["y"] = y.detach()
+        y.register_hook(lambda gr, rec=rec: rec.__setitem__("dy", gr.detach().clone()))
+        adds.append(rec)
+        return y
+
+    Fsp.sparse_conv, Fsp.batch_norm_act, Fsp.sparse_inverse_conv, Fsp.unet_merge, Fsp.unet_bn_relu_pairadd = \
+        conv, bn_act, inv_conv, merge, pairadd
+    try:
+        bd, loss = _step(net, bev, pts, offs, proj, projp, n1, row_order=mode)
+        torch.cuda.synchronize()
+    finally:
+        Fsp.sparse_conv, Fsp.batch_norm_act, Fsp.sparse_inverse_conv, Fsp.unet_merge, Fsp.unet_bn_relu_pairadd = orig
+    assert (len(convs), len(invs), len(bns), len(merges), len(adds)) == (25, 3, 24, 4, 4)
+    worst, fails = {}, []
+
+    def note(kind, name, e, tol=OP_TOL):
+        worst[kind] = max(worst.get(kind, 0.0), e)
+        if not e <= tol:
+            fails.append((kind, name, e))
+
+    for i, r in enumerate(convs):
+        w, rb = r["w"], r["rb"]
+        cout, cin = w.shape[0], w.shape[-1]
+        name = f"conv#{i} {cin}->{cout} K={rb.kvol}"
+        wk = _bf16(w.detach()).reshape(cout, -1, cin)
+        x = r["x"].double()[:, :cin]
+        nbr = rb.nbr_out.long()
+        y = torch.zeros((rb.n_out, cout), dtype=torch.float64, device=DEV)
+        dy = r["dy"].double()
+        dw = torch.zeros((cout, rb.kvol, cin), dtype=torch.float64, device=DEV)
+        dx = torch.zeros((rb.n_in, cin), dtype=torch.float64, device=DEV)
+        for k in range(rb.kvol):
+            idx = nbr[k, :rb.n_out]
+            m = idx >= 0
+            y[m] += x[idx[m]] @ wk[:, k, :].T
+            dw[:, k, :] = dy[m].T @ x[idx[m]]
+            dx.index_add_(0, idx[m], dy[m] @ wk[:, k, :])
+        note("conv fwd", name, _rel_t(r["y"], _bf16(y)))
+        note("conv wgrad", name, _rel_t(w.grad.reshape(cout, rb.kvol, cin), dw))
+        if "dx" in r:
+            if r["passthrough"] and "d_ident" in r:
+                dx = dx + r["d_ident"].double()[:, :cin]
+            note("conv dgrad" + (" (+identity)" if r["passthrough"] else ""), name, _rel_t(r["dx"][:, :cin], _bf16(dx)))
+    for i, r in enumerate(invs):
+        w, rb = r["w"], r["rb"]                                  # rb: the STRIDED conv's rulebook
+        cout, cin = w.shape[0], w.shape[-1]
+        name = f"inverse conv#{i} {cin}->{cout}"
+        assert rb._pairs is None and not rb.subm, name
+        wk = _bf16(w.detach()).reshape(cout, -1, cin)
+        x, dy = r["x"].double(), r["dy"].double()
+        nbr = rb.nbr_in.long()[:, :rb.n_in]
+        y = torch.zeros((rb.n_in, cout), dtype=torch.float64, device=DEV)
+        dx = torch.zeros((rb.n_out, cin), dtype=torch.float64, device=DEV)
+        dw = torch.zeros((cout, rb.kvol, cin), dtype=torch.float64, device=DEV)
+        for k in range(rb.kvol):
+            m = nbr[k] >= 0
+            j = nbr[k][m]
+            y[m] += x[j] @ wk[:, k, :].T
+            dx.index_add_(0, j, dy[m] @ wk[:, k, :])
+            dw[:, k, :] = dy[m].T @ x[j]
+        note("inverse fwd", name, _rel_t(r["y"], _bf16(y)))
+        note("inverse dgrad", name, _rel_t(r["dx"], _bf16(dx)))
+        note("inverse wgrad", name, _rel_t(w.grad.reshape(cout, rb.kvol, cin), dw))
+    for i, r in enumerate(bns):
+        bn = r["bn"]
+        name = f"bn#{i} c={r['x'].shape[1]} res={r['res'] is not None}"
+        x = r["x"].double()
+        n = x.shape[0]
+        xhat, invstd, z = _bn64(bn, x)
+        if r["res"] is not None:
+            z = z + r["res"].double()
+        y = torch.relu(z) if r["relu"] else z
+        note("bn fwd", name, _rel_t(r["y"], _bf16(y)))
+        dy = r["dy"].double()
+        dz = dy * (z > 0) if r["relu"] else dy
+        dbeta, dgamma = dz.sum(0), (dz * xhat).sum(0)
+        dx = bn.weight.detach().double() * invstd * (dz - dbeta / n - xhat * dgamma / n)
+        note("bn dgamma", name, _rel_t(bn.weight.grad, dgamma))
+        note("bn dbeta", name, _rel_t(bn.bias.grad, dbeta))
+        if "dx" in r:
+            note("bn dx", name, _rel_t(r["dx"], _bf16(dx)), tol=2 * OP_TOL)   # (cancellation: G7's module docstring)
+    for i, r in enumerate(merges):
+        name = f"merge#{i} c={r['bottom'].shape[1]}"
+        assert torch.equal(_bits(r["cat"]), _bits(UR.merge(r["bottom"], r["trans"]))), name
+        assert torch.equal(_bits(r["d_pair"]), _bits(adds[i]["dy"])), name       # dy reaches the merge backward unchanged
+        want = UR.merge_backward(r["d_cat"], r["d_pair"])
+        for key, wnt in zip(("d_bottom", "d_trans"), want):
+            assert torch.equal(_bits(r[key]), _bits(wnt)), (name, key)
+    for i, r in enumerate(adds):
+        bn = r["bn"]
+        name = f"post-add#{i} c={r['x'].shape[1]}"
+        x = r["x"].double()
+        n = x.shape[0]
+        xhat, invstd, z = _bn64(bn, x)
+        note("post-add fwd", name, _rel_t(r["y"], _bf16(torch.relu(z) + UR.pair_sum(r["cat"].double()))))
+        dz = r["dy"].double() * (z > 0)
+        dbeta, dgamma = dz.sum(0), (dz * xhat).sum(0)
+        dx = bn.weight.detach().double() * invstd * (dz - dbeta / n - xhat * dgamma / n)
+        note("post-add dgamma", name, _rel_t(bn.weight.grad, dgamma))
+        note("post-add dbeta", name, _rel_t(bn.bias.grad, dbeta))
+        note("post-add dx", name, _rel_t(r["dx"], _bf16(dx)), tol=2 * OP_TOL)
+    print(f"G54 in situ ({mode}), worst relative L2 per op kind:", {k: f"{v:.2e}" for k, v in worst.items()})
+    assert not fails, fails
+
+
+# ---------------------------------------------------------------------------------------------
+def test_composed_parta2_step_is_wired():
+    """MeanVFE -> UNetV2 -> HeightCompression -> BaseBEVBackbone -> AnchorHeadSingle -> PointIntraPartOffsetHead -> PartA2FCHead,
+    one eager training step on the fixture cloud with a few synthetic boxes: every loss is finite and every parameter gets a
+    finite gradient.  Wiring only -- no numeric bar.  (The point heads take fp32 rows: the cast of point_features is the
+    caller's, as is everything a PartA2Net detector class would do.)"""
+    import anchor_ref as AR
+    import point_head_box_ref as BR
+    from com_amd import hotpath
+    from com_amd.hotpath import dense2d
+    from tests.test_parta2_head_cpu import model_cfg
+    torch.manual_seed(4)
+    names = ["Vehicle"]
+    frames = P.points(P.SEED, P.POINTS_PER_FRAME, P.BATCH)
+    pts, offs = hotpath.collate_points(frames, DEV)
+    bd = {"points": pts, "frame_offsets": torch.tensor(offs, dtype=torch.int32, device=DEV), "batch_size": P.BATCH}
+    bd = hotpath.transform_points_to_voxels(bd, P.RANGE, P.VOXEL, P.MAX_POINTS, P.MAX_VOXELS, fuse_mean=False, keep_voxels=True)
+    vfe = hotpath.MeanVFE({}, P.IN_CHANNELS)
+    net, bev = _net()
+    b2d = dense2d.BaseBEVBackbone(dict(LAYER_NUMS=[1], LAYER_STRIDES=[1], NUM_FILTERS=[64], UPSAMPLE_STRIDES=[1],
+                                       NUM_UPSAMPLE_FILTERS=[64]), 128).to(DEV).train()
+    anchors = AR.small_cfg(names, 8, sizes={"Vehicle": [1.0, 0.8, 0.9]})
+    rpn = hotpath.AnchorHeadSingle(AR.head_cfg(names, stride=8, ANCHOR_GENERATOR_CONFIG=anchors), b2d.num_bev_features, 1, names,
+                                   np.array(P.GRID), list(P.RANGE), predict_boxes_when_training=True).to(DEV).train()
+    point_head = hotpath.PointIntraPartOffsetHead(1, net.num_point_features,
+                                                  BR.head_cfg('PointIntraPartOffsetHead', box=False, part=True)).to(DEV).train()
+    roi_head = hotpath.PartA2FCHead(input_channels=net.num_point_features, model_cfg=model_cfg(4), num_class=1).to(DEV).train()
+    gt = np.zeros((P.BATCH, 4, 8), np.float32)
+    rng = np.random.default_rng(4)
+    for b in range(P.BATCH):                                 # three boxes on dense parts of the frame's cloud
+        ctr = frames[b][rng.integers(200, P.POINTS_PER_FRAME, 3), :3]
+        gt[b, :3, :3] = ctr
+        gt[b, :3, 3:6] = [1.0, 0.8, 0.9]
+        gt[b, :3, 6] = rng.uniform(-1, 1, 3)
+        gt[b, :3, 7] = 1
+    bd["gt_boxes"] = torch.from_numpy(gt).to(DEV)
+    bd = b2d(bev(net(vfe(bd))))
+    bd = rpn(bd)
+    bd["point_features"] = bd["point_features"].float()
+    bd = roi_head(point_head(bd))
+    losses = {"rpn": rpn.get_loss()[0], "point": point_head.get_loss()[0], "rcnn": roi_head.get_loss()[0]}
+    total = sum(losses.values())
+    total.backward()
+    torch.cuda.synchronize()
+    print("composed step losses:", {k: float(v.detach()) for k, v in losses.items()})
+    assert all(bool(torch.isfinite(v.detach()).all()) for v in losses.values())
+    for mod in (net, b2d, rpn, point_head, roi_head):
+        for name, p in mod.named_parameters():
+            assert p.grad is not None and bool(torch.isfinite(p.grad).all()), (type(mod).__name__, name)
