@@ -3,7 +3,7 @@
 // anchorhead_cur.hip: its COM curriculum form; anchorhead_multi.hip: AnchorHeadMulti, kind-major).  A layout says how
 // anchor n becomes (global kind, y, x), how wide a kind row is, which head descriptor owns a kind and where the logits
 // of an anchor go in the decode output; everything else -- the rule of the assignment, the arithmetic of the loss, the
-// coder -- exists once.  focal_el and the ordered finish also serve the point head (roiaware.hip).  Include inside the
+// coder -- exists once.  focal_el and the ordered finish also serve the point heads (pointhead.hip).  Include inside the
 // translation unit (everything is file-local).
 #pragma once
 #include "common.h"
@@ -339,7 +339,7 @@ __device__ __forceinline__ float anc_cur_weight(const AncCur &q, const float *sv
 
 // One element of SigmoidFocalClassificationLoss (loss_utils.py:41-74), alpha 0.25, gamma 2, for a logit xv and a target t
 // in {0, 1}: the unweighted loss (GRAD == false) or its derivative with respect to the logit (GRAD == true).  The anchor
-// heads (below) and the point head (roiaware.hip) weight it per anchor / per point.
+// heads (below) and the point heads (pointhead.hip) weight it per anchor / per point.
 template <bool GRAD>
 __device__ __forceinline__ float focal_el(float xv, float t) {
     const float p = 1.f / (1.f + expf(-xv));

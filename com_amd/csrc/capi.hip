@@ -1,7 +1,7 @@
 // Library info entry points of libpcdops_hip.so.
 #include "common.h"
 
-extern "C" int pcd_version(void) { return 500; /* 0.5.0 */ }
+extern "C" int pcd_version(void) { return 600; /* 0.6.0 */ }
 
 extern "C" const char *pcd_build_arch(void) { return "gfx950"; }
 

@@ -16,6 +16,7 @@
 
 #define RA_MARGIN_DEVICE 1e-5f   // roiaware_pool3d_kernel.cu:27
 #define RA_MARGIN_HOST 1e-2f     // roiaware_pool3d.cpp:131
+#define RA_CHUNK 128             // boxes a workgroup stages in LDS per pass (roiaware.hip, pointhead.hip)
 
 struct RaBox {
     float cx, cy, cz, hz, cosa, sina;

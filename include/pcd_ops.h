@@ -60,10 +60,11 @@ int pcd_version(void);                    /* 10000*major + 100*minor + patch; 0.
                                              plane-form dense weight gradient left the ABI; 0.3.0: the entry points whose
                                              successors take a superset of their arguments left it; 0.4.0: the
                                              pcd_voxel2pinds_* / pcd_voxel_pool_* entry points joined; 0.5.0: the
-                                             pcd_vector_pool_* entry points joined.  A missing lower
-                                             version number (pcd_adam_flat_step_v4 without _v3, pcd_sparse_conv_wgrad_v2
-                                             without the unsuffixed form, _ld / _bn / _dir without the plain form) means
-                                             "retired": the survivors keep their names */
+                                             pcd_vector_pool_* entry points joined; 0.6.0: pcd_point_head_assign_targets
+                                             left it (pcd_point_head_assign_targets_full does its work).  A
+                                             missing lower version number (pcd_adam_flat_step_v4 without _v3,
+                                             pcd_sparse_conv_wgrad_v2 without the unsuffixed form, _ld / _bn / _dir / _full
+                                             without the plain form) means "retired": the survivors keep their names */
 const char *pcd_error_string(int code);
 const char *pcd_build_arch(void);         /* "gfx950" */
 /* text of the HIP runtime error behind the calling thread's last PCD_ERR_LAUNCH */
@@ -1396,7 +1397,7 @@ int pcd_sparse_conv_subm_window_f32(const void *x, int n_rows, int c_in, const v
                                     int c_out, void *y, float *y_f32, const void *addend, void *stream);
 
 /* ============================================================================================
- * (f5) Point-in-box tests, RoI-aware pooling and the PointHeadSimple targets / loss -- replaces pcdet/ops/roiaware_pool3d
+ * (f5) Point-in-box tests, RoI-aware pooling and the point heads' targets / losses / decoding -- replaces pcdet/ops/roiaware_pool3d
  *      (binder src/roiaware_pool3d.cpp:172-177; kernels src/roiaware_pool3d_kernel.cu; Python callers
  *      roiaware_pool3d_utils.py:9-107) and the host loops of pcdet/models/dense_heads/point_head_template.py.
  *      Boxes are rows of 7 float32 (x, y, z, dx, dy, dz, heading); the arithmetic of the test is the reference's, step by
@@ -1409,40 +1410,47 @@ int pcd_sparse_conv_subm_window_f32(const void *x, int n_rows, int c_in, const v
  *   pcd_points_in_boxes: points_in_boxes_gpu (roiaware_pool3d.cpp:98-118, roiaware_pool3d_kernel.cu:313-359).  boxes
  *                [batch][num_boxes][7], pts [batch][num_pts][3]; box_idx_of_pts [batch][num_pts] int32 receives the LOWEST
  *                index of a box that contains the point, -1 for a point in no box (every element written); MARGIN 1e-5.
- *   pcd_point_head_assign_targets: PointHeadSimple.assign_targets (point_head_simple.py:21-48) = enlarge_box3d
- *                (box_utils.py:187-200) + assign_stack_targets with set_ignore_flag (point_head_template.py:49-129) for the
- *                whole stacked batch.  point_coords [num_points][4] rows of (bs_idx, x, y, z); gt_boxes [batch][n_boxes][8]
- *                (7 box floats + class, zero rows = padding); extra_x / _y / _z = TARGET_CONFIG.GT_EXTRA_WIDTH, added to
- *                dx, dy, dz of EVERY row (padding rows included, as the reference does).  point_cls_labels int64
- *                [num_points]: the class of the first box that contains the point (1 when num_class == 1), -1 where
- *                foreground XOR inside-any-enlarged-box, 0 otherwise.  *num_pos (device int32) = number of labels > 0
- *                (integer atomics: deterministic).  No read-back: capturable.
- *   pcd_point_head_loss_forward / _backward: get_cls_layer_loss (point_head_template.py:131-155):
- *                SigmoidFocalClassificationLoss(alpha 0.25, gamma 2) over logits [num_points][num_class] (f32 or bf16, rows
- *                row_stride elements apart) with weights ((label == 0) + (label > 0)) / max(*num_pos, 1), summed in a fixed
- *                order (bit-reproducible) and multiplied by cls_weight.  out = 4 device floats: out[0] = out[1] = the loss,
- *                out[2] = out[3] = 0 (the ordered finish pass of the anchor heads is reused).  backward: d_logits (layout
- *                and dtype of logits, every element written) = *grad_out (device f32) x d loss / d logits.
- *   pcd_point_head_assign_targets_full: the targets of PointHeadBox (point_head_box.py:32-59) and PointIntraPartOffsetHead
- *                (point_intra_part_head.py:39-66): assign_stack_targets with set_ignore_flag and ret_box_labels and / or
- *                ret_part_labels (point_head_template.py:49-129), one launch for the whole stacked batch.  Labels and *num_pos
- *                by the rules of pcd_point_head_assign_targets.  point_box_labels f32 [num_points][8] (NULL: not wanted; 16-byte
- *                aligned) = PointResidualCoder.encode_torch (box_coder_utils.py:153-187) of the first containing box at the
+ *   The point heads (com_amd/csrc/pointhead.hip) have ONE targets entry for PointHeadSimple, PointHeadBox and
+ *   PointIntraPartOffsetHead.  (Retired: pcd_point_head_assign_targets, which was that entry with both label pointers NULL.)
+ *   pcd_point_head_assign_targets_full: the targets of PointHeadSimple (point_head_simple.py:21-48), PointHeadBox
+ *                (point_head_box.py:32-59) and PointIntraPartOffsetHead (point_intra_part_head.py:39-66) = enlarge_box3d
+ *                (box_utils.py:187-200) + assign_stack_targets with set_ignore_flag (point_head_template.py:49-129), one launch
+ *                for the whole stacked batch.  point_coords [num_points][4] rows of (bs_idx, x, y, z); gt_boxes
+ *                [batch][n_boxes][8] (7 box floats + class, zero rows = padding); extra_x / _y / _z =
+ *                TARGET_CONFIG.GT_EXTRA_WIDTH, added to dx, dy, dz of EVERY row (padding rows included, as the reference
+ *                does).  point_cls_labels int64 [num_points]: the class of the first box that contains the point (1 when
+ *                num_class == 1), -1 where foreground XOR inside-any-enlarged-box, 0 otherwise.  *num_pos (device int32) =
+ *                number of labels > 0 (integer atomics: deterministic).  No read-back: capturable.
+ *                point_box_labels f32 [num_points][8] (ret_box_labels; NULL: not wanted; 16-byte aligned) =
+ *                PointResidualCoder.encode_torch (box_coder_utils.py:153-187) of the first containing box at the
  *                point: sizes clamped to 1e-5; mean_size (DEVICE f32 [num_mean][3], num_mean <= 16; NULL / 0 =
  *                use_mean_size False) is indexed by (int)column 7 - 1 of the GT row even when num_class == 1, CLAMPED to
  *                [0, num_mean - 1] (the reference asserts class <= num_mean and wraps class 0 to the last row).
- *                point_part_labels f32 [num_points][3] (NULL: not wanted) = the point in the box's frame / (dx, dy, dz) + 0.5
- *                (:114-122; the clamped sizes when box labels are written too, as encode_torch clamps in place).  Both are
- *                zero on every point that is not foreground; every row is written.
+ *                point_part_labels f32 [num_points][3] (ret_part_labels; NULL: not wanted) = the point in the box's frame /
+ *                (dx, dy, dz) + 0.5 (:114-122; the clamped sizes when box labels are written too, as encode_torch clamps in
+ *                place).  Both are zero on every point that is not foreground; every row is written.  Both NULL
+ *                (PointHeadSimple): the kernel instantiation without the row bookkeeping runs.
+ *   pcd_point_head_loss_forward / _backward: PointHeadSimple's get_cls_layer_loss (point_head_template.py:131-155):
+ *                SigmoidFocalClassificationLoss(alpha 0.25, gamma 2; loss_utils.py:10-74) over logits [num_points][num_class]
+ *                (f32 or bf16, rows row_stride elements apart) with weights ((label == 0) + (label > 0)) / max(*num_pos, 1),
+ *                summed in a fixed order (bit-reproducible) and multiplied by cls_weight.  out = 4 device floats: out[0] =
+ *                out[1] = the loss, out[2] = out[3] = 0 (the ordered finish pass of the anchor heads is reused).  backward:
+ *                d_logits (layout and dtype of logits, every element written) = *grad_out (ONE device f32) x d loss /
+ *                d logits.  The _full entries below compute the same bits with NULL branches; this pair stays because
+ *                PointHeadSimple's replayed training step measured slower through them: this backward takes
+ *                the one upstream gradient as autograd delivers it, the _full backward wants four floats assembled.
  *   pcd_point_head_full_loss_forward / _backward: get_cls_layer_loss + get_box_layer_loss + get_part_layer_loss
  *                (point_head_template.py:131-191) in one pass.  Predictions f32 or bf16 (one dtype), rows *_stride elements
- *                apart; box_preds / part_preds NULL = the head has no such branch.  cls: as pcd_point_head_loss_forward.
+ *                apart; box_preds / part_preds NULL = the head has no such branch (its labels, code_weights and gradient
+ *                pointer may be NULL too).  cls: as pcd_point_head_loss_forward.
  *                box: WeightedSmoothL1Loss (loss_utils.py:338-399; nan targets ignored, code_weights = 8 device floats, beta
  *                1/9) with weights (label > 0) / max(*num_pos, 1), x box_weight.  part: F.binary_cross_entropy(sigmoid(p), t)
  *                over the 3 columns of the positives / (3 max(*num_pos, 1)) x part_weight, computed from the LOGIT as
  *                t softplus(-p) + (1 - t) softplus(p) with each log term capped at 100: the reference in EXACT arithmetic
  *                (its fp32 path rounds sigmoid(p) to 0 or 1 near |p| = 17 and then differs; this does not).  out = 4 device
- *                floats: cls + (box + part), cls, box, part (0 for an absent branch); fixed summation order.  backward:
+ *                floats: cls + (box + part), cls, box, part (0 for an absent branch), summed in a fixed order
+ *                (bit-reproducible; the ordered finish pass of the anchor heads).  Both branches NULL:
+ *                out[0] = out[1] = the classification loss, out[2] = out[3] = 0.  backward:
  *                d_cls / d_box / d_part (layout and dtype of the predictions, every element written: zeros on ignored points
  *                for cls, on non-positive points and nan targets for box / part); grad_out = 4 device floats, the upstream
  *                gradients of out[0..4): a term is scaled by grad_out[0] + grad_out[1 + term].
@@ -1467,9 +1475,10 @@ int pcd_sparse_conv_subm_window_f32(const void *x, int n_rows, int c_in, const v
 int pcd_points_in_boxes_host(const float *boxes_host, int num_boxes, const float *pts_host, int num_pts, int *out_host);
 int pcd_points_in_boxes(const float *boxes, const float *pts, int batch, int num_boxes, int num_pts, int *box_idx_of_pts,
                         void *stream);
-int pcd_point_head_assign_targets(const float *point_coords, int num_points, const float *gt_boxes, int batch, int n_boxes,
-                                  float extra_x, float extra_y, float extra_z, int num_class, long long *point_cls_labels,
-                                  int *num_pos, void *stream);
+int pcd_point_head_assign_targets_full(const float *point_coords, int num_points, const float *gt_boxes, int batch, int n_boxes,
+                                       float extra_x, float extra_y, float extra_z, int num_class, const float *mean_size,
+                                       int num_mean, long long *point_cls_labels, float *point_box_labels,
+                                       float *point_part_labels, int *num_pos, void *stream);
 size_t pcd_point_head_loss_workspace_bytes(int num_points);
 int pcd_point_head_loss_forward(const void *logits, int dtype, long long row_stride, const long long *point_cls_labels,
                                 const int *num_pos, int num_points, int num_class, float cls_weight, float *out,
@@ -1477,10 +1486,6 @@ int pcd_point_head_loss_forward(const void *logits, int dtype, long long row_str
 int pcd_point_head_loss_backward(const void *logits, void *d_logits, int dtype, long long row_stride,
                                  const long long *point_cls_labels, const int *num_pos, int num_points, int num_class,
                                  float cls_weight, const float *grad_out, void *stream);
-int pcd_point_head_assign_targets_full(const float *point_coords, int num_points, const float *gt_boxes, int batch, int n_boxes,
-                                       float extra_x, float extra_y, float extra_z, int num_class, const float *mean_size,
-                                       int num_mean, long long *point_cls_labels, float *point_box_labels,
-                                       float *point_part_labels, int *num_pos, void *stream);
 size_t pcd_point_head_full_loss_workspace_bytes(int num_points);
 int pcd_point_head_full_loss_forward(const void *cls_preds, long long cls_stride, const void *box_preds, long long box_stride,
                                      const void *part_preds, long long part_stride, int dtype,

@@ -6,8 +6,12 @@ Run ONCE, on the GPU, on the commit BEFORE a change that must leave these kernel
 file and tests/kernel_digests.py into a checkout of that commit.  Every group is recorded twice; the two records must agree
 (a kernel that sums with atomics would show here), or nothing is written.
 
-Usage: python tests/golden/make_kernel_digests.py [output.json]
+With group names, only those groups are recorded and merged into the existing file: the entries of every other group stay
+as they are.
+
+Usage: python tests/golden/make_kernel_digests.py [--out output.json] [group ...]
 """
+import argparse
 import json
 import os
 import sys
@@ -19,18 +23,26 @@ import kernel_digests as K  # noqa: E402
 
 
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "kernel_digests.json")
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(HERE, "kernel_digests.json"))
+    ap.add_argument("groups", nargs="*", help="record only these groups (default: all)")
+    args = ap.parse_args()
+    assert set(args.groups) <= set(K.GROUPS), f"groups are {K.GROUPS}"
     golden = {}
-    for group in K.GROUPS:
+    if args.groups:
+        with open(args.out) as f:
+            golden = json.load(f)
+    for group in args.groups or K.GROUPS:
         first, again = K.record(group), K.record(group)
         differ = sorted(k for k in first if first[k] != again[k])
         assert not differ, f"{group}: two runs of the same code differ in {differ}"
         golden[group] = first
         print(f"{group:18s} {len(first)} digests")
-    multi = {k: v for k, v in golden["subm_window"].items() if k.endswith("multi_pass_tiles")}
-    print("multi-pass tiles:", multi)
-    assert all(multi[f"dense/{ch}/multi_pass_tiles"] > 0 for ch in (16, 32, 64)), "the dense block must have multi-pass tiles"
-    with open(out, "w") as f:
+    if "subm_window" in (args.groups or K.GROUPS):
+        multi = {k: v for k, v in golden["subm_window"].items() if k.endswith("multi_pass_tiles")}
+        print("multi-pass tiles:", multi)
+        assert all(multi[f"dense/{ch}/multi_pass_tiles"] > 0 for ch in (16, 32, 64)), "the dense block must have multi-pass tiles"
+    with open(args.out, "w") as f:
         json.dump(golden, f, indent=0, sort_keys=True)
         f.write("\n")
 

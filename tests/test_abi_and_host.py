@@ -102,8 +102,9 @@ def test_header_lists_exactly_the_tuning_options_of_the_library():
 def test_retired_kernels_are_out_of_the_library():
     """The measured-slower kernels were retired: the library exports none of their entry points (the
     five of the former EXPERIMENTS build and the two of the plane-form dense weight gradient), nor the entry points whose
-    successors take a superset of their arguments (ABI 0.3.0); it has no 128-channel window configuration, and rejects the
-    retired option keys like any unknown key."""
+    successors take a superset of their arguments (ABI 0.3.0), nor PointHeadSimple's own targets entry
+    (pcd_point_head_assign_targets_full with NULL box / part label pointers does its work); it has no 128-channel window configuration,
+    and rejects the retired option keys like any unknown key."""
     from com_amd import _lib
     default = ctypes.CDLL(_lib.LIB_PATH)
     retired = ["pcd_sparse_conv_gather_gemm_zfast", "pcd_sparse_conv_pairs", "pcd_sparse_conv_pairs_seg",
@@ -111,7 +112,8 @@ def test_retired_kernels_are_out_of_the_library():
                "pcd_conv2d_wgrad_planes_splits", "pcd_conv2d_wgrad_planes_nhwc",
                "pcd_adam_flat_step", "pcd_adam_flat_step_v2", "pcd_adam_flat_step_v3", "pcd_sparse_conv_wgrad",
                "pcd_sparse_conv_dgrad_classes", "pcd_bn_forward", "pcd_bn_backward", "pcd_conv2d_3x3_nhwc",
-               "pcd_conv2d_3x3_nhwc_ld", "pcd_sparse_conv_gather_gemm_tiles", "pcd_subm_window_set_trace"]
+               "pcd_conv2d_3x3_nhwc_ld", "pcd_sparse_conv_gather_gemm_tiles", "pcd_subm_window_set_trace",
+               "pcd_point_head_assign_targets"]
     for name in retired:
         assert not hasattr(default, name), f"{name} was retired: it must not be in the library"
     assert not set(retired) & set(_declared_symbols()) and not set(retired) & set(_lib.PROTOTYPES)

@@ -1,6 +1,8 @@
 """GPU: the window kernels (forward, data gradient, weight gradient), every instantiation the gather-GEMM dispatch returns, the
 class-grouped data gradient and the bucket farthest point sampling compute, bit for bit, what they computed on the commit
-before their ablation switches and trace stamps were taken out (tests/golden/kernel_digests.json, written there by
+before their ablation switches and trace stamps were taken out; the anchor heads and the point heads (PointHeadSimple,
+PointHeadBox, PointIntraPartOffsetHead: targets, losses with their gradients, decoding) what they computed on the commit before
+each family was folded onto one core (tests/golden/kernel_digests.json, written there by
 tests/golden/make_kernel_digests.py from the cases of tests/kernel_digests.py).  None of them sums with float atomics (the
 record was taken twice and agreed), so every output compares by sha256.
 
