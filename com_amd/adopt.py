@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .hotpath import backbone3d, center_head, curriculum_head, dense2d, map_to_bev, unet, vfe
+from .hotpath import anchor_head, backbone3d, center_head, curriculum_head, dense2d, map_to_bev, unet, vfe
 from .hotpath.conv2d_fast import BatchNormReLU2d
 from .spconv.conv import SparseConvolution
 
@@ -262,6 +262,48 @@ def _adopt_head(path, s, cls, **_):
     return _rehome(path, s, new, extra_ok=extra)
 
 
+_ANCHOR_LOSS_CHILDREN = ("cls_loss_func", "reg_loss_func", "dir_loss_func")
+
+
+def _adopt_anchor_head(path, s, cls, model=None, **_):
+    """AnchorHeadSingle (anchor_head_single.py + anchor_head_template.py).  The stock head keeps neither grid_size nor
+    point_cloud_range; Detector3DTemplate keeps `dataset`, which has both.  The counterpart describes its anchors instead of
+    storing them, from its own host generator: they must equal the stock head's `anchors` bit for bit."""
+    try:
+        cin = int(s.conv_cls.in_channels)
+    except AttributeError as exc:
+        raise _Refuse(path, f"no conv_cls conv ({exc})") from exc
+    dataset = getattr(model, "dataset", None)
+    if dataset is None:
+        raise _Refuse(path, "the model has no `dataset` (grid_size / point_cloud_range of an anchor head come from "
+                            "model.dataset)")
+    for a in ("grid_size", "point_cloud_range"):
+        if getattr(dataset, a, None) is None:
+            raise _Refuse(path, f"model.dataset has no {a}")
+    for k in _ANCHOR_LOSS_CHILDREN:                          # the stock loss modules are replaced, so they must hold no state
+        m = getattr(s, k, None)
+        if isinstance(m, nn.Module) and (list(m.parameters()) or m.state_dict()):
+            raise _Refuse(f"{path}.{k}", "loss module with parameters / persistent buffers")
+    try:
+        new = _build(lambda: cls(s.model_cfg, cin, s.num_class, s.class_names, dataset.grid_size, dataset.point_cloud_range,
+                                 predict_boxes_when_training=getattr(s, "predict_boxes_when_training", True)))
+    except L.PcdError as exc:
+        raise _Refuse(path, str(exc)) from exc
+    stock_anchors = getattr(s, "anchors", None)
+    if not isinstance(stock_anchors, (list, tuple)) or len(stock_anchors) != len(new.anchors):
+        raise _Refuse(f"{path}.anchors", f"no list of {len(new.anchors)} anchor tensors")
+    for i, (a, b) in enumerate(zip(stock_anchors, new.anchors)):
+        a = a.detach().cpu()
+        if a.dtype != b.dtype or tuple(a.shape) != tuple(b.shape) or not torch.equal(a, b):
+            raise _Refuse(f"{path}.anchors[{i}]", "differs from the anchors the fused head generates from model.dataset's "
+                                                  "grid_size / point_cloud_range")
+    _same(path, "num_anchors_per_location", int(s.num_anchors_per_location), int(new.num_anchors_per_location))
+    _same(path, "box_coder", type(s.box_coder).__name__, "ResidualCoder")
+    _same(path, "box_coder.code_size", int(s.box_coder.code_size), int(new.box_coder.code_size))
+    _match(path, s, new, extra_ok=_ANCHOR_LOSS_CHILDREN)
+    return _rehome(path, s, new, extra_ok=_ANCHOR_LOSS_CHILDREN)
+
+
 # class name -> (adopter, counterpart class)
 RECOGNISED = {
     "MeanVFE": (_adopt_vfe, vfe.MeanVFE),
@@ -273,6 +315,7 @@ RECOGNISED = {
     "CenterHead": (_adopt_head, center_head.CenterHead),
     "CurriculumCenterHead": (_adopt_head, curriculum_head.CurriculumCenterHead),
     "CurriculumCenterHead_x5": (_adopt_head, curriculum_head.CurriculumCenterHead_x5),
+    "AnchorHeadSingle": (_adopt_anchor_head, anchor_head.AnchorHeadSingle),
 }
 _FUSED = tuple({c for _, c in RECOGNISED.values()})
 
@@ -304,7 +347,7 @@ def adopt_model(model, *, strict=True, bev_channels_last=True):
             if entry is None:
                 raise _Refuse(path, f"unknown module class {name}")
             adopter, cls = entry
-            new = adopter(path, s, cls=cls, channels_last=bev_channels_last)
+            new = adopter(path, s, cls=cls, channels_last=bev_channels_last, model=model)
         except _Refuse as exc:
             if strict:
                 raise L.PcdError(f"adopt_model: {exc.path}: {exc.reason} (strict=False leaves the module as it is)") from None

@@ -536,35 +536,20 @@ struct AncDecodeCfg {
     float dir_offset, dir_limit_offset, period;
 };
 
-// boxes [B][N][code - sincos] (box_coder_utils.py:54-77 + anchor_head_template.py:258-269) and the logits as fp32 where the
-// layout puts them
-template <class Layout>
-__global__ __launch_bounds__(256) void anc_decode_kernel(Layout lay, AncDecodeCfg c, const float *kinds, const float *shifts,
-                                                         float *box_out) {
-    __shared__ float s_kind[ANC_MAX_KINDS * Layout::KIND_F];
-    __shared__ typename Layout::Shared s_lay;
-    const int HW = c.H * c.W, N = HW * c.G;
-    const int b = blockIdx.y;
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    lay.stage(s_lay);
-    stage_kinds(s_kind, kinds, c.G * Layout::KIND_F);
-    if (n >= N) return;
-    const AncGeom q = Layout::geom(n, c.H, c.W, c.G);
-    const AncHead &hh = lay.head(s_lay, q.g);
-    const float *kd = s_kind + q.g * Layout::KIND_F;
+// The decoded box of ONE anchor -- kind row `kd` (of the head's kind k) at cell (q.x, q.y) of frame b -- into r[0 .. code -
+// sincos): box_coder_utils.py:54-77 + anchor_head_template.py:258-269.  The one copy of the decode arithmetic: the dense
+// decode below and the static post-processing (anchor_postproc.hip, selected anchors only) both call it.
+__device__ __forceinline__ void anc_decode_box(const AncDecodeCfg &c, const AncHead &hh, const float *kd, const float *shifts,
+                                               int b, const AncGeom &q, int k, float *r /*[9]*/) {
     const Anchor a = anchor_of_kind(kd, shifts, q.x, q.y, c.W, c.H, c.n_classes);
-    const int k = q.g - hh.kind0, nc = hh.num_class;
-    long long base[3];
+    long long base[3];                                                   // (box and direction maps: rows 1 and 2)
 #pragma unroll
-    for (int m = 0; m < 3; ++m)
+    for (int m = 1; m < 3; ++m)
         base[m] = (long long)b * hh.strides[m][0] + (long long)q.y * hh.strides[m][2] + (long long)q.x * hh.strides[m][3];
-    float *co = lay.logit_row(s_lay, hh, b, n, HW, N);
-    for (int j = 0; j < nc; ++j) co[j] = load_el(hh.map[0], c.dtype, base[0] + (long long)(k * nc + j) * hh.strides[0][1]);
     float t[ANC_MAX_CODE];
 #pragma unroll
     for (int j = 0; j < ANC_MAX_CODE; ++j)
         t[j] = j < c.code ? load_el(hh.map[1], c.dtype, base[1] + (long long)(k * c.code + j) * hh.strides[1][1]) : 0.f;
-    float r[9];
     r[0] = t[0] * a.diag + a.xa;
     r[1] = t[1] * a.diag + a.ya;
     r[2] = t[2] * a.dza + a.za;
@@ -589,6 +574,28 @@ __global__ __launch_bounds__(256) void anc_decode_kernel(Layout lay, AncDecodeCf
         const float dir_rot = v - floorf(__fdiv_rn(v, c.period) + c.dir_limit_offset) * c.period;
         r[6] = (dir_rot + c.dir_offset) + c.period * (float)lab;
     }
+}
+
+// boxes [B][N][code - sincos] and the logits as fp32 where the layout puts them
+template <class Layout>
+__global__ __launch_bounds__(256) void anc_decode_kernel(Layout lay, AncDecodeCfg c, const float *kinds, const float *shifts,
+                                                         float *box_out) {
+    __shared__ float s_kind[ANC_MAX_KINDS * Layout::KIND_F];
+    __shared__ typename Layout::Shared s_lay;
+    const int HW = c.H * c.W, N = HW * c.G;
+    const int b = blockIdx.y;
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    lay.stage(s_lay);
+    stage_kinds(s_kind, kinds, c.G * Layout::KIND_F);
+    if (n >= N) return;
+    const AncGeom q = Layout::geom(n, c.H, c.W, c.G);
+    const AncHead &hh = lay.head(s_lay, q.g);
+    const int k = q.g - hh.kind0, nc = hh.num_class;
+    const long long base0 = (long long)b * hh.strides[0][0] + (long long)q.y * hh.strides[0][2] + (long long)q.x * hh.strides[0][3];
+    float *co = lay.logit_row(s_lay, hh, b, n, HW, N);
+    for (int j = 0; j < nc; ++j) co[j] = load_el(hh.map[0], c.dtype, base0 + (long long)(k * nc + j) * hh.strides[0][1]);
+    float r[9];
+    anc_decode_box(c, hh, s_kind + q.g * Layout::KIND_F, shifts, b, q, k, r);
     const int ow = c.code - c.sincos;
     float *bo = box_out + ((size_t)b * N + n) * ow;
 #pragma unroll

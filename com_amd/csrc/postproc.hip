@@ -23,14 +23,12 @@
 //   output    B blocks: heads concatenated in head order, NMS_POST_MAXSIZE per head, zeros behind count
 // Workgroups never hand data to each other inside a launch: every hand-over is a launch boundary.  The only atomics are
 // integer adds (histograms, candidate slots); the candidates are sorted by their unique keys, so slot order never shows.
-#include "common.h"
-#include "iou3d_geom.h"
+// Every launch but `finish` is the shared core of postproc_common.h (also under anchor_postproc.hip); this file holds the
+// centre heads' key producer (PpArgs::key), their finish kernel and the entry points.
+#include "postproc_common.h"
 
 namespace {
 
-constexpr int PP_THREADS = 256;
-constexpr int PP_CHUNK = 2048;                 // pixels per block of the streaming launches (8 per thread)
-constexpr int PP_BINS = 65536;                 // 16-bit digits
 constexpr int PP_MAPS = 6;                     // hm, center, center_z, dim, rot, vel
 
 struct PpMap {
@@ -49,200 +47,19 @@ struct PpArgs {
     long long thr;                             // a pixel passes SCORE_THRESH iff (long long)bits > thr (-1: every pixel)
     float limit[6];
     float fstride, vx, vy, px, py, nms_thresh;
+    // the key producer of the shared core (postproc_common.h): problem p = (frame, head), element i = c*H*W + y*W + x,
+    // key = bits of sigmoid(hm) (a non-negative float: its bit pattern orders like the score)
+    __device__ __forceinline__ int count(int p) const { return h[p % NH].C * H * W; }
+    __device__ __forceinline__ u32 key(int p, int i) const;
+    __device__ __forceinline__ int out_label(int hd, int c) const { return h[hd].label[c]; }
 };
-// per-problem selection state (find launches -> later launches)
-struct PpSel {
-    int all;                                   // fewer than K pass: take every passing pixel
-    int b1;                                    // high digit of the cut
-    int above;                                 // keys above the cut's bin (pass 1), above T (pass 2)
-    int r;                                     // ties at T still taken
-    long long T;                               // take key > T (+ the first r with key == T)
-    long long pad;
-};
-
 __device__ __forceinline__ float ld_map(const PpMap &m, int b, int c, int y, int x) {
     const long long off = (long long)b * m.s[0] + (long long)c * m.s[1] + (long long)y * m.s[2] + (long long)x * m.s[3];
     return load_el(m.p, m.bf16 ? PCD_BF16 : PCD_F32, off);
 }
-
-// one atomic per distinct bin of the wave (all-equal scores -- fresh weights -- would otherwise serialise on one address)
-__device__ __forceinline__ void wave_hist_add(u32 *hist, bool active, u32 bin) {
-    u64 todo = __ballot(active);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const u32 lb = (u32)__shfl((int)bin, leader, 64);
-        const u64 same = __ballot(active && bin == lb) & todo;
-        if (lane_id() == leader) atomicAdd(hist + lb, (u32)__popcll(same));
-        todo &= ~same;
-    }
-}
-
-__device__ __forceinline__ int problem_chw(const PpArgs &a, int p) { return a.h[p % a.NH].C * a.H * a.W; }
-
-// keys[p][i] = bits of sigmoid(hm); hist1[p][bits >> 16] counts the pixels that pass SCORE_THRESH
-__global__ __launch_bounds__(PP_THREADS) void pp_keys_kernel(PpArgs a, u32 *__restrict__ keys, u32 *__restrict__ hist1) {
-    const int p = blockIdx.y, chw = problem_chw(a, p);
-    const int i0 = blockIdx.x * PP_CHUNK;
-    if (i0 >= chw) return;
-    const PpMap &hm = a.h[p % a.NH].m[0];
-    const int b = p / a.NH, hw = a.H * a.W;
-    u32 *kp = keys + (size_t)p * a.chw_max;
-    u32 *hp = hist1 + (size_t)p * PP_BINS;
-    for (int e = 0; e < PP_CHUNK; e += PP_THREADS) {
-        const int i = i0 + e + threadIdx.x;
-        const bool in = i < chw;
-        u32 key = 0;
-        if (in) {
-            const int c = i / hw, rem = i - c * hw, y = rem / a.W, x = rem - y * a.W;
-            key = __float_as_uint(sigmoid_f32(ld_map(hm, b, c, y, x)));
-            kp[i] = key;
-        }
-        wave_hist_add(hp, in && (long long)key > a.thr, key >> 16);
-    }
-}
-
-// The bin holding the `need`-th largest counted key: thread t owns bins of group 255 - t (thread 0 the highest), an exclusive
-// scan over the threads gives the count above each group, the one thread whose group crosses `need` walks its bins.
-__device__ void find_cut(const u32 *__restrict__ hist, int need, int *lds, int &bin_out, int &above_out) {
-    const int g = PP_THREADS - 1 - (int)threadIdx.x, per = PP_BINS / PP_THREADS;
-    const u32 *hg = hist + (size_t)g * per;
-    int sum = 0;
-    for (int j = 0; j < per; ++j) sum += (int)hg[j];
-    int total;
-    const int above = block_exclusive_scan(sum, lds, total);
-    if (above < need && above + sum >= need) {
-        int acc = above;
-        for (int j = per - 1; j >= 0; --j) {
-            const int c = (int)hg[j];
-            if (acc + c >= need) {
-                lds[4] = g * per + j;
-                lds[5] = acc;
-                break;
-            }
-            acc += c;
-        }
-    }
-    __syncthreads();
-    bin_out = lds[4];
-    above_out = lds[5];
-}
-
-__global__ __launch_bounds__(PP_THREADS) void pp_find1_kernel(PpArgs a, const u32 *__restrict__ hist1, PpSel *__restrict__ sel) {
-    __shared__ int lds[8];
-    const int p = blockIdx.x;
-    const u32 *hp = hist1 + (size_t)p * PP_BINS;
-    int sum = 0;
-    for (int j = threadIdx.x; j < PP_BINS; j += PP_THREADS) sum += (int)hp[j];
-    int total;
-    block_exclusive_scan(sum, lds, total);
-    if (total <= a.K) {                                  // every passing pixel is selected
-        if (threadIdx.x == 0) {
-            PpSel s = {};
-            s.all = 1;
-            s.T = a.thr;
-            s.above = total;
-            sel[p] = s;
-        }
-        return;
-    }
-    int bin, above;
-    find_cut(hp, a.K, lds, bin, above);
-    if (threadIdx.x == 0) {
-        PpSel s = {};
-        s.all = 0;
-        s.b1 = bin;
-        s.above = above;
-        sel[p] = s;
-    }
-}
-
-// low 16 bits of the passing keys inside the cut's bin
-__global__ __launch_bounds__(PP_THREADS) void pp_hist2_kernel(PpArgs a, const u32 *__restrict__ keys, const PpSel *__restrict__ sel,
-                                                              u32 *__restrict__ hist2) {
-    const int p = blockIdx.y, chw = problem_chw(a, p);
-    const int i0 = blockIdx.x * PP_CHUNK;
-    const PpSel s = sel[p];
-    if (i0 >= chw || s.all) return;
-    const u32 *kp = keys + (size_t)p * a.chw_max;
-    u32 *hp = hist2 + (size_t)p * PP_BINS;
-    for (int e = 0; e < PP_CHUNK; e += PP_THREADS) {
-        const int i = i0 + e + threadIdx.x;
-        const u32 key = i < chw ? kp[i] : 0u;
-        wave_hist_add(hp, i < chw && (long long)key > a.thr && (int)(key >> 16) == s.b1, key & 0xffffu);
-    }
-}
-
-__global__ __launch_bounds__(PP_THREADS) void pp_find2_kernel(PpArgs a, const u32 *__restrict__ hist2, PpSel *__restrict__ sel) {
-    __shared__ int lds[8];
-    const int p = blockIdx.x;
-    const PpSel s = sel[p];
-    if (s.all) return;
-    int bin, above;
-    find_cut(hist2 + (size_t)p * PP_BINS, a.K - s.above, lds, bin, above);
-    if (threadIdx.x == 0) {
-        PpSel o = s;
-        o.T = ((long long)s.b1 << 16) | bin;
-        o.above = s.above + above;                       // keys > T
-        o.r = a.K - o.above;                             // >= 1 ties at T taken
-        sel[p] = o;
-    }
-}
-
-// pixels with key == T per chunk
-__global__ __launch_bounds__(PP_THREADS) void pp_ties_kernel(PpArgs a, const u32 *__restrict__ keys, const PpSel *__restrict__ sel,
-                                                             int *__restrict__ ties) {
-    __shared__ int lds[4];
-    const int p = blockIdx.y, chw = problem_chw(a, p);
-    const int i0 = blockIdx.x * PP_CHUNK;
-    const PpSel s = sel[p];
-    if (i0 >= chw || s.all) return;
-    const u32 *kp = keys + (size_t)p * a.chw_max;
-    int n = 0;
-    for (int e = 0; e < PP_CHUNK; e += PP_THREADS) {
-        const int i = i0 + e + threadIdx.x;
-        n += (i < chw && (long long)kp[i] == s.T) ? 1 : 0;
-    }
-    int total;
-    block_exclusive_scan(n, lds, total);
-    if (threadIdx.x == 0) ties[(size_t)p * a.nchunks + blockIdx.x] = total;
-}
-
-// candidates: keys > T, and the ties at T whose rank in index order is below r
-__global__ __launch_bounds__(PP_THREADS) void pp_gather_kernel(PpArgs a, const u32 *__restrict__ keys, const PpSel *__restrict__ sel,
-                                                               const int *__restrict__ ties, u64 *__restrict__ cand,
-                                                               u32 *__restrict__ cand_n) {
-    __shared__ int lds[4];
-    __shared__ int wbase[PP_THREADS / 64];
-    const int p = blockIdx.y, chw = problem_chw(a, p);
-    const int i0 = blockIdx.x * PP_CHUNK;
-    const PpSel s = sel[p];
-    if (i0 >= chw) return;
-    int base = 0;                                        // ties at T in the chunks before this one
-    if (!s.all) {
-        int v = 0;
-        for (int c = threadIdx.x; c < (int)blockIdx.x; c += PP_THREADS) v += ties[(size_t)p * a.nchunks + c];
-        block_exclusive_scan(v, lds, base);
-    }
-    const u32 *kp = keys + (size_t)p * a.chw_max;
-    u64 *cp = cand + (size_t)p * a.K;
-    for (int e = 0; e < PP_CHUNK; e += PP_THREADS) {
-        const int i = i0 + e + threadIdx.x;
-        const long long key = i < chw ? (long long)kp[i] : -2;
-        const bool tie = !s.all && key == s.T;
-        int nt;
-        const int rank = base + block_exclusive_scan(tie ? 1 : 0, lds, nt);
-        base += nt;
-        const bool take = key > s.T || (tie && rank < s.r);
-        int wn;
-        const int wr = wave_rank(take, wn);
-        if (lane_id() == 0 && wn) wbase[threadIdx.x >> 6] = (int)atomicAdd(cand_n + p, (u32)wn);
-        __syncthreads();
-        if (take) {
-            const int slot = wbase[threadIdx.x >> 6] + wr;
-            if (slot < a.K) cp[slot] = ((u64)(u32)key << 32) | (u64)(0xffffffffu - (u32)i);
-        }
-        __syncthreads();
-    }
+__device__ __forceinline__ u32 PpArgs::key(int p, int i) const {
+    const int hw = H * W, c = i / hw, rem = i - c * hw, y = rem / W, x = rem - y * W;
+    return __float_as_uint(sigmoid_f32(ld_map(h[p % NH].m[0], p / NH, c, y, x)));
 }
 
 // sort (score desc, index asc), decode (centernet_utils.py:217-257), POST_CENTER_LIMIT_RANGE, compaction in score order
@@ -251,25 +68,8 @@ __global__ __launch_bounds__(PP_THREADS) void pp_finish_kernel(PpArgs a, const u
                                                                int *__restrict__ scls, int *__restrict__ scount) {
     extern __shared__ u64 srt[];                         // [KP2]
     __shared__ int lds[4];
-    const int p = blockIdx.x, N = a.KP2;
-    const int n = min((int)cand_n[p], a.K);
-    const u64 *cp = cand + (size_t)p * a.K;
-    for (int i = threadIdx.x; i < N; i += PP_THREADS) srt[i] = i < n ? cp[i] : 0ull;     // (0 sorts behind every key)
-    __syncthreads();
-    for (int k = 2; k <= N; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < N; i += PP_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const u64 x = srt[i], y = srt[ixj];
-                    if (((i & k) == 0) ? (x < y) : (x > y)) {
-                        srt[i] = y;
-                        srt[ixj] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
+    const int p = blockIdx.x;
+    const int n = sel_load_sort(cand, cand_n, p, a.K, a.KP2, srt);
     const PpHead &hd = a.h[p % a.NH];
     const int b = p / a.NH, hw = a.H * a.W, D = a.D;
     float *bp = sbox + (size_t)p * a.K * D;
@@ -317,95 +117,6 @@ __global__ __launch_bounds__(PP_THREADS) void pp_finish_kernel(PpArgs a, const u
     }
     if (threadIdx.x == 0) scount[p] = base;
 }
-
-// suppression mask of each problem over its first n = min(count, NMS_PRE_MAXSIZE) boxes (nms_mask_kernel of iou3d.hip with a
-// device-side n and box rows of D floats)
-template <bool NORMAL>
-__global__ __launch_bounds__(64) void pp_nms_mask_kernel(PpArgs a, const float *__restrict__ sbox, const int *__restrict__ scount,
-                                                         u64 *__restrict__ mask) {
-    const int col = blockIdx.x, row = blockIdx.y, p = blockIdx.z;
-    const int n = min(scount[p], a.pre);
-    if (col < row || row * 64 >= n || col * 64 >= n) return;
-    __shared__ float cb[64 * 7];
-    const int lane = threadIdx.x, D = a.D;
-    const float *boxes = sbox + (size_t)p * a.K * D;
-    const int ncol = min(n - col * 64, 64), nrow = min(n - row * 64, 64);
-    for (int e = lane; e < ncol * 7; e += 64) cb[e] = boxes[(size_t)(col * 64 + e / 7) * D + e % 7];
-    __syncthreads();
-    if (lane >= nrow) return;
-    const int me = row * 64 + lane;
-    float bx[7];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) bx[j] = boxes[(size_t)me * D + j];
-    u64 t = 0;
-    for (int i = (row == col) ? lane + 1 : 0; i < ncol; ++i) {
-        const float v = NORMAL ? iou_normal_dev(bx, cb + i * 7) : iou_bev_dev(bx, cb + i * 7);
-        if (v > a.nms_thresh) t |= 1ull << i;
-    }
-    mask[((size_t)p * a.K + me) * a.cbk + col] = t;
-}
-
-// greedy keep list per problem (nms_reduce_kernel of iou3d.hip, one wave per problem)
-__global__ __launch_bounds__(64) void pp_nms_reduce_kernel(PpArgs a, const u64 *__restrict__ mask, const int *__restrict__ scount,
-                                                           int *__restrict__ keep, int *__restrict__ nkeep) {
-    __shared__ u64 remv[PCD_POSTPROC_MAX_K / 64];
-    const int p = blockIdx.x, lane = threadIdx.x, cbk = a.cbk;
-    const int n = min(scount[p], a.pre);
-    const u64 *mp = mask + (size_t)p * a.K * cbk;
-    int *kp = keep + (size_t)p * a.K;
-    for (int w = lane; w < cbk; w += 64) remv[w] = 0;
-    __syncthreads();
-    int kept = 0;
-    for (int i = 0; i < n; ++i) {
-        const int blk = i >> 6, bit = i & 63;
-        const u64 word = remv[blk];
-        if (!((word >> bit) & 1ull)) {
-            if (lane == 0) kp[kept] = i;
-            ++kept;
-            const int wlim = (n + 63) >> 6;
-            for (int w = blk + lane; w < wlim; w += 64) remv[w] |= mp[(size_t)i * cbk + w];
-            __syncthreads();
-        }
-    }
-    if (lane == 0) nkeep[p] = kept;
-}
-
-// per frame: the heads' kept boxes (first NMS_POST_MAXSIZE each) in head order, zeros behind
-__global__ __launch_bounds__(PP_THREADS) void pp_output_kernel(PpArgs a, const float *__restrict__ sbox, const float *__restrict__ sscore,
-                                                               const int *__restrict__ scls, const int *__restrict__ keep,
-                                                               const int *__restrict__ nkeep, float *__restrict__ boxes,
-                                                               float *__restrict__ scores, long long *__restrict__ labels,
-                                                               int32_t *__restrict__ count) {
-    const int b = blockIdx.x, D = a.D, M = a.NH * a.post;
-    float *ob = boxes + (size_t)b * M * D;
-    float *os = scores + (size_t)b * M;
-    long long *ol = labels + (size_t)b * M;
-    int off = 0;
-    for (int h = 0; h < a.NH; ++h) {
-        const int p = b * a.NH + h;
-        const int k = min(nkeep[p], a.post);
-        const int *kp = keep + (size_t)p * a.K;
-        for (int j = threadIdx.x; j < k; j += PP_THREADS) {
-            const int src = kp[j];
-            const size_t q = (size_t)p * a.K + src;
-            for (int d = 0; d < D; ++d) ob[(size_t)(off + j) * D + d] = sbox[q * D + d];
-            os[off + j] = sscore[q];
-            ol[off + j] = a.h[h].label[scls[q]];
-        }
-        off += k;
-    }
-    for (int j = off + threadIdx.x; j < M; j += PP_THREADS) {
-        for (int d = 0; d < D; ++d) ob[(size_t)j * D + d] = 0.f;
-        os[j] = 0.f;
-        ol[j] = 0;
-    }
-    if (threadIdx.x == 0) count[b] = off;
-}
-
-struct PpLayout {
-    size_t zero_bytes, total;
-    size_t o_hist1, o_hist2, o_cand_n, o_keys, o_sel, o_ties, o_cand, o_sbox, o_sscore, o_scls, o_scount, o_mask, o_keep, o_nkeep;
-};
 
 // validation + kernel arguments; 0 when the configuration is refused
 int pp_setup(const PcdPostprocHead *heads, const PcdPostprocConfig *cfg, PpArgs &a) {
@@ -469,36 +180,12 @@ int pp_setup(const PcdPostprocHead *heads, const PcdPostprocConfig *cfg, PpArgs 
     return PCD_OK;
 }
 
-PpLayout pp_layout(const PpArgs &a) {
-    PpLayout l{};
-    const size_t P = (size_t)a.B * a.NH, K = a.K;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += pcd_align_up(bytes, 256); return o; };
-    l.o_hist1 = take(P * PP_BINS * 4);
-    l.o_hist2 = take(P * PP_BINS * 4);
-    l.o_cand_n = take(P * 4);
-    l.zero_bytes = off;
-    l.o_keys = take(P * (size_t)a.chw_max * 4);
-    l.o_sel = take(P * sizeof(PpSel));
-    l.o_ties = take(P * (size_t)a.nchunks * 4);
-    l.o_cand = take(P * K * 8);
-    l.o_sbox = take(P * K * a.D * 4);
-    l.o_sscore = take(P * K * 4);
-    l.o_scls = take(P * K * 4);
-    l.o_scount = take(P * 4);
-    l.o_mask = take(P * K * a.cbk * 8);
-    l.o_keep = take(P * K * 4);
-    l.o_nkeep = take(P * 4);
-    l.total = off;
-    return l;
-}
-
 }  // namespace
 
 extern "C" size_t pcd_centerhead_postproc_workspace_bytes(const PcdPostprocHead *heads, const PcdPostprocConfig *cfg) {
     PpArgs a;
     if (pp_setup(heads, cfg, a) != PCD_OK) return 0;
-    return pp_layout(a).total;
+    return pp_layout((size_t)a.B * a.NH, a.K, a.D, a.chw_max, a.nchunks, a.cbk).total;
 }
 
 extern "C" int pcd_centerhead_postproc(const PcdPostprocHead *heads, const PcdPostprocConfig *cfg, float *boxes, float *scores,
@@ -509,38 +196,14 @@ extern "C" int pcd_centerhead_postproc(const PcdPostprocHead *heads, const PcdPo
     const int rc = pp_setup(heads, cfg, a);
     if (rc != PCD_OK) return rc;
     if (!boxes || !scores || !labels || !count) return PCD_ERR_INVALID_ARG;
-    const PpLayout l = pp_layout(a);
-    if (!workspace || workspace_bytes < l.total || ((uintptr_t)workspace & 255)) return PCD_ERR_WORKSPACE;
-    char *ws = (char *)workspace;
-    u32 *hist1 = (u32 *)(ws + l.o_hist1), *hist2 = (u32 *)(ws + l.o_hist2), *cand_n = (u32 *)(ws + l.o_cand_n);
-    u32 *keys = (u32 *)(ws + l.o_keys);
-    PpSel *sel = (PpSel *)(ws + l.o_sel);
-    int *ties = (int *)(ws + l.o_ties);
-    u64 *cand = (u64 *)(ws + l.o_cand);
-    float *sbox = (float *)(ws + l.o_sbox), *sscore = (float *)(ws + l.o_sscore);
-    int *scls = (int *)(ws + l.o_scls), *scount = (int *)(ws + l.o_scount);
-    u64 *mask = (u64 *)(ws + l.o_mask);
-    int *keep = (int *)(ws + l.o_keep), *nkeep = (int *)(ws + l.o_nkeep);
-    hipStream_t st = (hipStream_t)stream;
     const unsigned P = (unsigned)(a.B * a.NH);
-    const dim3 stream_grid((unsigned)a.nchunks, P);
-    pcd_fill(ws, 0, l.zero_bytes, st);
-    pp_keys_kernel<<<stream_grid, PP_THREADS, 0, st>>>(a, keys, hist1);
-    pp_find1_kernel<<<P, PP_THREADS, 0, st>>>(a, hist1, sel);
-    pp_hist2_kernel<<<stream_grid, PP_THREADS, 0, st>>>(a, keys, sel, hist2);
-    pp_find2_kernel<<<P, PP_THREADS, 0, st>>>(a, hist2, sel);
-    pp_ties_kernel<<<stream_grid, PP_THREADS, 0, st>>>(a, keys, sel, ties);
-    pp_gather_kernel<<<stream_grid, PP_THREADS, 0, st>>>(a, keys, sel, ties, cand, cand_n);
-    pp_finish_kernel<<<P, PP_THREADS, (size_t)a.KP2 * sizeof(u64), st>>>(a, cand, cand_n, sbox, sscore, scls, scount);
-    const dim3 tiles((unsigned)a.cbk, (unsigned)a.cbk, P);
-    if (a.cbk > 0) {
-        if (cfg->nms_normal)
-            pp_nms_mask_kernel<true><<<tiles, 64, 0, st>>>(a, sbox, scount, mask);
-        else
-            pp_nms_mask_kernel<false><<<tiles, 64, 0, st>>>(a, sbox, scount, mask);
-    }
-    pp_nms_reduce_kernel<<<P, 64, 0, st>>>(a, mask, scount, keep, nkeep);
-    pp_output_kernel<<<(unsigned)a.B, PP_THREADS, 0, st>>>(a, sbox, sscore, scls, keep, nkeep, boxes, scores, labels, count);
+    const PpLayout l = pp_layout(P, a.K, a.D, a.chw_max, a.nchunks, a.cbk);
+    if (!workspace || workspace_bytes < l.total || ((uintptr_t)workspace & 255)) return PCD_ERR_WORKSPACE;
+    const PpBuffers w = pp_buffers(workspace, l);
+    hipStream_t st = (hipStream_t)stream;
+    pp_launch_select(a, P, workspace, l, w, st);
+    pp_finish_kernel<<<P, PP_THREADS, (size_t)a.KP2 * sizeof(u64), st>>>(a, w.cand, w.cand_n, w.sbox, w.sscore, w.scls, w.scount);
+    pp_launch_nms_output(a, P, (unsigned)a.B, cfg->nms_normal != 0, w, boxes, scores, labels, count, st);
     PCD_RETURN_IF_LAUNCH_FAILED();
     return PCD_OK;
 }

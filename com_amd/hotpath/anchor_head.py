@@ -298,7 +298,8 @@ def decode_boxes(tab, cls_preds, box_preds, dir_cls_preds=None):
 def post_processing(batch_dict, post_process_cfg, num_class=None):
     """The single-head, class-agnostic-NMS branch of Detector3DTemplate.post_processing (detector3d_template.py:178-290
     with model_nms_utils.py:6-25) over com_amd.iou3d_nms: the reference's list of pred_boxes / pred_scores / pred_labels
-    dicts.  (Eager, with the reference's read-backs; a static, capturable form is not part of this module.)"""
+    dicts.  (Eager, with the reference's read-backs; the static, capturable form is
+    com_amd.postprocess.anchor_predictions_static -- AnchorHeadSingle.generate_predicted_boxes_static.)"""
     from .center_head import class_agnostic_nms
     nms_cfg = _get(post_process_cfg, 'NMS_CONFIG')
     if _get(nms_cfg, 'MULTI_CLASSES_NMS', False):
@@ -402,9 +403,23 @@ class AnchorHeadSingle(nn.Module):
         assert cls_preds.shape[0] == batch_size
         return decode_boxes(self.tables(cls_preds.device), cls_preds, box_preds, dir_cls_preds)
 
+    def generate_predicted_boxes_static(self, cls_preds, box_preds, dir_cls_preds, post_process_cfg):
+        """generate_predicted_boxes + the detector's post_processing as fixed-shape device tensors, without a host read-back
+        and without the [B, N, 7] / [B, N, num_class] tensors (com_amd.postprocess.anchor_predictions_static):
+        {'boxes' [B, M, 7], 'scores' [B, M], 'labels' [B, M], 'count' [B]}; postprocess.to_pred_dicts gives the list.
+        post_process_cfg: the DETECTOR's POST_PROCESSING block (an anchor head has none of its own)."""
+        from .. import postprocess
+        if post_process_cfg is None:
+            raise L.PcdError(f"{type(self).__name__}: static_predictions needs data_dict['post_process_cfg'] (the detector's "
+                             "POST_PROCESSING block)")
+        with torch.no_grad():
+            return postprocess.anchor_predictions_static(self, cls_preds, box_preds, dir_cls_preds, post_process_cfg)
+
     def forward(self, data_dict):
         """anchor_head_single.py:41-76.  The three 1 x 1 convs run as ONE product over the channels-last map: the
-        [B, H, W, C] prediction maps of the reference are channel blocks of its result (views, no permute copies)."""
+        [B, H, W, C] prediction maps of the reference are channel blocks of its result (views, no permute copies).
+        In eval mode `data_dict.pop('static_predictions', False)` asks for the static post-processing instead of
+        generate_predicted_boxes: `final_box_tensors` from data_dict['post_process_cfg'], no batch_box_preds."""
         x = data_dict['spatial_features_2d']
         convs = [self.conv_cls, self.conv_box] + ([self.conv_dir_cls] if self.use_dir else [])
         weight = torch.cat([c.weight.flatten(1) for c in convs], dim=0)
@@ -417,6 +432,11 @@ class AnchorHeadSingle(nn.Module):
             self.forward_ret_dict['dir_cls_preds'] = dir_cls_preds
         if self.training:
             self.forward_ret_dict.update(self._targets(data_dict))
+        # (popped in every mode, so that the key never travels on; honoured in eval mode only)
+        if data_dict.pop('static_predictions', False) and not self.training:
+            data_dict['final_box_tensors'] = self.generate_predicted_boxes_static(
+                cls_preds, box_preds, dir_cls_preds, data_dict.get('post_process_cfg', None))
+            return data_dict
         if not self.training or self.predict_boxes_when_training:
             with torch.no_grad():
                 batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(

@@ -9,7 +9,23 @@ workspace -- so it can sit inside a captured inference graph (com_amd.infer.Capt
 `static` holds boxes f32 [B, M, 7 | 9], scores f32 [B, M], labels int64 [B, M] (class_id_mapping_each_head[h][c] + 1) and
 count int32 [B]; M = number of heads x NMS_POST_MAXSIZE, rows behind count are zero, each frame's rows are its heads' kept
 boxes in head order, each head's in score order.  Selection order: score descending, then flat index c*H*W + y*W + x
-ascending (torch.topk leaves ties unordered; with distinct scores both agree)."""
+ascending (torch.topk leaves ties unordered; with distinct scores both agree).
+
+The anchor-head counterpart (AnchorHeadSingle and its curriculum forms; com_amd/csrc/anchor_postproc.hip) replaces
+generate_predicted_boxes + Detector3DTemplate.post_processing (anchor_head_template.py:229-276, detector3d_template.py:178-290,
+model_nms_utils.py:6-25) the same way, one selection problem per frame:
+
+    static = anchor_predictions_static(head, cls_preds, box_preds, dir_cls_preds, post_process_cfg)
+
+with the same dict layout (M = NMS_POST_MAXSIZE, boxes [B, M, 7]), so `to_pred_dicts` serves both.  Its rules, as a total
+order: score_c = fp32 sigmoid of the class logit (bf16 widened first); an anchor's score is the maximum over its num_class
+scores and its label the lowest class index that attains it, + 1; with SCORE_THRESH an anchor passes iff score >=
+SCORE_THRESH (INCLUSIVE, model_nms_utils.py:9 -- the centre path above is exclusive), without it every anchor passes; a NaN
+score never passes (the one deliberate difference from torch.topk, which ranks NaN first); the first
+min(NMS_PRE_MAXSIZE, passing) anchors are taken by score descending, then anchor index n = (y * W + x) * A + kind ascending;
+only those are decoded (the arithmetic of pcd_anchor_decode: one device function); nms_gpu / nms_normal_gpu runs over them in
+that order on columns 0:7 and the first NMS_POST_MAXSIZE survivors are written in keep order.  No [B, N, 7] and no
+[B, N, num_class] tensor exists on this path."""
 import ctypes
 
 import torch
@@ -116,6 +132,93 @@ def decode_predictions_static(pred_dicts, head):
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     L.check(lib.pcd_centerhead_postproc(hp, cp, L.ptr(out["boxes"]), L.ptr(out["scores"]), L.ptr(out["labels"]),
                                         L.ptr(out["count"]), L.ptr(ws), nbytes, L.stream_ptr()), "pcd_centerhead_postproc")
+    return out
+
+
+class PcdAnchorPostprocConfig(ctypes.Structure):
+    """include/pcd_ops.h: struct PcdAnchorPostprocConfig (POST_PROCESSING of an anchor-head detector + the head's
+    shapes); the mirror lives beside its one user."""
+    _fields_ = [("batch", ctypes.c_int), ("height", ctypes.c_int), ("width", ctypes.c_int), ("n_kinds", ctypes.c_int),
+                ("n_classes", ctypes.c_int), ("num_class", ctypes.c_int), ("num_dir_bins", ctypes.c_int),
+                ("nms_pre", ctypes.c_int), ("nms_post", ctypes.c_int), ("nms_normal", ctypes.c_int),
+                ("use_score_thresh", ctypes.c_int), ("score_thresh", ctypes.c_float), ("nms_thresh", ctypes.c_float),
+                ("dir_offset", ctypes.c_float), ("dir_limit_offset", ctypes.c_float)]
+
+
+def anchor_static_settings(post_process_cfg):
+    """The POST_PROCESSING block of an anchor-head detector as pcd_anchor_postproc takes it; PcdError naming the key for what
+    the static path refuses (MULTI_CLASSES_NMS, OUTPUT_RAW_SCORE, other NMS types, NMS_PRE_MAXSIZE above the LDS cap)."""
+    pp = post_process_cfg
+    if pp is None:
+        raise L.PcdError("static anchor post-processing: no POST_PROCESSING block")
+    nms = _get(pp, 'NMS_CONFIG')
+    if _get(nms, 'MULTI_CLASSES_NMS', False):
+        raise L.PcdError("static anchor post-processing: MULTI_CLASSES_NMS = True is not supported (class-agnostic NMS only)")
+    if _get(pp, 'OUTPUT_RAW_SCORE', False):
+        raise L.PcdError("static anchor post-processing: OUTPUT_RAW_SCORE = True is not supported")
+    kind = _get(nms, 'NMS_TYPE')
+    if kind not in NMS_TYPES:
+        raise L.PcdError(f"static anchor post-processing: NMS_TYPE {kind!r} (supported: {sorted(NMS_TYPES)})")
+    s = dict(nms_pre=int(_get(nms, 'NMS_PRE_MAXSIZE')), nms_post=int(_get(nms, 'NMS_POST_MAXSIZE')),
+             nms_thresh=float(_get(nms, 'NMS_THRESH')), nms_normal=NMS_TYPES[kind], score_thresh=_get(pp, 'SCORE_THRESH', None))
+    if s["nms_pre"] > L.POSTPROC_MAX_K:
+        raise L.PcdError(f"static anchor post-processing: NMS_PRE_MAXSIZE = {s['nms_pre']} above the cap {L.POSTPROC_MAX_K} "
+                         "(the per-frame sort runs in LDS)")
+    for key, v in (("NMS_PRE_MAXSIZE", s["nms_pre"]), ("NMS_POST_MAXSIZE", s["nms_post"])):
+        if v < 1:
+            raise L.PcdError(f"static anchor post-processing: {key} = {v}")
+    return s
+
+
+def anchor_postproc_config(s, tab, batch):
+    """PcdAnchorPostprocConfig of settings `s` (anchor_static_settings) for the anchor tables `tab` of a head"""
+    cfg = PcdAnchorPostprocConfig()
+    cfg.batch, cfg.height, cfg.width, cfg.n_kinds, cfg.n_classes = int(batch), tab.H, tab.W, tab.A, tab.C
+    cfg.num_class, cfg.num_dir_bins = tab.num_class, tab.num_dir_bins
+    cfg.nms_pre, cfg.nms_post, cfg.nms_normal = s["nms_pre"], s["nms_post"], s["nms_normal"]
+    cfg.use_score_thresh = int(s["score_thresh"] is not None)
+    cfg.score_thresh = float(s["score_thresh"]) if s["score_thresh"] is not None else 0.0
+    cfg.nms_thresh = s["nms_thresh"]
+    cfg.dir_offset, cfg.dir_limit_offset = tab.dir_offset, tab.dir_limit_offset
+    return cfg
+
+
+def anchor_predictions_static(head, cls_preds, box_preds, dir_cls_preds, post_process_cfg):
+    """head: an AnchorHeadSingle (its anchor tables); cls_preds / box_preds / dir_cls_preds: the [B, H, W, C] prediction maps
+    of its forward (device tensors, f32 or bf16, any strides -- the channel blocks of the fused tensor are fine;
+    dir_cls_preds None without a direction classifier); post_process_cfg: the detector's POST_PROCESSING block.  Returns
+    {'boxes' [B, M, 7], 'scores' [B, M], 'labels' [B, M], 'count' [B]} with M = NMS_POST_MAXSIZE (module docstring)."""
+    from .hotpath.anchor_head import _strides3
+    s = anchor_static_settings(post_process_cfg)
+    maps = [cls_preds, box_preds, dir_cls_preds]
+    if any(m is not None and not (torch.is_tensor(m) and m.is_cuda) for m in maps) or cls_preds is None or box_preds is None:
+        raise L.PcdError("static anchor post-processing needs HIP device tensors (there is no CPU fallback)")
+    if cls_preds.dtype not in (torch.float32, torch.bfloat16):
+        raise L.PcdError(f"static anchor post-processing: prediction maps of dtype {cls_preds.dtype} (f32 / bf16)")
+    if any(m is not None and (m.dtype != cls_preds.dtype or m.dim() != 4 or m.shape[:3] != cls_preds.shape[:3]) for m in maps):
+        raise L.PcdError("static anchor post-processing: the three prediction maps must share dtype and [B, H, W]")
+    tab = head.tables(cls_preds.device)
+    if (cls_preds.shape[1], cls_preds.shape[2]) != (tab.H, tab.W) or cls_preds.shape[3] != tab.A * tab.num_class \
+            or box_preds.shape[3] != tab.A * 7 or (dir_cls_preds is not None and dir_cls_preds.shape[3] != tab.A * tab.num_dir_bins):
+        raise L.PcdError(f"static anchor post-processing: prediction maps {tuple(cls_preds.shape)} / {tuple(box_preds.shape)} "
+                         f"do not match the {tab.H} x {tab.W} x {tab.A} anchors")
+    B = int(cls_preds.shape[0])
+    cfg = anchor_postproc_config(s, tab, B)
+    lib = L.lib()
+    cp = ctypes.cast(ctypes.pointer(cfg), ctypes.c_void_p)
+    nbytes = int(lib.pcd_anchor_postproc_workspace_bytes(cp))
+    if nbytes == 0:
+        raise L.PcdError("static anchor post-processing: configuration refused by pcd_anchor_postproc (include/pcd_ops.h)")
+    dev, M = cls_preds.device, s["nms_post"]
+    out = {"boxes": torch.empty((B, M, 7), dtype=torch.float32, device=dev),
+           "scores": torch.empty((B, M), dtype=torch.float32, device=dev),
+           "labels": torch.empty((B, M), dtype=torch.int64, device=dev),
+           "count": torch.empty((B,), dtype=torch.int32, device=dev)}
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    L.check(lib.pcd_anchor_postproc(L.ptr(cls_preds), L.ptr(box_preds), L.ptr(dir_cls_preds), L.dtype_code(cls_preds),
+                                    _strides3(maps), L.ptr(tab.kinds), L.ptr(tab.shifts), cp, L.ptr(out["boxes"]),
+                                    L.ptr(out["scores"]), L.ptr(out["labels"]), L.ptr(out["count"]), L.ptr(ws), nbytes,
+                                    L.stream_ptr()), "pcd_anchor_postproc")
     return out
 
 
