@@ -72,11 +72,11 @@ class SparseBasicBlock(spconv.SparseModule):
 
 
 class _RulebookPrefetcher:
-    def __init__(self, units, x0, side):
+    def __init__(self, units, x0, side, hook=None, hook_at=None):
         self.units, self.t, self.side, self.next = units, x0, side, 0
         self.unit0_stream = None       # (the stream unit 0 was built on: _BackboneBase._prefetch_rulebooks)
-        self.after_units = x0.indice_dict.pop("__after_units__", None)
-        self.hook_at = x0.indice_dict.pop("__after_units_at__", None)
+        self.after_units = hook
+        self.hook_at = hook_at if hook is not None else None
 
     def advance(self, stream=None):
         """Build the next unit on `stream` (default: the prefetcher's own) and record one event its consumers wait on.
@@ -90,10 +90,7 @@ class _RulebookPrefetcher:
             t = self.t
             built = []
             for conv in unit:
-                if conv.subm:
-                    t.indice_dict["__subm_hint__"] = self._subm_hint(conv, unit, t)
-                rb, out_idx, out_shape = conv._rulebook(t)
-                t.indice_dict.pop("__subm_hint__", None)
+                rb, out_idx, out_shape = conv._rulebook(t, self._subm_hint(conv, unit, t) if conv.subm else None)
                 if rb.ready_event is None:
                     built.append(rb)
                     # the window kernel's tile plan too (ops.subm_window_plan caches it on the rulebook), here on the rulebook
@@ -102,7 +99,7 @@ class _RulebookPrefetcher:
                         ops.subm_window_plan(rb, conv.out_channels, conv.out_channels)
                 if not conv.subm:
                     t = SparseConvTensor(t.features, out_idx, out_shape, t.batch_size, indice_dict=t.indice_dict,
-                                         num_rows=rb.n_out_dev)
+                                         num_rows=rb.n_out_dev, chain=t.chain)
             self.t = t
             if built:
                 ev = torch.cuda.Event()
@@ -169,8 +166,8 @@ class _BackboneBase(nn.Module):
         rank = batch_dict.get('voxel_rank', None)
         if rank is not None and rank.indices is x.indices and list(rank.shape) == list(x.spatial_shape):
             # key-ordered voxel rows: the voxeliser's bitmap ranks ARE the row ids -> level-1 SubM without a hash table
-            x.indice_dict[("__rank__", x.indices.data_ptr())] = rank
-            x.indice_dict["__row_order__"] = rank.order      # the strided builds number their rows the same way
+            x.chain.add_rank(rank)
+            x.chain.row_order = rank.order      # the strided builds number their rows the same way
         return x
 
     def _bump_bn_counters(self):
@@ -198,7 +195,7 @@ class _BackboneBase(nn.Module):
     prefetch_depth = 2
     _packed_ahead = None       # the `weight._version`s pack_after_update() packed, until the next forward takes its packs
 
-    def _prefetch_rulebooks(self, x0):
+    def _prefetch_rulebooks(self, x0, hook=None, hook_at=None):
         """All 9 rulebooks depend only on the voxel coordinates, not on features: they are built on a second HIP
         stream, one UNIT (a strided conv's rulebook + the SubM rulebook of the level it opens) ahead of the
         feature kernels, so the latency-bound, LDS-free hash / bitmap kernels run beside the gather-GEMMs.  The
@@ -212,8 +209,7 @@ class _BackboneBase(nn.Module):
         cur = torch.cuda.current_stream()
         dev = x0.features.device
         side = Fsp.side_stream(dev, "rulebook")
-        pf = _RulebookPrefetcher(self._rb_units, x0, side)
-        x0.indice_dict["__prefetcher__"] = pf
+        pf = x0.chain.prefetcher = _RulebookPrefetcher(self._rb_units, x0, side, hook, hook_at)
         depth = max(1, int(self.prefetch_depth))
         side.wait_stream(cur)
         # The level-1 SubM rulebook (unit 0: all the first conv waits for) on a short branch of its own; the other units do
@@ -290,15 +286,12 @@ class _BackboneBase(nn.Module):
         hook_at = batch_dict.pop('after_rulebooks_at', self.after_rulebooks_at)
         if hook is None:
             hook, hook_at = self.after_rulebooks, self.after_rulebooks_at
-        if hook is not None:
-            x0.indice_dict["__after_units__"] = hook
-            x0.indice_dict["__after_units_at__"] = hook_at
-        self._prefetch_rulebooks(x0)
+        self._prefetch_rulebooks(x0, hook, hook_at)
         x = self.conv_input(x0)
         ops.stamp("conv_input")
         x_conv1 = self.conv1(x)
         ops.stamp("conv1")
-        pf_ = x0.indice_dict.get("__prefetcher__", None)
+        pf_ = x0.chain.prefetcher
 
         def hook_point(name):
             if pf_ is not None and pf_.hook_at == name:
@@ -321,8 +314,8 @@ class _BackboneBase(nn.Module):
         hook_point("conv4")
         out = self.conv_out(x_conv4) if self.conv_out is not None else None    # (UNetV2 without RETURN_ENCODED_TENSOR)
         ops.stamp("conv_out")
-        if "__prefetcher__" in x0.indice_dict:                 # every unit was consumed; join the stream(s) anyway
-            pf = x0.indice_dict.pop("__prefetcher__")
+        pf, x0.chain.prefetcher = x0.chain.prefetcher, None
+        if pf is not None:                                     # every unit was consumed; join the stream(s) anyway
             pf.run_hook(after_stream=torch.cuda.current_stream())      # (a hook point that came before the last unit was issued)
             torch.cuda.current_stream().wait_stream(pf.side)
             if pf.unit0_stream is not None:

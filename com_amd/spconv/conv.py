@@ -154,8 +154,8 @@ class SparseConvolution(SparseModule):
             self._packs.key = [None, None]
         return super().train(mode)
 
-    def _rulebook(self, x):
-        """Look up / build the rulebook; returns (rulebook, out_indices, out_spatial_shape)."""
+    def _rulebook(self, x, subm_hint=None):
+        """Look up / build the rulebook; returns (rulebook, out_indices, out_spatial_shape).  `subm_hint`: see below."""
         cached = x.find_indice_pair(self.indice_key)
         if self.inverse:
             assert cached is not None and self.indice_key is not None, \
@@ -168,18 +168,14 @@ class SparseConvolution(SparseModule):
         if cached is not None and not self.subm and cached[1] is x.indices and cached[0].out_indices is not None:
             rb = cached[0]                          # pre-built for exactly this input (rulebook prefetch)
             return rb, rb.out_indices, rb.out_shape
+        chain = x.chain
+        order = chain.row_order                     # (set by the backbone from the voxeliser's rank map)
+        rank = chain.rank_of(x.indices)             # rows created by the voxeliser or a strided conv of this chain: no hash table
         if self.subm:
             # a SubM rulebook depends only on (indices, kernel, dilation): layers with different indice_keys on
             # the same tensor (conv_input 'subm1' and conv1 'res1' of VoxelResBackBone8x) share one build
-            gkey = ("__subm__", x.indices.data_ptr(), x.indices.shape[0], tuple(self.kernel_size),
-                    tuple(self.dilation))
-            hit = x.indice_dict.get(gkey, None)
-            if hit is not None and hit[1] is x.indices:
-                rb = hit[0]
-            else:
-                # rows created by a strided conv of this chain are its bitmap ranks: no hash table needed
-                rank = x.indice_dict.get(("__rank__", x.indices.data_ptr()), None)
-                order = x.indice_dict.get("__row_order__", ops.ROWS_ZYX)
+            rb = chain.subm_rulebook(x.indices, self.kernel_size, self.dilation)
+            if rb is None:
                 # 16-channel layers run their weight gradient through nbr_out (ops.WGRAD_OS): their rulebook is built
                 # without indice_pairs (derived on demand if some other consumer asks for them), and so are the layers whose
                 # weight gradient runs over the window kernel's tiles
@@ -187,17 +183,16 @@ class SparseConvolution(SparseModule):
                         and tuple(self.kernel_size) == (3, 3, 3)) \
                     or window.wgrad_on_tiles(window.forward_on_tiles(self, order), self.in_channels, self.out_channels)
                 # with a column map the window plan comes out of the same pass as the rulebook; a caller that knows ALL
-                # consumers of this rulebook (the backbones' prefetcher: indice_dict["__subm_hint__"] = (width, tables needed))
-                # can drop the neighbour table altogether -- alone, a layer keeps it for the others
-                hint = x.indice_dict.pop("__subm_hint__", None)
+                # consumers of this rulebook (the backbones' prefetcher: subm_hint = (width, tables needed)) can drop the
+                # neighbour table altogether -- alone, a layer keeps it for the others
                 win_c, tables = (self.out_channels if window.forward_on_tiles(self, order) else None), True
-                if hint is not None and order == ops.ROWS_YXZ:
-                    win_c, tables = hint
+                if subm_hint is not None and order == ops.ROWS_YXZ:
+                    win_c, tables = subm_hint
                 rb = ops.rulebook_subm(x.indices, x.batch_size, x.spatial_shape, self.kernel_size,
                                        self.dilation, n_dev=x.num_rows, rank=rank,
                                        want_pairs=self._needs_backward(x) and not lazy,   # (inference never needs them)
                                        window=(win_c, win_c) if win_c else None, nbr_tables=tables)
-                x.indice_dict[gkey] = (rb, x.indices, list(x.spatial_shape))
+                chain.add_subm_rulebook(x.indices, self.kernel_size, self.dilation, rb)
             out_idx, out_shape = x.indices, x.spatial_shape
         else:
             rb = ops.rulebook_conv(x.indices, x.batch_size, x.spatial_shape, self.kernel_size, self.stride,
@@ -208,13 +203,11 @@ class SparseConvolution(SparseModule):
                                    pair_lists=not (ops.IMPLICIT_STRIDED_PAIRS and not (self.in_channels == 128 and self.out_channels == 128)),
                                    compact=ops.COMPACT_STRIDED_TABLES and self._compact_tables_usable(x),
                                    plan_key=("conv", self.indice_key if self.indice_key is not None else id(self)),
-                                   # the chain's row order (set by the backbone from the voxeliser's rank map)
-                                   order=x.indice_dict.get("__row_order__", ops.ROWS_ZYX),
                                    # (z-fastest chains: the input level's column map -> the output level's)
-                                   in_rank=x.indice_dict.get(("__rank__", x.indices.data_ptr()), None))
+                                   order=order, in_rank=rank)
             out_idx, out_shape = rb.out_indices, rb.out_shape
             if rb.rank is not None:
-                x.indice_dict[("__rank__", out_idx.data_ptr())] = rb.rank
+                chain.add_rank(rb.rank)             # (the map of the level this conv opens: rb.rank.indices is out_idx)
         if self.indice_key is not None:
             # spconv stores (.., indice_pairs, indice_pair_num, spatial_shape) by key; for inverse convs
             # we also remember the INPUT side
@@ -272,11 +265,9 @@ class SparseConvolution(SparseModule):
         if passthrough:
             feats, ident = feats
         out = SparseConvTensor(feats, out_idx, out_shape, input.batch_size, input.grid, input.voxel_num,
-                               input.indice_dict, input.benchmark, rb.n_out_dev)
-        if first_use:                               # first consumer of a prefetched unit: start the next unit
-            pf = input.indice_dict.get("__prefetcher__", None)
-            if pf is not None:
-                pf.advance()
+                               input.indice_dict, input.benchmark, rb.n_out_dev, chain=input.chain)
+        if first_use and input.chain.prefetcher is not None:   # first consumer of a prefetched unit: start the next unit
+            input.chain.prefetcher.advance()
         if passthrough:
             return out, ident
         return out
@@ -293,7 +284,7 @@ class SparseConvolution(SparseModule):
         feats = Fsp.sparse_inverse_conv(input.features, self.weight, rb, self._packs.get(self, 0),
                                         lambda: self._packs.dgrad_for(self, False))
         return SparseConvTensor(feats, in_indices, in_shape, input.batch_size, input.grid, input.voxel_num,
-                                input.indice_dict, input.benchmark, rb.n_in_dev)
+                                input.indice_dict, input.benchmark, rb.n_in_dev, chain=input.chain)
 
 
 class SubMConv3d(SparseConvolution):

@@ -133,7 +133,7 @@ class Fp8Backbone(torch.nn.Module):
             else:
                 y = conv_fp8(x8, packed, rb, conv.out_channels, alpha, beta, True, "fp8", self.scales[i + 1])
             cur = SparseConvTensor(y, out_idx, out_shape, cur.batch_size, indice_dict=cur.indice_dict,
-                                   num_rows=rb.n_out_dev)
+                                   num_rows=rb.n_out_dev, chain=cur.chain)
             if tap is not None:
                 taps[tap] = (cur, None if last else self.scales[i + 1], conv.out_channels)
             x8 = y

@@ -132,8 +132,7 @@ def window_decisions(monkeypatch):
                 conv = spconv.SubMConv3d(cin, cout, k, padding=1, dilation=dil, bias=False)
                 rec = {"window_capable": bool(conv.window_capable()), "window_wgrad": bool(_window_wgrad(cout))}
                 for dname, dtype in (("bf16", torch.bfloat16), ("fp32", torch.float32)):
-                    t = types.SimpleNamespace(features=torch.zeros(4, cin, dtype=dtype),
-                                              indice_dict={"__row_order__": ops.ROWS_YXZ})
+                    t = types.SimpleNamespace(features=torch.zeros(4, cin, dtype=dtype))
                     for fp8 in (False, True):
                         conv.fp8_train = object() if fp8 else None
                         for gname, ctx in (("grad", torch.enable_grad), ("no_grad", torch.no_grad)):

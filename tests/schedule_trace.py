@@ -123,8 +123,8 @@ def sparse_case():
     def step():
         nonlocal gout
         x = spconv.SparseConvTensor(feats, idx_t, shape, batch)
-        x.indice_dict["__row_order__"] = ops.ROWS_YXZ
-        x.indice_dict[("__rank__", idx_t.data_ptr())] = cmap
+        x.chain.row_order = ops.ROWS_YXZ
+        x.chain.add_rank(cmap)
         y = net(x).features
         if gout is None:
             gout = torch.randn(y.shape, generator=torch.Generator().manual_seed(13)).to(DEV).to(y.dtype)

@@ -538,7 +538,7 @@ def test_inverse_convs_on_the_strided_kernels(golden, mode):
                 z = z0.clone().requires_grad_(True)
                 inv.weight.grad = None
                 out = inv(SparseConvTensor(z, y.indices, y.spatial_shape, y.batch_size, indice_dict=y.indice_dict,
-                                           num_rows=y.num_rows))
+                                           num_rows=y.num_rows, chain=y.chain))
                 assert out.features.shape == (n_in, cout) and out.indices.shape[0] == n_in
                 out.features.backward(dy)
                 torch.cuda.synchronize()

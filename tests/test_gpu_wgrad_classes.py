@@ -357,8 +357,8 @@ def test_layers_with_compact_tables_train_to_the_same_values(monkeypatch):
         for c in (c1, c2):
             c.zero_grad()
         x = spconv.SparseConvTensor(feats.clone().requires_grad_(True), idx_t, shape, batch)
-        x.indice_dict["__row_order__"] = ops.ROWS_YXZ
-        x.indice_dict[("__rank__", idx_t.data_ptr())] = cmap
+        x.chain.row_order = ops.ROWS_YXZ
+        x.chain.add_rank(cmap)
         with plan:
             y = c2(c1(x))
             n_out = int(y.indice_dict["b"][0].n_out_dev.item()) if plan.active else y.features.shape[0]

@@ -111,7 +111,8 @@ def inverse_layers(net, make, rounds, iters):
             try:
                 z = z0.clone().requires_grad_(True)
                 conv.weight.grad = None
-                y = conv(SparseConvTensor(z, src.indices, src.spatial_shape, B, indice_dict=src.indice_dict, num_rows=src.num_rows))
+                y = conv(SparseConvTensor(z, src.indices, src.spatial_shape, B, indice_dict=src.indice_dict, num_rows=src.num_rows,
+                                          chain=src.chain))
                 y.features.backward(dy)
                 if keep is not None:
                     keep.extend([y.features.detach().float(), z.grad.float(), conv.weight.grad.clone()])
