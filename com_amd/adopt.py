@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .hotpath import anchor_head, backbone3d, center_head, curriculum_head, dense2d, map_to_bev, unet, vfe
+from .hotpath import anchor_head, anchor_head_multi, backbone3d, center_head, curriculum_head, dense2d, map_to_bev, unet, vfe
 from .hotpath.conv2d_fast import BatchNormReLU2d
 from .spconv.conv import SparseConvolution
 
@@ -265,14 +265,9 @@ def _adopt_head(path, s, cls, **_):
 _ANCHOR_LOSS_CHILDREN = ("cls_loss_func", "reg_loss_func", "dir_loss_func")
 
 
-def _adopt_anchor_head(path, s, cls, model=None, **_):
-    """AnchorHeadSingle (anchor_head_single.py + anchor_head_template.py).  The stock head keeps neither grid_size nor
-    point_cloud_range; Detector3DTemplate keeps `dataset`, which has both.  The counterpart describes its anchors instead of
-    storing them, from its own host generator: they must equal the stock head's `anchors` bit for bit."""
-    try:
-        cin = int(s.conv_cls.in_channels)
-    except AttributeError as exc:
-        raise _Refuse(path, f"no conv_cls conv ({exc})") from exc
+def _anchor_dataset(path, s, model):
+    """`model.dataset` (an anchor head's grid_size / point_cloud_range: the stock head keeps neither, Detector3DTemplate keeps
+    `dataset`, which has both); the stock loss modules are replaced, so they must hold no state"""
     dataset = getattr(model, "dataset", None)
     if dataset is None:
         raise _Refuse(path, "the model has no `dataset` (grid_size / point_cloud_range of an anchor head come from "
@@ -280,10 +275,17 @@ def _adopt_anchor_head(path, s, cls, model=None, **_):
     for a in ("grid_size", "point_cloud_range"):
         if getattr(dataset, a, None) is None:
             raise _Refuse(path, f"model.dataset has no {a}")
-    for k in _ANCHOR_LOSS_CHILDREN:                          # the stock loss modules are replaced, so they must hold no state
+    for k in _ANCHOR_LOSS_CHILDREN:
         m = getattr(s, k, None)
         if isinstance(m, nn.Module) and (list(m.parameters()) or m.state_dict()):
             raise _Refuse(f"{path}.{k}", "loss module with parameters / persistent buffers")
+    return dataset
+
+
+def _build_anchor_head(path, s, cls, cin, dataset):
+    """The counterpart of a stock anchor head.  It describes its anchors instead of storing them, from its own host generator:
+    they must equal the stock head's `anchors` bit for bit; same coder and code size.  What its constructor refuses (a
+    PcdError naming the key) is an adopt refusal."""
     try:
         new = _build(lambda: cls(s.model_cfg, cin, s.num_class, s.class_names, dataset.grid_size, dataset.point_cloud_range,
                                  predict_boxes_when_training=getattr(s, "predict_boxes_when_training", True)))
@@ -297,9 +299,40 @@ def _adopt_anchor_head(path, s, cls, model=None, **_):
         if a.dtype != b.dtype or tuple(a.shape) != tuple(b.shape) or not torch.equal(a, b):
             raise _Refuse(f"{path}.anchors[{i}]", "differs from the anchors the fused head generates from model.dataset's "
                                                   "grid_size / point_cloud_range")
-    _same(path, "num_anchors_per_location", int(s.num_anchors_per_location), int(new.num_anchors_per_location))
     _same(path, "box_coder", type(s.box_coder).__name__, "ResidualCoder")
     _same(path, "box_coder.code_size", int(s.box_coder.code_size), int(new.box_coder.code_size))
+    return new
+
+
+def _adopt_anchor_head(path, s, cls, model=None, **_):
+    """AnchorHeadSingle (anchor_head_single.py + anchor_head_template.py)."""
+    try:
+        cin = int(s.conv_cls.in_channels)
+    except AttributeError as exc:
+        raise _Refuse(path, f"no conv_cls conv ({exc})") from exc
+    new = _build_anchor_head(path, s, cls, cin, _anchor_dataset(path, s, model))
+    _same(path, "num_anchors_per_location", int(s.num_anchors_per_location), int(new.num_anchors_per_location))
+    _match(path, s, new, extra_ok=_ANCHOR_LOSS_CHILDREN)
+    return _rehome(path, s, new, extra_ok=_ANCHOR_LOSS_CHILDREN)
+
+
+def _adopt_anchor_head_multi(path, s, cls, model=None, **_):
+    """AnchorHeadMulti (anchor_head_multi.py + anchor_head_template.py): as _adopt_anchor_head, with the per-class
+    `num_anchors_per_location` list and an identical state-dict key / shape set (heads, branches of SEPARATE_REG_CONFIG)."""
+    try:
+        shared = getattr(s, "shared_conv", None)
+        first = shared[0] if shared is not None else next(m for m in s.rpn_heads[0].modules() if isinstance(m, nn.Conv2d))
+        cin = int(first.in_channels)
+    except (AttributeError, TypeError, IndexError, StopIteration) as exc:
+        raise _Refuse(path, f"no shared_conv[0] / rpn_heads[0] conv ({exc})") from exc
+    new = _build_anchor_head(path, s, cls, cin, _anchor_dataset(path, s, model))
+    _same(path, "num_anchors_per_location", [int(v) for v in s.num_anchors_per_location],
+          [int(v) for v in new.num_anchors_per_location])
+    stock_state = {k: tuple(v.shape) for k, v in s.state_dict().items()}
+    new_state = {k: tuple(v.shape) for k, v in new.state_dict().items()}
+    if stock_state != new_state:
+        odd = sorted(k for k in set(stock_state) | set(new_state) if stock_state.get(k) != new_state.get(k))
+        raise _Refuse(f"{path}.{odd[0]}", "state-dict key / shape the fused head does not share")
     _match(path, s, new, extra_ok=_ANCHOR_LOSS_CHILDREN)
     return _rehome(path, s, new, extra_ok=_ANCHOR_LOSS_CHILDREN)
 
@@ -316,6 +349,7 @@ RECOGNISED = {
     "CurriculumCenterHead": (_adopt_head, curriculum_head.CurriculumCenterHead),
     "CurriculumCenterHead_x5": (_adopt_head, curriculum_head.CurriculumCenterHead_x5),
     "AnchorHeadSingle": (_adopt_anchor_head, anchor_head.AnchorHeadSingle),
+    "AnchorHeadMulti": (_adopt_anchor_head_multi, anchor_head_multi.AnchorHeadMulti),
 }
 _FUSED = tuple({c for _, c in RECOGNISED.values()})
 

@@ -19,37 +19,6 @@
 
 namespace {
 
-bool am_code_ok(int code, int sincos) {
-    const int code_gt = code - sincos;
-    return (sincos == 0 || sincos == 1) && (code_gt == 7 || code_gt == 9);
-}
-
-// heads -> the kernel argument; false unless they tile the kinds [0, n_kinds) and the classes [0, num_class) in order and
-// agree on the direction maps.  need_grad: the three (two) gradient pointers must be there.
-bool am_fill_heads(KindMajor &hd, const PcdAnchorMultiHead *heads, int n_heads, int n_kinds, int num_class, bool need_grad,
-                   bool &has_dir) {
-    if (!heads || n_heads < 1 || n_heads > ANC_MAX_HEADS) return false;
-    int kind = 0, cls = 0;
-    has_dir = heads[0].map[2] != nullptr;
-    for (int h = 0; h < n_heads; ++h) {
-        const PcdAnchorMultiHead &s = heads[h];
-        if (!s.map[0] || !s.map[1] || (s.map[2] != nullptr) != has_dir) return false;
-        if (need_grad && (!s.grad[0] || !s.grad[1] || (has_dir && !s.grad[2]))) return false;
-        if (s.kind0 != kind || s.n_kinds < 1 || s.class0 != cls || s.num_class < 1) return false;
-        kind += s.n_kinds;
-        cls += s.num_class;
-        hd.h[h] = s;
-        if (!has_dir) clear_dir_row(hd.h[h]);
-        hd.cls_out[h] = nullptr;
-    }
-    for (int h = n_heads; h < ANC_MAX_HEADS; ++h) {
-        hd.h[h] = PcdAnchorMultiHead{};
-        hd.cls_out[h] = nullptr;
-    }
-    hd.n = n_heads;
-    return kind == n_kinds && cls == num_class;
-}
-
 // the config of both loss entries (has_dir as the first head shows it: am_fill_heads, which runs after the checks here,
 // holds every head to it)
 bool am_loss_cfg(AncLossCfg &c, const PcdAnchorMultiHead *heads, int dtype, int batch, int height, int width, int n_kinds,

@@ -6,7 +6,9 @@ kitti_models/second_multihead.yaml) as a registry drop-in: same constructor argu
 strict=True) and `forward(data_dict)` contract, with target assignment, the losses + their gradients and the box decoding
 of ALL heads on the device (com_amd/csrc/anchorhead_multi.hip; C ABI `pcd_anchor_multi_*`): no host loop over frames,
 classes and heads, no [N, M] IoU matrix, no `nonzero()`, no `.item()` -- forward + get_loss + backward can sit in a
-captured graph.
+captured graph.  In eval mode `static_predictions` in the data dict swaps generate_predicted_boxes + the detector's
+per-class post_processing for their static form (com_amd/csrc/anchor_multi_postproc.hip; com_amd.postprocess), which
+com_amd.infer.CapturedInference captures with the forward.
 
 Scope: USE_MULTIHEAD + SEPARATE_MULTIHEAD, AxisAlignedTargetAssigner (MATCH_HEIGHT False, POS_FRACTION < 0,
 NORM_BY_NUM_EXAMPLES False), ResidualCoder (code_size 7 | 9, encode_angle_by_sincos), WeightedSmoothL1Loss |
@@ -21,6 +23,7 @@ import ctypes
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import _lib as L
 from .. import iou3d_nms
@@ -350,12 +353,16 @@ class SingleHead(BaseBEVBackbone):
         x = spatial_features_2d
         if len(self.blocks) > 0:
             x = super().forward({'spatial_features': x})['spatial_features_2d']
-        cls_preds = self.conv_cls(x)
+        # (the plain 1 x 1 convs keep fp32 parameters; behind a bf16 trunk they run in the dtype of the map, as
+        #  AnchorHeadSingle's do)
+        def conv1x1(conv):
+            return F.conv2d(x, conv.weight.to(x.dtype), conv.bias.to(x.dtype))
         if self.separate_reg_config is None:
-            box_preds = self.conv_box(x)
+            cls_preds, box_preds = conv1x1(self.conv_cls), conv1x1(self.conv_box)
         else:
+            cls_preds = self.conv_cls(x)
             box_preds = torch.cat([self.conv_box[name](x) for name in self.conv_box_names], dim=1)
-        dir_cls_preds = self.conv_dir_cls(x) if self.conv_dir_cls is not None else None
+        dir_cls_preds = conv1x1(self.conv_dir_cls) if self.conv_dir_cls is not None else None
         if dir_cls_preds is not None and dir_cls_preds.dtype != cls_preds.dtype:
             dir_cls_preds = dir_cls_preds.to(cls_preds.dtype)
         if box_preds.dtype != cls_preds.dtype:
@@ -456,6 +463,8 @@ class AnchorHeadMulti(nn.Module):
                                     self.box_coder.code_size, cfg, head_label_indices=label_indices,
                                     separate_reg_config=_get(self.model_cfg, 'SEPARATE_REG_CONFIG', None)))
         self.rpn_heads = nn.ModuleList(heads)
+        # the label of every global class on the host (head_label_indices, heads concatenated): the static path's table
+        self.head_labels = [self.class_names.index(n) + 1 for cfg in head_cfgs for n in cfg['HEAD_CLS_NAME']]
 
     tables = cached_tables
 
@@ -479,8 +488,22 @@ class AnchorHeadMulti(nn.Module):
         assert cls_preds[0].shape[0] == batch_size
         return decode_boxes(self.tables(cls_preds[0].device), cls_preds, box_preds, dir_cls_preds)
 
+    def generate_predicted_boxes_static(self, cls_preds, box_preds, dir_cls_preds, post_process_cfg):
+        """generate_predicted_boxes + the detector's MULTI_CLASSES_NMS post_processing as fixed-shape device tensors, without
+        a host read-back and without the [B, N, D] / [B, N_h, C_h] tensors (postprocess.anchor_multi_predictions_static):
+        {'boxes' [B, M, D], 'scores' [B, M], 'labels' [B, M], 'count' [B]}, M = num_class x NMS_POST_MAXSIZE;
+        postprocess.to_pred_dicts gives the list.  post_process_cfg: the DETECTOR's POST_PROCESSING block."""
+        from .. import postprocess
+        if post_process_cfg is None:
+            raise L.PcdError("AnchorHeadMulti: static_predictions needs data_dict['post_process_cfg'] (the detector's "
+                             "POST_PROCESSING block)")
+        with torch.no_grad():
+            return postprocess.anchor_multi_predictions_static(self, cls_preds, box_preds, dir_cls_preds, post_process_cfg)
+
     def forward(self, data_dict):
-        """anchor_head_multi.py:198-243"""
+        """anchor_head_multi.py:198-243.  In eval mode `data_dict.pop('static_predictions', False)` asks for the static
+        post-processing instead of generate_predicted_boxes: `final_box_tensors` from data_dict['post_process_cfg'], no
+        batch_box_preds / batch_cls_preds / multihead_label_mapping."""
         x = data_dict['spatial_features_2d']
         if self.shared_conv is not None:
             x = self.shared_conv(x)
@@ -491,6 +514,11 @@ class AnchorHeadMulti(nn.Module):
         self.forward_ret_dict.update(ret)
         if self.training:
             self.forward_ret_dict.update(self.assign_targets(gt_boxes=data_dict['gt_boxes']))
+        # (popped in every mode, so that the key never travels on; honoured in eval mode only)
+        if data_dict.pop('static_predictions', False) and not self.training:
+            data_dict['final_box_tensors'] = self.generate_predicted_boxes_static(
+                ret['cls_preds'], ret['box_preds'], ret.get('dir_cls_preds', None), data_dict.get('post_process_cfg', None))
+            return data_dict
         if not self.training or self.predict_boxes_when_training:
             with torch.no_grad():
                 batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(

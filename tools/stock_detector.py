@@ -13,6 +13,8 @@ state-dict keys.  `com_amd.adopt.adopt_model` turns such an object into the fuse
     build_detector("com")          + BaseBEVBackbone + CurriculumCenterHead_x5         (the COM head, bench.py --com)
     build_detector("second")       MeanVFE -> VoxelBackBone8x -> HeightCompression -> BaseBEVBackbone -> AnchorHeadSingle,
                                    POST_PROCESSING on the detector                     (waymo_models/second.yaml)
+    build_detector("second_multihead")  the same with AnchorHeadMulti: three one-class heads behind a shared conv,
+                                   MULTI_CLASSES_NMS                                   (kitti_models/second_multihead.yaml)
 """
 import copy
 import types
@@ -350,6 +352,159 @@ class AnchorHeadSingle(nn.Module):
         return data_dict
 
 
+def _plain_stack(c_in, c_mid, n_mid, c_out):
+    """(conv3x3 without bias, BatchNorm2d, ReLU) x n_mid + conv3x3 with bias: a branch of a SEPARATE_REG_CONFIG head"""
+    layers = []
+    for _ in range(n_mid):
+        layers += [nn.Conv2d(c_in, c_mid, kernel_size=3, stride=1, padding=1, bias=False), nn.BatchNorm2d(c_mid), nn.ReLU()]
+        c_in = c_mid
+    layers.append(nn.Conv2d(c_in, c_out, kernel_size=3, stride=1, padding=1, bias=True))
+    return nn.Sequential(*layers)
+
+
+class SingleHead(nn.Module):
+    """One head of the plain multi-head anchor head: a (here always empty) BaseBEVBackbone tower -- `blocks` / `deblocks`
+    stay in the module tree -- then `conv_cls`, `conv_box` (1 x 1 convs, or 3 x 3 stacks per SEPARATE_REG_CONFIG branch in
+    a ModuleDict) and `conv_dir_cls`, buffer `head_label_indices`.  forward returns the maps as the convs write them,
+    [B, A * items, H, W] (box branches concatenated in REG_LIST order): the layout com_amd.hotpath.anchor_head_multi's
+    functions address with the stock view(-1, A, items, H, W) channel rule."""
+
+    def __init__(self, model_cfg, input_channels, num_class, num_anchors_per_location, code_size, rpn_head_cfg=None,
+                 head_label_indices=None, separate_reg_config=None):
+        super().__init__()
+        if rpn_head_cfg is not None and rpn_head_cfg.get('LAYER_NUMS'):
+            raise NotImplementedError("stock SingleHead: a head tower (LAYER_NUMS) is not part of this test model")
+        self.blocks, self.deblocks = nn.ModuleList(), nn.ModuleList()
+        self.num_anchors_per_location, self.num_class, self.code_size = num_anchors_per_location, num_class, code_size
+        self.model_cfg, self.separate_reg_config = model_cfg, separate_reg_config
+        self.register_buffer('head_label_indices', head_label_indices)
+        A = num_anchors_per_location
+        if separate_reg_config is not None:
+            n_mid, c_mid = separate_reg_config['NUM_MIDDLE_CONV'], separate_reg_config['NUM_MIDDLE_FILTER']
+            self.conv_box = nn.ModuleDict()
+            self.conv_box_names = []
+            self.conv_cls = _plain_stack(input_channels, c_mid, n_mid, A * num_class)
+            for reg_config in separate_reg_config['REG_LIST']:
+                reg_name, reg_channel = reg_config.split(':')
+                self.conv_box[f'conv_{reg_name}'] = _plain_stack(input_channels, c_mid, n_mid, A * int(reg_channel))
+                self.conv_box_names.append(f'conv_{reg_name}')
+            for m in self.conv_box.modules():
+                if isinstance(m, nn.Conv2d):
+                    nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+                    if m.bias is not None:
+                        nn.init.constant_(m.bias, 0)
+        else:
+            self.conv_cls = nn.Conv2d(input_channels, A * num_class, kernel_size=1)
+            self.conv_box = nn.Conv2d(input_channels, A * code_size, kernel_size=1)
+        if model_cfg.get('USE_DIRECTION_CLASSIFIER', None) is not None:
+            self.conv_dir_cls = nn.Conv2d(input_channels, A * model_cfg['NUM_DIR_BINS'], kernel_size=1)
+        else:
+            self.conv_dir_cls = None
+        last = self.conv_cls if isinstance(self.conv_cls, nn.Conv2d) else self.conv_cls[-1]
+        nn.init.constant_(last.bias, -np.log((1 - 0.01) / 0.01))
+
+    def forward(self, x):
+        if self.separate_reg_config is None:
+            box_preds = self.conv_box(x)
+        else:
+            box_preds = torch.cat([self.conv_box[name](x) for name in self.conv_box_names], dim=1)
+        return {'cls_preds': self.conv_cls(x), 'box_preds': box_preds,
+                'dir_cls_preds': self.conv_dir_cls(x) if self.conv_dir_cls is not None else None}
+
+
+class AnchorHeadMulti(nn.Module):
+    """The plain multi-head anchor head (USE_MULTIHEAD + SEPARATE_MULTIHEAD): `shared_conv` (conv3x3, BatchNorm2d, ReLU) and
+    one SingleHead per RPN_HEAD_CFGS entry in fp32 torch; the anchors kept as the template keeps them (`anchors`: one tensor
+    per class, `num_anchors_per_location`: one count per class, `box_coder`); target assignment, loss and box decoding of
+    com_amd.hotpath.anchor_head_multi; the eager per-class post-processing is that module's `post_processing`."""
+
+    def __init__(self, model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range,
+                 predict_boxes_when_training=True, **kwargs):
+        super().__init__()
+        from com_amd.hotpath import anchor_head as AH, anchor_head_multi as AM
+        self.model_cfg, self.num_class, self.class_names = model_cfg, num_class, class_names
+        self.predict_boxes_when_training = predict_boxes_when_training
+        self.use_multihead, self.separate_multihead = True, True
+        self.use_dir = bool(model_cfg.get('USE_DIRECTION_CLASSIFIER', False))
+        ta, ag_cfg, head_cfgs = model_cfg['TARGET_ASSIGNER_CONFIG'], model_cfg['ANCHOR_GENERATOR_CONFIG'], model_cfg['RPN_HEAD_CFGS']
+        self.box_coder = AM.ResidualCoder(num_dir_bins=ta.get('NUM_DIR_BINS', 6), **(ta.get('BOX_CODER_CONFIG', None) or {}))
+        sincos = self.box_coder.encode_angle_by_sincos
+        grid_xy = np.asarray(grid_size)[:2]
+        gen = AH.AnchorGenerator(point_cloud_range, ag_cfg)
+        anchors, self.num_anchors_per_location = gen.generate_anchors([grid_xy // c['feature_map_stride'] for c in ag_cfg])
+        if self.box_coder.code_size != 7:
+            anchors = [torch.cat((a, a.new_zeros([*a.shape[:-1], self.box_coder.code_size - 7])), dim=-1) for a in anchors]
+        self.anchors = anchors
+        self.num_dir_bins = int(model_cfg.get('NUM_DIR_BINS', 2)) if self.use_dir else 1
+        self._tables_host = AM.multi_tables(
+            ag_cfg, list(class_names), point_cloud_range, grid_xy, [len(h['HEAD_CLS_NAME']) for h in head_cfgs],
+            self.box_coder.code_size - int(sincos), sincos, self.num_dir_bins,
+            model_cfg.get('DIR_OFFSET', 0.0) if self.use_dir else 0.0, model_cfg.get('DIR_LIMIT_OFFSET', 0.0) if self.use_dir else 0.0)
+        self._tables = {}
+        if model_cfg.get('SHARED_CONV_NUM_FILTER', None) is not None:
+            c = model_cfg['SHARED_CONV_NUM_FILTER']
+            self.shared_conv = nn.Sequential(nn.Conv2d(input_channels, c, 3, stride=1, padding=1, bias=False),
+                                             nn.BatchNorm2d(c, eps=1e-3, momentum=0.01), nn.ReLU())
+        else:
+            self.shared_conv, c = None, input_channels
+        names = [n for h in head_cfgs for n in h['HEAD_CLS_NAME']]
+        heads = []
+        for cfg in head_cfgs:
+            per_location = sum(self.num_anchors_per_location[names.index(n)] for n in cfg['HEAD_CLS_NAME'])
+            label_indices = torch.from_numpy(np.array([list(class_names).index(n) + 1 for n in cfg['HEAD_CLS_NAME']]))
+            heads.append(SingleHead(model_cfg, c, len(cfg['HEAD_CLS_NAME']), per_location, self.box_coder.code_size, cfg,
+                                    head_label_indices=label_indices,
+                                    separate_reg_config=model_cfg.get('SEPARATE_REG_CONFIG', None)))
+        self.rpn_heads = nn.ModuleList(heads)
+        self.forward_ret_dict = {}
+        for name in ('cls_loss_func', 'reg_loss_func', 'dir_loss_func'):
+            self.add_module(name, _LossSlot())
+
+    def tables(self, device):
+        from com_amd.hotpath import anchor_head as AH
+        return AH.cached_tables(self, device)
+
+    def get_loss(self):
+        from com_amd.hotpath import anchor_head_multi as AM
+        f = self.forward_ret_dict
+        dev = f['cls_preds'][0].device
+        lc = self.model_cfg['LOSS_CONFIG']
+        lw = lc['LOSS_WEIGHTS']
+        settings = AM.LossSettings(self.num_class, lc.get('REG_LOSS_TYPE', None) == 'WeightedL1Loss', lw.get('pos_cls_weight', 1.0),
+                                   lw.get('neg_cls_weight', 1.0), lw['cls_weight'], lw['loc_weight'], lw.get('dir_weight', 0.0),
+                                   self.use_dir)
+        code_weights = torch.tensor(lw['code_weights'], dtype=torch.float32, device=dev)
+        loss, out = AM.multi_loss(f['cls_preds'], f['box_preds'], f.get('dir_cls_preds'), f, self.tables(dev), code_weights,
+                                  settings)
+        tb = {'rpn_loss_cls': out[1], 'rpn_loss_loc': out[2], 'rpn_loss': out[0]}
+        if self.use_dir:
+            tb['rpn_loss_dir'] = out[3]
+        return loss, tb
+
+    def forward(self, data_dict):
+        from com_amd.hotpath import anchor_head_multi as AM
+        x = data_dict['spatial_features_2d']
+        if self.shared_conv is not None:
+            x = self.shared_conv(x)
+        rets = [head(x) for head in self.rpn_heads]
+        ret = {'cls_preds': [r['cls_preds'] for r in rets], 'box_preds': [r['box_preds'] for r in rets]}
+        if self.use_dir:
+            ret['dir_cls_preds'] = [r['dir_cls_preds'] for r in rets]
+        self.forward_ret_dict.update(ret)
+        tab = self.tables(x.device)
+        if self.training:
+            self.forward_ret_dict.update(AM.assign_targets(tab, data_dict['gt_boxes']))
+        if not self.training or self.predict_boxes_when_training:
+            with torch.no_grad():
+                batch_cls_preds, batch_box_preds = AM.decode_boxes(tab, ret['cls_preds'], ret['box_preds'],
+                                                                   ret.get('dir_cls_preds', None))
+            data_dict['multihead_label_mapping'] = [head.head_label_indices for head in self.rpn_heads]
+            data_dict['batch_cls_preds'] = batch_cls_preds
+            data_dict['batch_box_preds'] = batch_box_preds
+            data_dict['cls_preds_normalized'] = False
+        return data_dict
+
+
 # ---------------------------------------------------------------------------------------------------------- detector
 class StockDetector(nn.Module):
     """Detector3DTemplate + CenterPoint's forward / get_training_loss.  (tb_dict keeps the losses as device tensors: the
@@ -389,9 +544,10 @@ class StockDetector(nn.Module):
             elif name == 'backbone_2d' and cfg.get('BACKBONE_2D'):
                 m = BaseBEVBackbone(cfg.BACKBONE_2D, c)
                 c = m.num_bev_features
-            elif name == 'dense_head' and cfg.get('DENSE_HEAD') and cfg.DENSE_HEAD.NAME == 'AnchorHeadSingle':
-                m = AnchorHeadSingle(cfg.DENSE_HEAD, c, self.num_class, self.class_names, info['grid_size'],
-                                     info['point_cloud_range'], predict_boxes_when_training=False)
+            elif name == 'dense_head' and cfg.get('DENSE_HEAD') and cfg.DENSE_HEAD.NAME in ('AnchorHeadSingle', 'AnchorHeadMulti'):
+                cls = {'AnchorHeadSingle': AnchorHeadSingle, 'AnchorHeadMulti': AnchorHeadMulti}[cfg.DENSE_HEAD.NAME]
+                m = cls(cfg.DENSE_HEAD, c, self.num_class, self.class_names, info['grid_size'], info['point_cloud_range'],
+                        predict_boxes_when_training=False)
             elif name == 'dense_head' and cfg.get('DENSE_HEAD'):
                 cls = {'CenterHead': CenterHead, 'CurriculumCenterHead': CurriculumCenterHead,
                        'CurriculumCenterHead_x5': CurriculumCenterHead_x5}[cfg.DENSE_HEAD.NAME]
@@ -440,13 +596,28 @@ SECOND_MODEL = dict(
                                          NMS_POST_MAXSIZE=500)))
 
 
+def _second_multihead_model():
+    """SECOND_MODEL with the dense head and POST_PROCESSING of kitti_models/second_multihead.yaml on the three classes here:
+    three one-class heads behind a 64-channel shared conv, direction classifier, per-class NMS."""
+    d = copy.deepcopy(SECOND_MODEL)
+    head = d['DENSE_HEAD']
+    head.update(NAME='AnchorHeadMulti', USE_MULTIHEAD=True, SEPARATE_MULTIHEAD=True, SHARED_CONV_NUM_FILTER=64,
+                RPN_HEAD_CFGS=[dict(HEAD_CLS_NAME=[n]) for n in CLASS_NAMES])
+    d['POST_PROCESSING'].update(MULTI_CLASSES_NMS=True, SCORE_THRESH=0.1)
+    d['POST_PROCESSING']['NMS_CONFIG'].update(MULTI_CLASSES_NMS=True, NMS_TYPE='nms_gpu', NMS_THRESH=0.1, NMS_PRE_MAXSIZE=4096,
+                                              NMS_POST_MAXSIZE=500)
+    return d
+
+
 def model_cfg(kind, com_curriculum=None):
     """MODEL block of waymo_models/centerpoint.yaml (kind "centerpoint"), its 3-D part alone ("3d"), with the COM head
-    of com/centercurriculum_*_com.yaml ("com"), or of waymo_models/second.yaml ("second"); head hyper-parameters as
-    bench.py uses them."""
+    of com/centercurriculum_*_com.yaml ("com"), of waymo_models/second.yaml ("second"), or that with the multi-head dense
+    head of kitti_models/second_multihead.yaml ("second_multihead"); head hyper-parameters as bench.py uses them."""
     from com_amd.hotpath import dense2d
     if kind == 'second':
         return _cfg(SECOND_MODEL)
+    if kind == 'second_multihead':
+        return _cfg(_second_multihead_model())
     d = {'NAME': 'CenterPoint', 'VFE': {'NAME': 'MeanVFE'}, 'BACKBONE_3D': {'NAME': 'VoxelResBackBone8x'},
          'MAP_TO_BEV': {'NAME': 'HeightCompression', 'NUM_BEV_FEATURES': 256}}
     if kind in ('centerpoint', 'com'):
