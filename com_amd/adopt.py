@@ -17,7 +17,8 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .hotpath import anchor_head, anchor_head_multi, backbone3d, center_head, curriculum_head, dense2d, map_to_bev, unet, vfe
+from .hotpath import (anchor_head, anchor_head_multi, backbone3d, center_head, curriculum_head, dense2d, map_to_bev, second_head,
+                      unet, vfe)
 from .hotpath.conv2d_fast import BatchNormReLU2d
 from .spconv.conv import SparseConvolution
 
@@ -337,6 +338,42 @@ def _adopt_anchor_head_multi(path, s, cls, model=None, **_):
     return _rehome(path, s, new, extra_ok=_ANCHOR_LOSS_CHILDREN)
 
 
+_ROI_STATELESS_CHILDREN = ("proposal_target_layer", "reg_loss_func")
+
+
+def _adopt_second_head(path, s, cls, model=None, **_):
+    """SECONDHead (second_head.py + roi_head_template.py), for inference: the fused head built from the stock module's
+    `model_cfg` / `num_class` and the geometry of the BEV map (the stock module's `point_cloud_range` / `voxel_size` when it
+    kept them, else `model.dataset`'s); `shared_fc_layer` / `iou_layers` re-homed; an identical state-dict key / shape set.
+    The target layer and the loss holder are replaced as a whole, so they must hold no state."""
+    for k in _ROI_STATELESS_CHILDREN:
+        m = getattr(s, k, None)
+        if isinstance(m, nn.Module) and (list(m.parameters()) or m.state_dict()):
+            raise _Refuse(f"{path}.{k}", "module with parameters / persistent buffers")
+    dataset = getattr(model, "dataset", None)
+    geom = {}
+    for a in ("point_cloud_range", "voxel_size"):
+        v = getattr(s, a, None)
+        v = getattr(dataset, a, None) if v is None else v
+        if v is None:
+            raise _Refuse(path, f"no {a} on the module or on model.dataset (the geometry of the BEV map)")
+        geom[a] = [float(x) for x in v]
+    if getattr(s, "model_cfg", None) is None:
+        raise _Refuse(path, "no model_cfg")
+    try:
+        cin = int(dense2d._get(dense2d._get(s.model_cfg, "ROI_GRID_POOL"), "IN_CHANNEL"))
+        new = _build(lambda: cls(cin, s.model_cfg, num_class=int(getattr(s, "num_class", 1)), **geom))
+    except (L.PcdError, TypeError, AttributeError, KeyError) as exc:
+        raise _Refuse(path, str(exc)) from exc
+    stock_state = {k: tuple(v.shape) for k, v in s.state_dict().items()}
+    new_state = {k: tuple(v.shape) for k, v in new.state_dict().items()}
+    if stock_state != new_state:
+        odd = sorted(k for k in set(stock_state) | set(new_state) if stock_state.get(k) != new_state.get(k))
+        raise _Refuse(f"{path}.{odd[0]}", "state-dict key / shape the fused head does not share")
+    _match(path, s, new, extra_ok=_ROI_STATELESS_CHILDREN)
+    return _rehome(path, s, new, extra_ok=_ROI_STATELESS_CHILDREN)
+
+
 # class name -> (adopter, counterpart class)
 RECOGNISED = {
     "MeanVFE": (_adopt_vfe, vfe.MeanVFE),
@@ -350,6 +387,7 @@ RECOGNISED = {
     "CurriculumCenterHead_x5": (_adopt_head, curriculum_head.CurriculumCenterHead_x5),
     "AnchorHeadSingle": (_adopt_anchor_head, anchor_head.AnchorHeadSingle),
     "AnchorHeadMulti": (_adopt_anchor_head_multi, anchor_head_multi.AnchorHeadMulti),
+    "SECONDHead": (_adopt_second_head, second_head.SECONDHead),
 }
 _FUSED = tuple({c for _, c in RECOGNISED.values()})
 

@@ -6,12 +6,15 @@
         pred_dicts, ret_dict = model(batch_dict)        ->  out = infer(batch)      -- ONE graph replay
     (CenterHead.generate_predicted_boxes -> class_agnostic_nms -> nms_gpu inside the forward; for an anchor-head detector
      AnchorHeadSingle / AnchorHeadMulti.generate_predicted_boxes, then Detector3DTemplate.post_processing after it -- for
-     the multi head its per-frame, per-head, per-class multi_classes_nms loop)
+     the multi head its per-frame, per-head, per-class multi_classes_nms loop; for SECOND-IoU -- AnchorHeadSingle ->
+     SECONDHead -- RoIHeadTemplate.proposal_layer inside the RoI head's forward and SECONDNetIoU.post_processing after it)
                                                          ->  preds = infer.pred_dicts(out)   (final_box_dicts)
 
 `CapturedInference` mirrors com_amd.train.CapturedStep and reuses its pieces (VoxelizeConfig, ops.StaticPlan, the in-graph
 voxeliser): capacities are observed during eager warm-up forwards, then voxelise -> `module_list` forward (eval mode,
-no_grad, `static_predictions=True`) -> the static post-processing of com_amd.postprocess is captured as one hipGraph.
+no_grad, `static_predictions=True`) -> the static post-processing of com_amd.postprocess is captured as one hipGraph.  A
+two-stage detector is handed `static_proposal_cfg` too: its anchor head writes the RoIs straight from its maps
+(pcd_anchor_proposals), its RoI head the final boxes (pcd_roi_postproc).
 Every replay predicts the batch handed to that call (no one-behind staging as in training).
 
 Weights and BatchNorm statistics are read live by every replay: the captured forward packs the sparse and dense weight packs
@@ -27,6 +30,7 @@ from .hotpath.anchor_head import AnchorHeadSingle
 from .hotpath.anchor_head_multi import AnchorHeadMulti
 from .hotpath.center_head import BoxDecodeMixin
 from .hotpath.dense2d import _get
+from .hotpath.second_head import SECONDHead
 
 
 def _offsets(offs, dev):
@@ -41,18 +45,25 @@ class CapturedInference:
                centre head (BoxDecodeMixin; its own POST_PROCESSING), an AnchorHeadSingle / curriculum anchor head
                (class-agnostic NMS) or an AnchorHeadMulti (MULTI_CLASSES_NMS: per-class NMS as B x num_class selection
                problems); the anchor heads take the detector's `model_cfg.POST_PROCESSING`, handed to every forward as
-               `post_process_cfg`.  Detectors with a `roi_head` / `point_head` are refused (the second stage has no static
-               form), and so is an AnchorHeadMulti that is not the fused class.
+               `post_process_cfg`.  One two-stage form is accepted: a fused SECONDHead as `roi_head` behind a fused
+               AnchorHeadSingle (SECOND-IoU); both settings blocks -- the RoI head's NMS_CONFIG.TEST, handed to every
+               forward as `static_proposal_cfg`, and POST_PROCESSING with its SCORE_TYPE -- are validated before anything
+               runs, and the output carries `cls_scores` / `iou_scores` too.  Any other `roi_head`, a `point_head`, and an
+               AnchorHeadMulti that is not the fused class are refused.
     voxelize   com_amd.train.VoxelizeConfig.
     batch_size frames per call.
     margin     capacity over the observed row counts (ops.StaticPlan)."""
 
     def __init__(self, model, voxelize, batch_size, margin=1.25):
         head = getattr(model, "dense_head", None)
-        for slot in ("roi_head", "point_head"):
-            if getattr(model, slot, None) is not None:
-                raise L.PcdError(f"CapturedInference: the model has a {slot} ({type(getattr(model, slot)).__name__}): "
-                                 "two-stage detectors are not supported")
+        roi_head = getattr(model, "roi_head", None)
+        if getattr(model, "point_head", None) is not None:
+            raise L.PcdError(f"CapturedInference: the model has a point_head ({type(model.point_head).__name__}): "
+                             "point-based second stages are not supported")
+        if roi_head is not None and not (type(roi_head) is SECONDHead and isinstance(head, AnchorHeadSingle)):
+            raise L.PcdError(f"CapturedInference: the model has a roi_head ({type(roi_head).__name__}) behind a "
+                             f"{type(head).__name__}: the only two-stage detector supported is a fused SECONDHead behind a "
+                             "fused AnchorHeadSingle (adopt_model(model) first)")
         if type(head).__name__ == "AnchorHeadMulti" and not isinstance(head, AnchorHeadMulti):
             raise L.PcdError("CapturedInference: the dense head is an AnchorHeadMulti that is not com_amd.hotpath's (the stock "
                              "class has no static post-processing): adopt_model(model) first")
@@ -61,7 +72,7 @@ class CapturedInference:
             raise L.PcdError("CapturedInference: adopt_model(model) first")
         if report.unrecognised:
             raise L.PcdError(f"CapturedInference: the model has modules adopt_model() left unfused: {report.unrecognised}")
-        self.post_cfg = None
+        self.post_cfg = self.proposal_cfg = self.class_names = None
         if isinstance(head, BoxDecodeMixin):
             postprocess.static_settings(head)                # (refuses circle_nms / oversize K before anything runs)
         elif isinstance(head, (AnchorHeadSingle, AnchorHeadMulti)):
@@ -69,7 +80,20 @@ class CapturedInference:
             if self.post_cfg is None:
                 raise L.PcdError("CapturedInference: an anchor-head detector needs model.model_cfg.POST_PROCESSING")
             # (refuse before anything runs: the single head MULTI_CLASSES_NMS, the multi head its absence; oversize K)
-            if isinstance(head, AnchorHeadMulti):
+            if roi_head is not None:
+                # both settings blocks of the two-stage path: the RoI head's proposals, the detector's final NMS
+                self.proposal_cfg = _get(_get(roi_head.model_cfg, "NMS_CONFIG"), "TEST")
+                postprocess.roi_proposal_settings(self.proposal_cfg)
+                s = postprocess.roi_static_settings(self.post_cfg, second_iou=True)
+                if s["score_type"] == "num_pts_iou_cls":
+                    raise L.PcdError("CapturedInference: NMS_CONFIG.SCORE_TYPE = 'num_pts_iou_cls' is not supported (it counts "
+                                     "batch_dict['points'] rows with a batch column; the in-graph voxeliser hands the model "
+                                     "none)")
+                if int(_get(self.proposal_cfg, "NMS_POST_MAXSIZE")) > L.POSTPROC_MAX_K:
+                    raise L.PcdError(f"CapturedInference: roi_head NMS_CONFIG.TEST.NMS_POST_MAXSIZE above the cap "
+                                     f"{L.POSTPROC_MAX_K} (the RoI rows of a frame are sorted in LDS)")
+                self.class_names = list(getattr(model, "class_names", None) or getattr(head, "class_names", []))
+            elif isinstance(head, AnchorHeadMulti):
                 postprocess.anchor_multi_static_settings(self.post_cfg)
             else:
                 postprocess.anchor_static_settings(self.post_cfg)
@@ -94,6 +118,9 @@ class CapturedInference:
         bd["static_predictions"] = True
         if self.post_cfg is not None:
             bd["post_process_cfg"] = self.post_cfg
+        if self.proposal_cfg is not None:
+            bd["static_proposal_cfg"] = self.proposal_cfg
+            bd["class_names"] = self.class_names
         with torch.no_grad():
             modules = getattr(self.model, "module_list", None)
             if modules is None:
@@ -103,7 +130,7 @@ class CapturedInference:
                 for m in modules:
                     bd = m(bd)
         if "final_box_tensors" not in bd:
-            raise L.PcdError("CapturedInference: the dense head did not produce final_box_tensors")
+            raise L.PcdError("CapturedInference: the heads did not produce final_box_tensors")
         return bd["final_box_tensors"]
 
     def _drop_packs_ahead(self):

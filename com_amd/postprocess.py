@@ -38,7 +38,21 @@ then class order inside the head).  Per (frame, class) the elements are the head
 row order of batch_cls_preds[h]); score = fp32 sigmoid of the class logit; score >= SCORE_THRESH passes (inclusive, a NaN
 never); order: score descending, then i ascending; the first min(NMS_PRE_MAXSIZE, passing) are decoded (the arithmetic of
 pcd_anchor_multi_decode) and go through NMS; an anchor selected under two classes of a head appears twice, as in the
-reference; labels through multihead_label_mapping."""
+reference; labels through multihead_label_mapping.
+
+The two-stage counterparts (a RoI head behind an AnchorHeadSingle; com_amd/csrc/roi_proposals.hip) replace the two host loops
+of a RoI head's eval forward:
+
+    prop = anchor_proposals_static(head, cls_preds, box_preds, dir_cls_preds, nms_config)      # ROI_HEAD.NMS_CONFIG.TEST
+    static = roi_predictions_static(batch_dict, post_process_cfg, class_names, second_iou)
+
+The first is RoIHeadTemplate.proposal_layer (roi_head_template.py:45-102) straight from the anchor head's maps: `rois`
+[B, POST, 7], `roi_scores` [B, POST] (the anchor's maximum LOGIT, its own bits -- no sigmoid), `roi_labels` [B, POST] (1-based,
+the lowest class at the maximum) and `count` [B]; no score threshold, a NaN never takes part, score descending then anchor
+index, rows behind count are boxes 0 / scores 0 / labels 1 as the reference leaves them.  The second is the final
+post-processing over ALL R RoI rows of a frame (detector3d_template.py:178-290 with roi_labels: score type 'rcnn'; or
+second_net_iou.py:75-177: the five SCORE_TYPEs, both quirks of the reference kept): the same dict layout as above plus
+`cls_scores` / `iou_scores` [B, M] for SECOND-IoU, which `to_pred_dicts` returns as pred_cls_scores / pred_iou_scores."""
 import ctypes
 
 import torch
@@ -318,9 +332,239 @@ def anchor_multi_predictions_static(head, cls_maps, box_maps, dir_maps, post_pro
     return out
 
 
+class PcdAnchorProposalsConfig(ctypes.Structure):
+    """include/pcd_ops.h: struct PcdAnchorProposalsConfig (NMS_CONFIG.TEST of a RoI head + the anchor head's shapes); the
+    mirror lives beside its one user."""
+    _fields_ = [("batch", ctypes.c_int), ("height", ctypes.c_int), ("width", ctypes.c_int), ("n_kinds", ctypes.c_int),
+                ("n_classes", ctypes.c_int), ("num_class", ctypes.c_int), ("num_dir_bins", ctypes.c_int),
+                ("nms_pre", ctypes.c_int), ("nms_post", ctypes.c_int), ("nms_normal", ctypes.c_int),
+                ("nms_thresh", ctypes.c_float), ("dir_offset", ctypes.c_float), ("dir_limit_offset", ctypes.c_float)]
+
+
+def _nms_keys(nms, what):
+    """the four NMS keys of an NMS_CONFIG block and the refusals every static path shares; PcdError naming the key"""
+    if nms is None:
+        raise L.PcdError(f"{what}: no NMS_CONFIG block")
+    if _get(nms, 'MULTI_CLASSES_NMS', False):
+        raise L.PcdError(f"{what}: NMS_CONFIG.MULTI_CLASSES_NMS = True is not supported (class-agnostic NMS only)")
+    kind = _get(nms, 'NMS_TYPE', None)
+    if kind not in NMS_TYPES:
+        raise L.PcdError(f"{what}: NMS_TYPE {kind!r} (supported: {sorted(NMS_TYPES)})")
+    s = dict(nms_pre=int(_get(nms, 'NMS_PRE_MAXSIZE')), nms_post=int(_get(nms, 'NMS_POST_MAXSIZE')),
+             nms_thresh=float(_get(nms, 'NMS_THRESH')), nms_normal=NMS_TYPES[kind])
+    if s["nms_pre"] > L.POSTPROC_MAX_K:
+        raise L.PcdError(f"{what}: NMS_PRE_MAXSIZE = {s['nms_pre']} above the cap {L.POSTPROC_MAX_K} (the per-frame sort runs in "
+                         "LDS)")
+    for key, v in (("NMS_PRE_MAXSIZE", s["nms_pre"]), ("NMS_POST_MAXSIZE", s["nms_post"])):
+        if v < 1:
+            raise L.PcdError(f"{what}: {key} = {v}")
+    return s
+
+
+def roi_proposal_settings(nms_config):
+    """One block of a RoI head's NMS_CONFIG (TEST) as pcd_anchor_proposals takes it; PcdError naming the key for what the
+    static proposal layer refuses: MULTI_CLASSES_NMS, other NMS types, NMS_PRE_MAXSIZE above the LDS cap (the 9000 of the
+    TRAIN blocks: the training forward keeps the eager proposal_layer), sizes below 1."""
+    return _nms_keys(nms_config, "static proposal layer")
+
+
+def anchor_proposals_static(head, cls_preds, box_preds, dir_cls_preds, nms_config):
+    """RoIHeadTemplate.proposal_layer (roi_head_template.py:45-102) straight from the prediction maps of an
+    AnchorHeadSingle (`head`: its anchor tables; the maps as anchor_predictions_static takes them), one call into
+    pcd_anchor_proposals: no [B, N, 7] and no [B, N, num_class] tensor.  Per frame: an anchor's score is the maximum of its
+    num_class LOGITS (no sigmoid; bf16 widened first), its label the lowest class index at the maximum, + 1; every anchor
+    takes part but one whose maximum is NaN; the first min(NMS_PRE_MAXSIZE, N) by score descending, then anchor index
+    n = (y * W + x) * A + kind ascending, are decoded (the arithmetic of pcd_anchor_decode) and go through NMS on columns 0:7;
+    the first NMS_POST_MAXSIZE survivors are kept.  Returns {'rois' f32 [B, POST, 7], 'roi_scores' f32 [B, POST],
+    'roi_labels' int64 [B, POST], 'count' int32 [B]}; rows behind count are what the reference leaves there: boxes 0,
+    scores 0, labels 1."""
+    from .hotpath.anchor_head import _strides3
+    what = "static proposal layer"
+    s = roi_proposal_settings(nms_config)
+    maps = [cls_preds, box_preds, dir_cls_preds]
+    if any(m is not None and not (torch.is_tensor(m) and m.is_cuda) for m in maps) or cls_preds is None or box_preds is None:
+        raise L.PcdError(f"{what} needs HIP device tensors (there is no CPU fallback)")
+    if cls_preds.dtype not in (torch.float32, torch.bfloat16):
+        raise L.PcdError(f"{what}: prediction maps of dtype {cls_preds.dtype} (f32 / bf16)")
+    if any(m is not None and (m.dtype != cls_preds.dtype or m.dim() != 4 or m.shape[:3] != cls_preds.shape[:3]) for m in maps):
+        raise L.PcdError(f"{what}: the three prediction maps must share dtype and [B, H, W]")
+    tab = head.tables(cls_preds.device)
+    if (cls_preds.shape[1], cls_preds.shape[2]) != (tab.H, tab.W) or cls_preds.shape[3] != tab.A * tab.num_class \
+            or box_preds.shape[3] != tab.A * 7 or (dir_cls_preds is not None and dir_cls_preds.shape[3] != tab.A * tab.num_dir_bins):
+        raise L.PcdError(f"{what}: prediction maps {tuple(cls_preds.shape)} / {tuple(box_preds.shape)} do not match the "
+                         f"{tab.H} x {tab.W} x {tab.A} anchors")
+    B = int(cls_preds.shape[0])
+    cfg = PcdAnchorProposalsConfig()
+    cfg.batch, cfg.height, cfg.width, cfg.n_kinds, cfg.n_classes = B, tab.H, tab.W, tab.A, tab.C
+    cfg.num_class, cfg.num_dir_bins = tab.num_class, tab.num_dir_bins
+    cfg.nms_pre, cfg.nms_post, cfg.nms_normal, cfg.nms_thresh = s["nms_pre"], s["nms_post"], s["nms_normal"], s["nms_thresh"]
+    cfg.dir_offset, cfg.dir_limit_offset = tab.dir_offset, tab.dir_limit_offset
+    lib = L.lib()
+    cp = ctypes.cast(ctypes.pointer(cfg), ctypes.c_void_p)
+    nbytes = int(lib.pcd_anchor_proposals_workspace_bytes(cp))
+    if nbytes == 0:
+        raise L.PcdError(f"{what}: configuration refused by pcd_anchor_proposals (include/pcd_ops.h)")
+    dev, M = cls_preds.device, s["nms_post"]
+    out = {"rois": torch.empty((B, M, 7), dtype=torch.float32, device=dev),
+           "roi_scores": torch.empty((B, M), dtype=torch.float32, device=dev),
+           "roi_labels": torch.empty((B, M), dtype=torch.int64, device=dev),
+           "count": torch.empty((B,), dtype=torch.int32, device=dev)}
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    L.check(lib.pcd_anchor_proposals(L.ptr(cls_preds), L.ptr(box_preds), L.ptr(dir_cls_preds), L.dtype_code(cls_preds),
+                                     _strides3(maps), L.ptr(tab.kinds), L.ptr(tab.shifts), cp, L.ptr(out["rois"]),
+                                     L.ptr(out["roi_scores"]), L.ptr(out["roi_labels"]), L.ptr(out["count"]), L.ptr(ws), nbytes,
+                                     L.stream_ptr()), "pcd_anchor_proposals")
+    return out
+
+
+class PcdRoiPostprocConfig(ctypes.Structure):
+    """include/pcd_ops.h: struct PcdRoiPostprocConfig (POST_PROCESSING of a two-stage detector + the RoI head's shapes); the
+    mirror lives beside its one user."""
+    _fields_ = [("batch", ctypes.c_int), ("rois", ctypes.c_int), ("score_type", ctypes.c_int), ("normalized", ctypes.c_int),
+                ("has_class_labels", ctypes.c_int), ("num_class", ctypes.c_int),
+                ("by_class_iou", ctypes.c_int * L.PCD_POSTPROC_MAX_CLASSES), ("nms_pre", ctypes.c_int),
+                ("nms_post", ctypes.c_int), ("nms_normal", ctypes.c_int), ("use_score_thresh", ctypes.c_int),
+                ("score_thresh", ctypes.c_float), ("nms_thresh", ctypes.c_float), ("weight_iou", ctypes.c_float),
+                ("weight_cls", ctypes.c_float), ("pts_cls_thresh", ctypes.c_float), ("pts_iou_thresh", ctypes.c_float),
+                ("pts_span", ctypes.c_float)]
+
+
+ROI_SCORE_TYPES = {"rcnn": L.PCD_ROIPP_SCORE_RCNN, "iou": L.PCD_ROIPP_SCORE_IOU, "cls": L.PCD_ROIPP_SCORE_CLS,
+                   "weighted_iou_cls": L.PCD_ROIPP_SCORE_WEIGHTED, "score_by_class": L.PCD_ROIPP_SCORE_BY_CLASS,
+                   "num_pts_iou_cls": L.PCD_ROIPP_SCORE_NUM_PTS}
+
+
+def roi_static_settings(post_process_cfg, second_iou):
+    """The POST_PROCESSING block of a two-stage detector as pcd_roi_postproc takes it.  second_iou False: the class-agnostic
+    branch of Detector3DTemplate.post_processing (score type 'rcnn': the sigmoid of the RoI head's one logit); True:
+    SECONDNetIoU.post_processing with NMS_CONFIG.SCORE_TYPE ('iou' when the key is absent) and the keys that type reads
+    (SCORE_WEIGHTS.iou / .cls, SCORE_BY_CLASS per class name -- checked against `class_names` at the call --,
+    NMS_CONFIG.SCORE_THRESH.cls / .iou).  PcdError naming the key for what the static path refuses: MULTI_CLASSES_NMS,
+    OUTPUT_RAW_SCORE, an unknown NMS_TYPE / SCORE_TYPE, SCORE_BY_CLASS missing, NMS_PRE_MAXSIZE above the LDS cap, sizes
+    below 1."""
+    what = "static RoI post-processing"
+    if post_process_cfg is None:
+        raise L.PcdError(f"{what}: no POST_PROCESSING block")
+    nms = _get(post_process_cfg, 'NMS_CONFIG', None)
+    s = _nms_keys(nms, what)
+    if _get(post_process_cfg, 'OUTPUT_RAW_SCORE', False):
+        raise L.PcdError(f"{what}: OUTPUT_RAW_SCORE = True is not supported")
+    s["score_thresh"] = _get(post_process_cfg, 'SCORE_THRESH', None)
+    s["score_type"] = "rcnn"
+    s["weights"], s["by_class"], s["pts"] = (0.0, 0.0), None, (0.0, 0.0)
+    if second_iou:
+        kind = _get(nms, 'SCORE_TYPE', None)
+        kind = 'iou' if kind is None else kind
+        if kind not in ROI_SCORE_TYPES or kind == "rcnn":
+            raise L.PcdError(f"{what}: NMS_CONFIG.SCORE_TYPE = {kind!r} is not supported (supported: "
+                             f"{[k for k in ROI_SCORE_TYPES if k != 'rcnn']})")
+        s["score_type"] = kind
+        if kind == 'weighted_iou_cls':
+            w = _get(nms, 'SCORE_WEIGHTS', None)
+            if w is None or _get(w, 'iou', None) is None or _get(w, 'cls', None) is None:
+                raise L.PcdError(f"{what}: NMS_CONFIG.SCORE_WEIGHTS (.iou, .cls) missing beside SCORE_TYPE = 'weighted_iou_cls'")
+            s["weights"] = (float(_get(w, 'iou')), float(_get(w, 'cls')))
+        elif kind == 'score_by_class':
+            by = _get(nms, 'SCORE_BY_CLASS', None)
+            if not by:
+                raise L.PcdError(f"{what}: NMS_CONFIG.SCORE_BY_CLASS missing beside SCORE_TYPE = 'score_by_class'")
+            for name in by:
+                if _get(by, name) not in ('iou', 'cls'):
+                    raise L.PcdError(f"{what}: NMS_CONFIG.SCORE_BY_CLASS.{name} = {_get(by, name)!r} is not supported "
+                                     "(supported: 'iou', 'cls')")
+            s["by_class"] = {name: _get(by, name) for name in by}
+        elif kind == 'num_pts_iou_cls':
+            t = _get(nms, 'SCORE_THRESH', None)
+            if t is None or _get(t, 'cls', None) is None or _get(t, 'iou', None) is None:
+                raise L.PcdError(f"{what}: NMS_CONFIG.SCORE_THRESH (.cls, .iou) missing beside SCORE_TYPE = 'num_pts_iou_cls'")
+            s["pts"] = (_get(t, 'cls'), _get(t, 'iou'))
+            if not s["pts"][1] >= s["pts"][0]:
+                raise L.PcdError(f"{what}: NMS_CONFIG.SCORE_THRESH.iou = {s['pts'][1]} below .cls = {s['pts'][0]} (the "
+                                 "reference asserts)")
+    return s
+
+
+def roi_predictions_static(batch_dict, post_process_cfg, class_names=None, second_iou=False):
+    """The final post-processing of a two-stage detector from the RoI head's eval outputs in `batch_dict`
+    (batch_box_preds [B, R, 7], batch_cls_preds [B, R, 1], cls_preds_normalized, roi_labels + has_class_labels; with
+    second_iou also roi_scores and, for SCORE_TYPE 'num_pts_iou_cls', `points` or ready `roi_point_counts` int32 [B, R]), one
+    call into pcd_roi_postproc.  All R rows take part, the zero rows behind the proposal count included.  Returns {'boxes'
+    [B, M, 7], 'scores' [B, M] (the NMS score), 'labels' [B, M], 'count' [B]} and with second_iou 'cls_scores' / 'iou_scores'
+    [B, M]; M = NMS_POST_MAXSIZE, rows behind count are zero.  Order: score descending, then RoI row ascending; a row passes
+    iff score >= SCORE_THRESH (inclusive; every row without one; a NaN never)."""
+    what = "static RoI post-processing"
+    s = roi_static_settings(post_process_cfg, second_iou)
+    if batch_dict.get('batch_index', None) is not None:
+        raise L.PcdError(f"{what}: batch_index (stacked predictions) is not supported; the RoI heads write [B, R, .] predictions")
+    boxes, iou = batch_dict['batch_box_preds'], batch_dict['batch_cls_preds']
+    has_labels = bool(batch_dict.get('has_class_labels', False))
+    tensors = [boxes, iou] + ([batch_dict['roi_scores']] if second_iou else []) + ([batch_dict['roi_labels']] if has_labels else [])
+    if any(not (torch.is_tensor(t) and t.is_cuda) for t in tensors):
+        raise L.PcdError(f"{what} needs HIP device tensors (there is no CPU fallback)")
+    if boxes.dim() != 3 or boxes.shape[2] != 7 or iou.dim() != 3 or iou.shape[2] != 1 or iou.shape[:2] != boxes.shape[:2]:
+        raise L.PcdError(f"{what}: batch_box_preds {tuple(boxes.shape)}, batch_cls_preds {tuple(iou.shape)}; want [B, R, 7] and "
+                         "[B, R, 1]")
+    B, R = int(boxes.shape[0]), int(boxes.shape[1])
+    if R > L.POSTPROC_MAX_K or R < 1 or B < 1:
+        raise L.PcdError(f"{what}: {R} RoIs per frame (1 .. {L.POSTPROC_MAX_K}: the per-frame sort runs in LDS), batch {B}")
+    cfg = PcdRoiPostprocConfig()
+    cfg.batch, cfg.rois, cfg.score_type = B, R, ROI_SCORE_TYPES[s["score_type"]]
+    cfg.normalized, cfg.has_class_labels = int(bool(batch_dict.get('cls_preds_normalized', False))), int(has_labels)
+    counts = None
+    if s["score_type"] == 'score_by_class':
+        names = list(class_names or [])
+        if not 1 <= len(names) <= L.PCD_POSTPROC_MAX_CLASSES:
+            raise L.PcdError(f"{what}: SCORE_TYPE 'score_by_class' needs class_names (1 .. {L.PCD_POSTPROC_MAX_CLASSES})")
+        for c, name in enumerate(names):
+            if name not in s["by_class"]:
+                raise L.PcdError(f"{what}: NMS_CONFIG.SCORE_BY_CLASS.{name} missing")
+            cfg.by_class_iou[c] = int(s["by_class"][name] == 'iou')
+        cfg.num_class = len(names)
+    elif s["score_type"] == 'num_pts_iou_cls':
+        counts = batch_dict.get('roi_point_counts', None)
+        if counts is None:
+            from .hotpath.second_head import points_in_boxes_count
+            counts = points_in_boxes_count(batch_dict['points'], boxes)
+        if not counts.is_cuda or counts.dtype != torch.int32 or tuple(counts.shape) != (B, R):
+            raise L.PcdError(f"{what}: roi_point_counts {tuple(counts.shape)} {counts.dtype}, want int32 [{B}, {R}] on the device")
+        counts = counts.contiguous()
+        cfg.pts_cls_thresh, cfg.pts_iou_thresh = float(s["pts"][0]), float(s["pts"][1])
+        cfg.pts_span = float(s["pts"][1] - s["pts"][0])
+    cfg.nms_pre, cfg.nms_post, cfg.nms_normal, cfg.nms_thresh = s["nms_pre"], s["nms_post"], s["nms_normal"], s["nms_thresh"]
+    cfg.use_score_thresh = int(s["score_thresh"] is not None)
+    cfg.score_thresh = float(s["score_thresh"]) if s["score_thresh"] is not None else 0.0
+    cfg.weight_iou, cfg.weight_cls = s["weights"]
+    boxes = boxes.detach().float().contiguous()
+    iou = iou.detach().float().contiguous()
+    cls = batch_dict['roi_scores'].detach().float().contiguous() if second_iou else None
+    labels = batch_dict['roi_labels'].detach().long().contiguous() if has_labels else None
+    if (cls is not None and tuple(cls.shape) != (B, R)) or (labels is not None and tuple(labels.shape) != (B, R)):
+        raise L.PcdError(f"{what}: roi_scores / roi_labels are not [{B}, {R}]")
+    lib = L.lib()
+    cp = ctypes.cast(ctypes.pointer(cfg), ctypes.c_void_p)
+    nbytes = int(lib.pcd_roi_postproc_workspace_bytes(cp))
+    if nbytes == 0:
+        raise L.PcdError(f"{what}: configuration refused by pcd_roi_postproc (include/pcd_ops.h)")
+    dev, M = boxes.device, s["nms_post"]
+    out = {"boxes": torch.empty((B, M, 7), dtype=torch.float32, device=dev),
+           "scores": torch.empty((B, M), dtype=torch.float32, device=dev),
+           "labels": torch.empty((B, M), dtype=torch.int64, device=dev),
+           "count": torch.empty((B,), dtype=torch.int32, device=dev)}
+    if second_iou:
+        out["cls_scores"] = torch.empty((B, M), dtype=torch.float32, device=dev)
+        out["iou_scores"] = torch.empty((B, M), dtype=torch.float32, device=dev)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    L.check(lib.pcd_roi_postproc(L.ptr(boxes), L.ptr(iou), L.ptr(cls), L.ptr(labels), L.ptr(counts), cp, L.ptr(out["boxes"]),
+                                 L.ptr(out["scores"]), L.ptr(out["labels"]), L.ptr(out["count"]), L.ptr(out.get("cls_scores")),
+                                 L.ptr(out.get("iou_scores")), L.ptr(ws), nbytes, L.stream_ptr()), "pcd_roi_postproc")
+    return out
+
+
 def to_pred_dicts(static):
-    """The reference's final_box_dicts (pred_boxes, pred_scores, pred_labels per frame) from the padded tensors: one
-    device -> host copy of `count`, then views of each frame's first count rows."""
+    """The reference's final_box_dicts (pred_boxes, pred_scores, pred_labels per frame; pred_cls_scores / pred_iou_scores too
+    when the static dict has them: the record of SECONDNetIoU.post_processing) from the padded tensors: one device -> host
+    copy of `count`, then views of each frame's first count rows."""
     count = static["count"].cpu().tolist()
-    return [{"pred_boxes": static["boxes"][b, :n], "pred_scores": static["scores"][b, :n],
-             "pred_labels": static["labels"][b, :n]} for b, n in enumerate(count)]
+    keys = [("pred_boxes", "boxes"), ("pred_scores", "scores"), ("pred_labels", "labels")]
+    keys += [(k, v) for k, v in (("pred_cls_scores", "cls_scores"), ("pred_iou_scores", "iou_scores")) if v in static]
+    return [{k: static[v][b, :n] for k, v in keys} for b, n in enumerate(count)]

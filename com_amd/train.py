@@ -226,6 +226,9 @@ class CapturedStep:
     def __init__(self, model, model_func, optimizer, voxelize, batch_size, *, lr_scheduler=None, world=1, form="auto",
                  hook_at="conv3", after_update=None, capture=True, margin=1.25, options=None, all_reduce=True,
                  batch_keys=(), max_gt=None):
+        if getattr(model, "roi_head", None) is not None:     # (adopt_model fuses a SECONDHead for inference only)
+            raise ops.L.PcdError(f"CapturedStep: the model has a roi_head ({type(model.roi_head).__name__}): the captured "
+                                 "training step of a two-stage detector is not supported")
         self.model, self.model_func, self.optimizer, self.vox_cfg = model, model_func, optimizer, voxelize
         self.bucket = optimizer.bucket
         self.batch_size, self.world, self.lr_scheduler = int(batch_size), int(world), lr_scheduler

@@ -1,6 +1,6 @@
 """A detector object shaped the way the reference's `Detector3DTemplate.build_networks` builds one (test infrastructure,
 like tools/seam1_model.py): the modules of `module_topology` registered as attributes (`vfe`, `backbone_3d`,
-`map_to_bev_module`, `backbone_2d`, `dense_head`; None where the config has none), `module_list` a plain list of them,
+`map_to_bev_module`, `backbone_2d`, `dense_head`, `roi_head`; None where the config has none), `module_list` a plain list of them,
 a `global_step` buffer, `forward` iterating `module_list` and then `get_training_loss()` reading `self.dense_head`.
 
 Every module is written the way a stock model file is written -- plain torch (`nn.Conv2d`, `nn.BatchNorm2d`, `nn.ReLU`,
@@ -15,6 +15,8 @@ state-dict keys.  `com_amd.adopt.adopt_model` turns such an object into the fuse
                                    POST_PROCESSING on the detector                     (waymo_models/second.yaml)
     build_detector("second_multihead")  the same with AnchorHeadMulti: three one-class heads behind a shared conv,
                                    MULTI_CLASSES_NMS                                   (kitti_models/second_multihead.yaml)
+    build_detector("second_iou")   "second" + the RoI head SECONDHead and the POST_PROCESSING of SECOND-IoU
+                                                                                       (kitti_models/second_iou.yaml)
 """
 import copy
 import types
@@ -505,6 +507,61 @@ class AnchorHeadMulti(nn.Module):
         return data_dict
 
 
+class SECONDHead(nn.Module):
+    """The plain IoU head of SECOND-IoU: `shared_fc_layer` (Conv1d, BatchNorm1d, ReLU[, Dropout] per SHARED_FC width) and
+    `iou_layers` (the same per IOU_FC width, then a Conv1d to one logit) in fp32 torch, xavier-initialised; the proposal
+    layer, the BEV RoI grid pooling and the score rectification of com_amd.hotpath (the eager forms).  Inference only: the
+    stock training half (target layer, IoU loss) is not rebuilt here."""
+
+    def __init__(self, input_channels, model_cfg, num_class=1, point_cloud_range=None, voxel_size=None, **kwargs):
+        super().__init__()
+        self.model_cfg, self.num_class = model_cfg, num_class
+        self.point_cloud_range, self.voxel_size = point_cloud_range, voxel_size
+        pool = model_cfg.ROI_GRID_POOL
+        c = pool.IN_CHANNEL * pool.GRID_SIZE * pool.GRID_SIZE
+        layers = []
+        for k, width in enumerate(model_cfg.SHARED_FC):
+            layers += [nn.Conv1d(c, width, kernel_size=1, bias=False), nn.BatchNorm1d(width), nn.ReLU()]
+            c = width
+            if k != len(model_cfg.SHARED_FC) - 1 and model_cfg.DP_RATIO > 0:
+                layers.append(nn.Dropout(model_cfg.DP_RATIO))
+        self.shared_fc_layer = nn.Sequential(*layers)
+        layers = []
+        for width in model_cfg.IOU_FC:
+            layers += [nn.Conv1d(c, width, kernel_size=1, bias=False), nn.BatchNorm1d(width), nn.ReLU()]
+            c = width
+            if model_cfg.DP_RATIO >= 0 and len(layers) == 3:
+                layers.append(nn.Dropout(model_cfg.DP_RATIO))
+        layers.append(nn.Conv1d(c, 1, kernel_size=1, bias=True))
+        self.iou_layers = nn.Sequential(*layers)
+        for m in self.modules():
+            if isinstance(m, nn.Conv1d):
+                nn.init.xavier_normal_(m.weight)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+
+    def forward(self, batch_dict):
+        from com_amd.hotpath import roi_head as RH
+        from com_amd.hotpath import second_head as SH
+        if self.training:
+            raise NotImplementedError("the stock SECONDHead here is an inference module")
+        RH.RoIHeadTemplate.proposal_layer(self, batch_dict, nms_config=self.model_cfg.NMS_CONFIG.TEST)
+        pool = self.model_cfg.ROI_GRID_POOL
+        pcr, vs = self.point_cloud_range, self.voxel_size
+        pooled = SH.bev_roi_grid_pool(batch_dict['spatial_features_2d'], batch_dict['rois'], pool.GRID_SIZE, pcr[0], pcr[1],
+                                      vs[0] * pool.DOWNSAMPLE_RATIO, vs[1] * pool.DOWNSAMPLE_RATIO)
+        shared = self.shared_fc_layer(pooled.view(pooled.shape[0], -1, 1).float())
+        rcnn_iou = self.iou_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
+        batch_dict['batch_cls_preds'] = rcnn_iou.view(batch_dict['batch_size'], -1, rcnn_iou.shape[-1])
+        batch_dict['batch_box_preds'] = batch_dict['rois']
+        batch_dict['cls_preds_normalized'] = False
+        return batch_dict
+
+    def post_processing(self, batch_dict, post_process_cfg, class_names):
+        from com_amd.hotpath import second_head as SH
+        return SH.post_processing(batch_dict, post_process_cfg, class_names)
+
+
 # ---------------------------------------------------------------------------------------------------------- detector
 class StockDetector(nn.Module):
     """Detector3DTemplate + CenterPoint's forward / get_training_loss.  (tb_dict keeps the losses as device tensors: the
@@ -553,6 +610,10 @@ class StockDetector(nn.Module):
                        'CurriculumCenterHead_x5': CurriculumCenterHead_x5}[cfg.DENSE_HEAD.NAME]
                 m = cls(cfg.DENSE_HEAD, c, self.num_class, self.class_names, info['grid_size'], info['point_cloud_range'],
                         info['voxel_size'], predict_boxes_when_training=False)
+            elif name == 'roi_head' and cfg.get('ROI_HEAD'):
+                m = {'SECONDHead': SECONDHead}[cfg.ROI_HEAD.NAME](
+                    c, cfg.ROI_HEAD, num_class=self.num_class if not cfg.ROI_HEAD.CLASS_AGNOSTIC else 1,
+                    point_cloud_range=[float(v) for v in info['point_cloud_range']], voxel_size=info['voxel_size'])
             if m is not None:
                 module_list.append(m)
             self.add_module(name, m)
@@ -609,15 +670,39 @@ def _second_multihead_model():
     return d
 
 
+def _second_iou_model():
+    """SECOND_MODEL with ROI_HEAD and POST_PROCESSING of kitti_models/second_iou.yaml on the three classes here (detector
+    SECONDNetIoU: AnchorHeadSingle -> SECONDHead, the score rectification of SECONDNetIoU.post_processing)."""
+    d = copy.deepcopy(SECOND_MODEL)
+    d['NAME'] = 'SECONDNetIoU'
+    nms = dict(NMS_TYPE='nms_gpu', MULTI_CLASSES_NMS=False)
+    d['ROI_HEAD'] = dict(
+        NAME='SECONDHead', CLASS_AGNOSTIC=True, SHARED_FC=[256, 256], IOU_FC=[256, 256], DP_RATIO=0.3,
+        NMS_CONFIG=dict(TRAIN=dict(nms, NMS_PRE_MAXSIZE=9000, NMS_POST_MAXSIZE=512, NMS_THRESH=0.8),
+                        TEST=dict(nms, NMS_PRE_MAXSIZE=1024, NMS_POST_MAXSIZE=100, NMS_THRESH=0.7)),
+        ROI_GRID_POOL=dict(GRID_SIZE=7, IN_CHANNEL=512, DOWNSAMPLE_RATIO=8),
+        TARGET_CONFIG=dict(BOX_CODER='ResidualCoder', ROI_PER_IMAGE=128, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=True,
+                           CLS_SCORE_TYPE='roi_iou', CLS_FG_THRESH=0.75, CLS_BG_THRESH=0.25, CLS_BG_THRESH_LO=0.1,
+                           HARD_BG_RATIO=0.8, REG_FG_THRESH=0.55),
+        LOSS_CONFIG=dict(IOU_LOSS='BinaryCrossEntropy', LOSS_WEIGHTS=dict(rcnn_iou_weight=1.0, code_weights=[1.0] * 7)))
+    d['POST_PROCESSING'] = dict(RECALL_THRESH_LIST=[0.3, 0.5, 0.7], SCORE_THRESH=0.1, OUTPUT_RAW_SCORE=False, EVAL_METRIC='kitti',
+                                NMS_CONFIG=dict(MULTI_CLASSES_NMS=False, NMS_TYPE='nms_gpu', NMS_THRESH=0.01,
+                                                NMS_PRE_MAXSIZE=4096, NMS_POST_MAXSIZE=500))
+    return d
+
+
 def model_cfg(kind, com_curriculum=None):
     """MODEL block of waymo_models/centerpoint.yaml (kind "centerpoint"), its 3-D part alone ("3d"), with the COM head
     of com/centercurriculum_*_com.yaml ("com"), of waymo_models/second.yaml ("second"), or that with the multi-head dense
-    head of kitti_models/second_multihead.yaml ("second_multihead"); head hyper-parameters as bench.py uses them."""
+    head of kitti_models/second_multihead.yaml ("second_multihead") or with the RoI head of kitti_models/second_iou.yaml
+    ("second_iou"); head hyper-parameters as bench.py uses them."""
     from com_amd.hotpath import dense2d
     if kind == 'second':
         return _cfg(SECOND_MODEL)
     if kind == 'second_multihead':
         return _cfg(_second_multihead_model())
+    if kind == 'second_iou':
+        return _cfg(_second_iou_model())
     d = {'NAME': 'CenterPoint', 'VFE': {'NAME': 'MeanVFE'}, 'BACKBONE_3D': {'NAME': 'VoxelResBackBone8x'},
          'MAP_TO_BEV': {'NAME': 'HeightCompression', 'NUM_BEV_FEATURES': 256}}
     if kind in ('centerpoint', 'com'):
